@@ -86,7 +86,15 @@ def main():
                     help="measurement of the fallback: LETKF_OPT_STAGED_POLY = 0, every staged point through the eigen stage "
                          "(workgroup Jacobi at orders <= 208, block Jacobi above) instead of the eigen-free route")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: min(affinity, cgroup quota, 16 = the box's CPU share)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; rank 0's domain; "
+                         "a fixed, seeded sample of the grid points, at most 64 MB in all): the inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output (dump_outputs below)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.scaling == "strong":
+        ap.error("--dump-outputs: the weak-scaling path only (--scaling strong keeps its analysis inside bench_tiles.py)")
 
     # --gpus N is the contract; WORLD_SIZE is how the ranks learn it.  Started bare with N > 1 (no torchrun), launch
     # the N ranks as a CHILD process -- before torch or HIP is touched in this one -- and hand back its exit code.
@@ -385,6 +393,14 @@ def main():
         anal_chk = as_
     else:
         w_chk, anal_chk = w, anal
+    if args.dump_outputs and rank == 0:
+        # the local-observation counts the step's own obs_local produced (lists built before the timed steps are inputs)
+        nobs = (nobs_fused if args.lists in ("fused", "pipeline")
+                else w["obs_off"][1:] - w["obs_off"][:-1] if (in_step and not slab_mode) else None)
+        if slab_mode and args.state_slab:       # only the last slab's analysis exists at the end of a step
+            dump_outputs(args.dump_outputs, w_chk, anal_chk, status, nobs, slab_stat["last"][0])
+        else:
+            dump_outputs(args.dump_outputs, w, anal, status, nobs, 0)
     if rank == 0:
         n_mean = w["n_mean"]
         b_alg = bw.alg_bytes_per_solve(n_mean, k, nv)
@@ -485,6 +501,33 @@ def main():
     if rc:
         sys.exit(rc)
     return out
+
+
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: the sample's budget (the promise is at most 64 MB in all)
+DUMP_SEED = 20241015
+
+
+def dump_outputs(path, w, anal, status, nobs, p_base):
+    """--dump-outputs: what the last timed step handed its caller, at a fixed seeded sample of the points of `w` (point p of
+    `w` is point p_base + p of status / nobs) as large as DUMP_BYTES allows:
+      points.npy  the sampled points                         anal.npy  the analysis [nv, k, points] (members 0..k-1: slot
+      status.npy  LETKF_ST_* of each sampled point                     k, the mean, is not written by the path)
+      nobs.npy    its local-observation count (only where the timed step ran obs_local itself)
+    Integers are stored as float64 (exact)."""
+    import numpy as np
+    import torch
+    import bench_workload as bw
+    k, nv, npts = w["k"], w["nv"], w["npts"]
+    ns = min(npts, DUMP_BYTES // (8 * (nv * k + 3)))
+    pts = np.sort(np.random.default_rng(DUMP_SEED).choice(npts, size=ns, replace=False))
+    tp = torch.from_numpy(pts).to(anal.device)
+    out = {"points": pts + p_base, "anal": bw.state_view(w, anal)[:, :k, tp], "status": status[tp + p_base]}
+    if nobs is not None:
+        out["nobs"] = nobs[tp + p_base]
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else a
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def host_threads(requested):

@@ -143,6 +143,49 @@ def golden_inputs(c):
                      rdiag_wloc=bool(c["rdiag_wloc"]), infl=c["infl"], with_det=c["det"])
 
 
+# The C restatement against the reference's own routines (tests/test_oracle_vs_ref.py, tests/test_oracle_search.py): the
+# inputs are generated here, the reference's answers to them are stored in tests/golden/reference_checks.npz
+# (tests/golden/make_golden.py), so that the comparisons run wherever the repository is checked out.
+REF_CORE_SHAPES = [(2, 1), (5, 3), (20, 500), (50, 200), (50, 49), (64, 64), (100, 30)]
+REF_CORE_MODES = [(True, True, True), (False, False, False)]      # (rdiag_wloc, infl_update, det)
+REF_EIGEN_SIZES = [2, 7, 50, 120]
+REF_SELECT_SIZES = [(10, 3), (200, 25), (1000, 100), (57, 56), (5, 5)]
+
+
+def ref_core_name(k, n, wloc, iu, det):
+    return f"core/k{k}_n{n}_w{int(wloc)}_iu{int(iu)}_d{int(det)}"
+
+
+def ref_core_inputs(k, n, wloc, det):
+    return core_case(k, n, seed=4242 + 7 * k + n, nobs=n + 3, rdiag_wloc=wloc, infl=1.05, with_det=det)
+
+
+def ref_eigen_input(n):
+    """A symmetric positive definite n x n matrix (mtx_eigen's input)."""
+    rng = np.random.default_rng(n)
+    m = rng.standard_normal((n, 3 * n))
+    return m @ m.T + n * np.eye(n)
+
+
+def ref_select_inputs():
+    """[(n, K, keys a, candidate indices x)] for the quick-select comparison, one stream for all sizes."""
+    rng = np.random.default_rng(3)
+    out = []
+    for n, K in REF_SELECT_SIZES:
+        a = rng.standard_normal(4 * n)
+        x = rng.choice(4 * n, size=n, replace=False).astype(np.int32)
+        out.append((n, K, a, x))
+    return out
+
+
+def array_sha(*arrays):
+    """Digest of the inputs a stored answer belongs to (a drifted generator must fail, not compare other problems)."""
+    h = hashlib.sha256()
+    for v in arrays:
+        h.update(np.ascontiguousarray(v).tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
+
+
 def probes(k):
     """Fixed probe vectors used to pin k x k outputs too large to store."""
     rng = np.random.default_rng(777 + k)

@@ -1,12 +1,15 @@
 """CPU checks of the oracle's obs_local restatement (scale/letkf/letkf_tools.f90:1325-1759): against a brute-force
 search over ALL observations (no sorting mesh), and of the selection semantics against the reference's own
-QUICKSELECT_arg / QUICKSELECT_desc_arg (common/common_sort.f90:341,404) compiled into oracle/_ref."""
+QUICKSELECT_arg / QUICKSELECT_desc_arg (common/common_sort.f90:341,404), whose selections are stored in
+tests/golden/reference_checks.npz (tests/golden/make_golden.py)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
 import _oracle
+from _cases import array_sha, ref_select_inputs
 from _search import build_case, oracle_lists
 
 DZ = float(np.float32(3.651483717))
@@ -69,20 +72,15 @@ def test_oracle_obs_local_vs_brute_force(max_nobs, criterion):
     assert nz > 200
 
 
-@pytest.mark.skipif(_oracle.ref() is None, reason="oracle/_ref not built")
 @pytest.mark.parametrize("desc", [0, 1])
 def test_select_matches_reference_quickselect(desc):
-    rng = np.random.default_rng(3)
-    lib, ref = _oracle.oracle(), _oracle.ref()
-    for n, K in [(10, 3), (200, 25), (1000, 100), (57, 56), (5, 5)]:
-        a = rng.standard_normal(4 * n)
-        x = rng.choice(4 * n, size=n, replace=False).astype(np.int32)
-        x_ref = (x + 1).astype(np.int32)      # Fortran indices
-        ref.ref_quickselect_arg(C.c_int(a.size), a.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(n),
-                                x_ref.ctypes.data_as(C.POINTER(C.c_int)), C.c_int(1), C.c_int(n), C.c_int(K),
-                                C.c_int(desc))
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checks.npz"))
+    lib = _oracle.oracle()
+    for n, K, a, x in ref_select_inputs():
+        nm = f"select/d{desc}_n{n}_K{K}"
+        assert np.array_equal(array_sha(a, x), ref[nm + "/sha"]), "input generator drifted from the committed fixture"
         x_orc = x.copy()
         lib.orc_select_arg(a.ctypes.data_as(C.POINTER(C.c_double)), x_orc.ctypes.data_as(C.POINTER(C.c_int32)),
                            C.c_int(n), C.c_int(K), C.c_int(desc))
-        assert set((x_ref[:K] - 1).tolist()) == set(x_orc[:K].tolist())
+        assert set(ref[nm + "/first"].tolist()) == set(x_orc[:K].tolist())
         assert sorted(x_orc.tolist()) == sorted(x.tolist())
