@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LETKF_AMD_ABI_VERSION 7
+#define LETKF_AMD_ABI_VERSION 8
 
 /* host-side errors (function return values) */
 #define LETKF_OK 0
@@ -583,6 +583,135 @@ int letkf_allreduce_sum_i32_dev(letkf_ctx *ctx, void *nccl_comm, int32_t nranks,
 int letkf_members_alltoall_dev(letkf_ctx *ctx, void *nccl_comm, int32_t nranks, int32_t myrank, int32_t dir, int32_t nlev,
                                int32_t nlon, int32_t nlat, int32_t nv3d, int32_t mstart, int32_t mcount, double *v3dg, double *x,
                                int64_t sp, int64_t sm, int64_t sv);
+
+/*---------------------------------------------------------------------------
+ * (9, ABI 8) set_letkf_obs behind one call (scale/letkf/letkf_obs.f90:142-1145 as PROGRAM letkf calls it,
+ *     letkf.f90:142): the observation table stays on the device and letkf_das_columns_dev reads it through
+ *     letkf_obs_table_search.  Two halves around the reference's exchanges, and one call for a single rank:
+ *       local half   pre-processing of the obs files (:268-305), combined-type tables (:307-342), sorting-mesh sizes
+ *                    (:657-677), row gather + departure + QC (:361-561), count tables (:744-760), bucket sort (:762-822)
+ *                    and the rank's sorted send buffer (obsbufs, :993-1010)
+ *       [the host exchanges: MPI_ALLREDUCE of the cell counts / tot_sub (:826-833, letkf_allreduce_sum_i32_dev) and the
+ *        ALLGATHERV of the send buffers (:1036-1046, letkf_obs_allgatherv_dev) -- or its own MPI]
+ *       finish half  extended-subdomain plan (:922-976) and the assembly of obsda_sort + the metadata (:1036-1100)
+ *     Observation files and obsda are read by the host (read_obs_all / obsope, out of scope); the observation files
+ *     are the SAME on every rank (as in the reference: every rank reads them all).  Not covered: the member-sliced
+ *     ensval of nprocs_e > 1 (:994-1004), LOG_LEVEL >= 3 prints, DEPARTURE_STAT_H08, NOBS_OUT files.
+ *-------------------------------------------------------------------------*/
+#define LETKF_NID_OBS 16   /* nid_obs, common_nml.f90:21: uid_obs() numbers the 16 element ids of common_obs_scale.f90:74-77 */
+
+typedef struct {
+  int32_t nobtype;                  /* report types (nobtype = 24, common_nml.f90:22); 1..32 */
+  int32_t use_obserr_radar_ref;     /* USE_OBSERR_RADAR_REF */
+  int32_t use_obserr_radar_vr;      /* USE_OBSERR_RADAR_VR */
+  int32_t nlon, nlat;               /* subdomain interior size */
+  int32_t ihalo, jhalo;             /* IHALO, JHALO */
+  int32_t nprocs, prc_num_x, myrank;   /* nprocs_d, PRC_NUM_X, myrank_d: rank r at (mod(r, prc_num_x), r / prc_num_x) */
+  int32_t fix_ij_obsgrd;            /* as letkf_mesh.fix_ij_obsgrd */
+  int32_t criterion;                /* MAX_NOBS_PER_GRID_CRITERION (letkf_search_tables.criterion) */
+  double min_radar_ref_dbz;         /* MIN_RADAR_REF_DBZ; MIN_RADAR_REF = 10**(MIN_RADAR_REF_DBZ/10) (common_obs_scale.f90:251) */
+  double low_ref_shift;             /* LOW_REF_SHIFT */
+  double obserr_radar_ref, obserr_radar_vr;                  /* OBSERR_RADAR_REF, OBSERR_RADAR_VR */
+  double hori_local_radar_obsnoref, hori_local_radar_vr;    /* resolved as common_nml.f90:772-780 does (< 0 there: HORI_LOCAL(22)) */
+  double vert_local_radar_vr;                               /* ... (< 0 there: VERT_LOCAL(22)) */
+  double dx, dy;                    /* DX, DY */
+  double rain_base;                 /* VERT_LOCAL_RAIN_BASE (letkf_search_tables.rain_base) */
+  const double *hori_local, *vert_local;                   /* HOST [nobtype]: HORI_LOCAL, VERT_LOCAL */
+  const double *obs_sort_grid_spacing, *obs_min_spacing;   /* HOST [nobtype]: OBS_SORT_GRID_SPACING, OBS_MIN_SPACING */
+  const int32_t *max_nobs_per_grid;                        /* HOST [nobtype]: MAX_NOBS_PER_GRID */
+  const int32_t *ctype_merge;       /* HOST column-major (LETKF_NID_OBS, nobtype), > 0 = merge class (letkf_ctype_merge_groups), or NULL */
+} letkf_setobs_params;
+
+/* The observation files, flattened into one row space: file f (0-based, OBS_IN_NUM = nfile) owns rows off[f] .. off[f+1]-1,
+ * obs(f+1)%{elm,typ,lev,dat,err,ri,rj}(n) = row off[f] + n - 1.  elm, dat and err are pre-processed IN PLACE (:268-305). */
+typedef struct {
+  int32_t nfile;
+  int32_t reserved0;
+  const int64_t *off;               /* HOST [nfile + 1] */
+  int32_t *elm;                     /* dev [off[nfile]] INOUT */
+  const int32_t *typ;               /* dev: report type, 1..nobtype */
+  const double *lev;                /* dev */
+  double *dat, *err;                /* dev INOUT */
+  const double *ri, *rj;            /* dev: global grid coordinates */
+} letkf_obs_file_rows;
+
+/* The table a set_letkf_obs call leaves behind.  Owned by the library, released with letkf_obs_table_destroy; every
+ * pointer below stays valid until then.  HOST arrays are the library's copies, dev arrays live on the context's GPU. */
+typedef struct letkf_obs_table letkf_obs_table;
+
+typedef struct {
+  int32_t nctype;                   /* combined types (:315) */
+  int32_t kld;                      /* doubles per ensval row: MEMBER (+1 with DET_RUN) */
+  int32_t finished;                 /* 1 once the finish half ran */
+  int32_t nobtype;
+  int64_t nobs;                     /* local H(x) rows (obsda%nobs) */
+  int64_t nsorted;                  /* accepted local rows = rows of the send buffer */
+  int64_t ncell;                    /* sum of ngrd_i * ngrd_j: entries of n_cell */
+  int64_t nacx;                     /* entries of ac_ext */
+  int64_t nobstotal;                /* rows of obsda_sort (finish half) */
+  int64_t ld_send;                  /* doubles per send-buffer row: kld + 4 */
+  const int32_t *elm_ctype, *elm_u_ctype, *typ_ctype;     /* HOST [nctype] (:315-342; elm_u_ctype, typ_ctype 1-based) */
+  const double *hori_loc_ctype, *vert_loc_ctype;          /* HOST [nctype] */
+  const int32_t *ctype_elmtyp;      /* HOST column-major (LETKF_NID_OBS, nobtype): 1-based ctype or 0 */
+  const int32_t *ngrd_i, *ngrd_j, *ngrdsch_i, *ngrdsch_j, *ngrdext_i, *ngrdext_j;   /* HOST [nctype] (:657-677) */
+  const double *grdspc_i, *grdspc_j;                      /* HOST [nctype] */
+  const int64_t *ac_off;            /* HOST [nctype]: start of every ctype inside ac_ext */
+  const int32_t *tot_sub, *tot_g;   /* HOST [nctype][2]: obsgrd%tot_sub / tot_g, [ic*2] before QC, [ic*2+1] after QC (:744-760, :833);
+                                       tot_g is filled by the finish half */
+  const int32_t *n_cell;            /* dev [ncell]: obsgrd%n(:,:,myrank), ctypes concatenated */
+  const int32_t *key;               /* dev [nsorted]: obsda%key, 0-based rows */
+  const double *sendbuf;            /* dev [nsorted][ld_send]: row = ensval(1:kld) | val | lev | set | idx of the sorted row */
+  const int32_t *row_elm, *row_ctype;   /* dev [nobs]: obs(set)%elm(idx) after pre-processing, 0-based ctype */
+  const double *row_dat, *row_err, *row_ri, *row_rj, *row_lev;   /* dev [nobs]: obs(set)%...(idx) */
+  const double *val;                /* dev [nobs]: obsda%val after the departure (rows with qc /= 0: untouched zeros) */
+  const double *ensval;             /* dev [nobstotal][kld]: obsda_sort%ensval */
+  const double *val_sort;           /* dev [nobstotal]: obsda_sort%val */
+  const int32_t *qc_sort;           /* dev [nobstotal]: obsda_sort%qc */
+} letkf_obs_table_info;
+
+/* Sorting-mesh sizes, letkf_obs.f90:657-677, HOST only (no device needed): per combined type the target spacing from
+ * OBS_SORT_GRID_SPACING(typ) > 0, else MAX_NOBS_PER_GRID(typ) > 0 (0.1 sqrt(MAX_NOBS_PER_GRID) OBS_MIN_SPACING), else
+ * hori_loc * dist_zero_fac / 6 -- dist_zero_fac the single-precision literal of :27 -- and from it ngrd_* (clamped to nlon / nlat),
+ * grdspc_*, ngrdsch_* and ngrdext_*, in the reference's double arithmetic.  typ_ctype 1-based; outputs [nctype]. */
+int letkf_obs_mesh_dims(int32_t nctype, const int32_t *typ_ctype, const double *hori_loc_ctype, int32_t nobtype,
+                        const double *obs_sort_grid_spacing, const int32_t *max_nobs_per_grid, const double *obs_min_spacing,
+                        double dx, double dy, int32_t nlon, int32_t nlat, int32_t *ngrd_i, int32_t *ngrd_j, double *grdspc_i,
+                        double *grdspc_j, int32_t *ngrdsch_i, int32_t *ngrdsch_j, int32_t *ngrdext_i, int32_t *ngrdext_j);
+
+/* The local half.  qcp: departure + QC (section 5; qcp->h08_lev / h08_val2 are per obsda row).  files: their device arrays must
+ * stay allocated until the finish half has run.  Argument checks that need no device come first; the file rows are pre-processed
+ * IN PLACE before the rows are checked on the device, so after a refusal of a file row (element / type) or of an obsda row
+ * (set / idx outside the files) the reflectivities of `files` may already be converted: do not retry on the same arrays.  obsda as obsope leaves it: set / idx (dev [nobs], 1-based file and row), qc (dev INOUT), ensval (dev
+ * INOUT [nobs][kld], member-fastest; becomes the perturbations).  Creates *tab.  Synchronises the stream. */
+int letkf_set_obs_local_dev(letkf_ctx *ctx, const letkf_setobs_params *p, const letkf_qc_params *qcp,
+                            const letkf_obs_file_rows *files, int64_t nobs,
+                            const int32_t *set, const int32_t *idx, int32_t *qc, double *ensval, int64_t kld,
+                            letkf_obs_table **tab);
+
+/* The finish half.  n_all: dev [nprocs][ncell], every rank's n_cell (the all-gather / all-reduce of obsgrd%n, :826-831);
+ * tot_g: dev [nctype][2], the all-reduce-sum of every rank's tot_sub, or NULL (= this rank's tot_sub); recv: dev [nrecv][ld_send],
+ * every rank's send buffer, rank-major (the ALLGATHERV receive buffer); nrecv must equal the total of n_all.  Fills the
+ * obsda_sort columns and the search tables.  Synchronises the stream. */
+int letkf_set_obs_finish_dev(letkf_ctx *ctx, letkf_obs_table *tab, const int32_t *n_all, const int32_t *tot_g, int64_t nrecv,
+                             const double *recv);
+
+/* Both halves for one rank (p->nprocs = 1): CALL set_letkf_obs. */
+int letkf_set_obs_dev(letkf_ctx *ctx, const letkf_setobs_params *p, const letkf_qc_params *qcp, const letkf_obs_file_rows *files,
+                      int64_t nobs,
+                      const int32_t *set, const int32_t *idx, int32_t *qc, double *ensval, int64_t kld, letkf_obs_table **tab);
+
+int letkf_obs_table_info_get(const letkf_obs_table *tab, letkf_obs_table_info *info);
+/* The table as letkf_das_columns_dev / letkf_obs_search_*_dev read it (after the finish half): every pointer a device copy the
+ * handle owns; groups from p->ctype_merge, vmode from (elm, typ) as das_letkf derives it (letkf_tools.f90:1851-1865), max_nobs =
+ * MAX_NOBS_PER_GRID(typ), limit_hint set, varloc = 1 until letkf_obs_table_set_varloc. */
+int letkf_obs_table_search(const letkf_obs_table *tab, letkf_search_tables *tables);
+/* varloc: HOST [nctype], var_local(n2n, uid_obs_varlocal(elm_ctype)) of the variable class about to be analysed. */
+int letkf_obs_table_set_varloc(letkf_ctx *ctx, letkf_obs_table *tab, const double *varloc);
+/* Copies obsda_sort and its metadata to HOST arrays (each may be NULL): ensval [nobstotal][kld], val, qc [nobstotal],
+ * ob_ri, ob_rj, ob_lev, ob_dat, ob_err [nobstotal], ac_ext [nacx].  Synchronises the stream. */
+int letkf_obs_table_download(letkf_ctx *ctx, const letkf_obs_table *tab, double *ensval, double *val, int32_t *qc, double *ob_ri,
+                             double *ob_rj, double *ob_lev, double *ob_dat, double *ob_err, int32_t *ac_ext);
+int letkf_obs_table_destroy(letkf_obs_table *tab);
 
 /* Name(s) of the kernel(s) the context's last letkf_das_points*_dev / letkf_core_batch_dev call went through, as a
  * NUL-terminated string (truncated to len): what bench.py reports as roofline.kernel. */

@@ -98,6 +98,128 @@ class HaloLayout(C.Structure):
                 ("ngrd_i", C.c_void_p), ("ngrd_j", C.c_void_p), ("ngrdsch_i", C.c_void_p), ("ngrdsch_j", C.c_void_p)]
 
 
+class SetObsParams(C.Structure):
+    """letkf_setobs_params (include/letkf_amd.h section 9); the per-report-type arrays are HOST arrays"""
+    _fields_ = [("nobtype", C.c_int32), ("use_obserr_radar_ref", C.c_int32), ("use_obserr_radar_vr", C.c_int32),
+                ("nlon", C.c_int32), ("nlat", C.c_int32), ("ihalo", C.c_int32), ("jhalo", C.c_int32),
+                ("nprocs", C.c_int32), ("prc_num_x", C.c_int32), ("myrank", C.c_int32), ("fix_ij_obsgrd", C.c_int32),
+                ("criterion", C.c_int32), ("min_radar_ref_dbz", C.c_double), ("low_ref_shift", C.c_double),
+                ("obserr_radar_ref", C.c_double), ("obserr_radar_vr", C.c_double),
+                ("hori_local_radar_obsnoref", C.c_double), ("hori_local_radar_vr", C.c_double),
+                ("vert_local_radar_vr", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("rain_base", C.c_double),
+                ("hori_local", C.c_void_p), ("vert_local", C.c_void_p), ("obs_sort_grid_spacing", C.c_void_p),
+                ("obs_min_spacing", C.c_void_p), ("max_nobs_per_grid", C.c_void_p), ("ctype_merge", C.c_void_p)]
+
+
+class ObsFileRows(C.Structure):
+    """letkf_obs_file_rows (section 9): off is a HOST int64 array, the rest device pointers"""
+    _fields_ = [("nfile", C.c_int32), ("reserved0", C.c_int32), ("off", C.c_void_p), ("elm", C.c_void_p),
+                ("typ", C.c_void_p), ("lev", C.c_void_p), ("dat", C.c_void_p), ("err", C.c_void_p), ("ri", C.c_void_p),
+                ("rj", C.c_void_p)]
+
+
+class ObsTableInfo(C.Structure):
+    """letkf_obs_table_info (section 9)"""
+    _fields_ = ([("nctype", C.c_int32), ("kld", C.c_int32), ("finished", C.c_int32), ("nobtype", C.c_int32)] +
+                [(n, C.c_int64) for n in ("nobs", "nsorted", "ncell", "nacx", "nobstotal", "ld_send")] +
+                [(n, C.c_void_p) for n in ("elm_ctype", "elm_u_ctype", "typ_ctype", "hori_loc_ctype", "vert_loc_ctype",
+                                           "ctype_elmtyp", "ngrd_i", "ngrd_j", "ngrdsch_i", "ngrdsch_j", "ngrdext_i",
+                                           "ngrdext_j", "grdspc_i", "grdspc_j", "ac_off", "tot_sub", "tot_g", "n_cell",
+                                           "key", "sendbuf", "row_elm", "row_ctype", "row_dat", "row_err", "row_ri",
+                                           "row_rj", "row_lev", "val", "ensval", "val_sort", "qc_sort")])
+
+
+def obs_mesh_dims(typ_ctype, hori_loc_ctype, obs_sort_grid_spacing, max_nobs_per_grid, obs_min_spacing, dx, dy, nlon, nlat):
+    """letkf_obs_mesh_dims (host only).  Returns dict of numpy arrays ngrd_i .. ngrdext_j, grdspc_i / grdspc_j."""
+    import numpy as np
+    ty = np.ascontiguousarray(typ_ctype, dtype=np.int32)
+    hl = np.ascontiguousarray(hori_loc_ctype, dtype=np.float64)
+    sp = np.ascontiguousarray(obs_sort_grid_spacing, dtype=np.float64)
+    mx = np.ascontiguousarray(max_nobs_per_grid, dtype=np.int32)
+    ms = np.ascontiguousarray(obs_min_spacing, dtype=np.float64)
+    nc = len(ty)
+    o = {n: np.zeros(max(nc, 1), dtype=np.int32) for n in ("ngrd_i", "ngrd_j", "ngrdsch_i", "ngrdsch_j", "ngrdext_i", "ngrdext_j")}
+    o["grdspc_i"], o["grdspc_j"] = np.zeros(max(nc, 1)), np.zeros(max(nc, 1))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib().letkf_obs_mesh_dims(C.c_int32(nc), p(ty), p(hl), C.c_int32(len(sp)), p(sp), p(mx), p(ms), C.c_double(dx),
+                                   C.c_double(dy), C.c_int32(nlon), C.c_int32(nlat), p(o["ngrd_i"]), p(o["ngrd_j"]),
+                                   p(o["grdspc_i"]), p(o["grdspc_j"]), p(o["ngrdsch_i"]), p(o["ngrdsch_j"]),
+                                   p(o["ngrdext_i"]), p(o["ngrdext_j"]))
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_obs_mesh_dims: {rc}: {lib().letkf_amd_last_error().decode()}")
+    return {k: v[:nc].copy() for k, v in o.items()}
+
+
+class ObsTable:
+    """A library-owned set_letkf_obs table (letkf_obs_table); released by close() / garbage collection."""
+
+    def __init__(self, ctx, handle, keep):
+        self._ctx, self._h, self._keep = ctx, handle, keep
+
+    def close(self):
+        if self._h:
+            self._ctx._l.letkf_obs_table_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        i = ObsTableInfo()
+        self._ctx._check(self._ctx._l.letkf_obs_table_info_get(self._h, C.byref(i)))
+        return i
+
+    def host(self):
+        """The small host tables and counts as numpy arrays."""
+        import numpy as np
+        i = self.info()
+        nc = i.nctype
+
+        def arr(ptr, ctype, n):
+            if n == 0 or not ptr:
+                return np.zeros(0, dtype=ctype)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(ctype))), (n,)).copy()
+        out = dict(nctype=nc, nobs=i.nobs, nsorted=i.nsorted, ncell=i.ncell, nacx=i.nacx, nobstotal=i.nobstotal,
+                   kld=i.kld, ld_send=i.ld_send)
+        for n in ("elm_ctype", "elm_u_ctype", "typ_ctype", "ngrd_i", "ngrd_j", "ngrdsch_i", "ngrdsch_j", "ngrdext_i",
+                  "ngrdext_j"):
+            out[n] = arr(getattr(i, n), np.int32, nc)
+        for n in ("hori_loc_ctype", "vert_loc_ctype", "grdspc_i", "grdspc_j"):
+            out[n] = arr(getattr(i, n), np.float64, nc)
+        out["ac_off"] = arr(i.ac_off, np.int64, nc)
+        out["ctype_elmtyp"] = arr(i.ctype_elmtyp, np.int32, 16 * i.nobtype).reshape(i.nobtype, 16)
+        out["tot_sub"] = arr(i.tot_sub, np.int32, 2 * nc).reshape(nc, 2)
+        out["tot_g"] = arr(i.tot_g, np.int32, 2 * nc).reshape(nc, 2) if i.tot_g else None
+        return out
+
+    def search_tables(self):
+        t = SearchTables()
+        self._ctx._check(self._ctx._l.letkf_obs_table_search(self._h, C.byref(t)))
+        return t
+
+    def set_varloc(self, varloc):
+        import numpy as np
+        v = np.ascontiguousarray(varloc, dtype=np.float64)
+        self._ctx._check(self._ctx._l.letkf_obs_table_set_varloc(self._ctx._c, self._h, v.ctypes.data_as(C.c_void_p)))
+
+    def download(self):
+        """obsda_sort and the metadata as numpy arrays (letkf_obs_table_download)."""
+        import numpy as np
+        i = self.info()
+        nt, kld = i.nobstotal, i.kld
+        o = dict(ensval=np.zeros((max(nt, 1), kld)), val=np.zeros(max(nt, 1)), qc=np.zeros(max(nt, 1), np.int32),
+                 ob_ri=np.zeros(max(nt, 1)), ob_rj=np.zeros(max(nt, 1)), ob_lev=np.zeros(max(nt, 1)),
+                 ob_dat=np.zeros(max(nt, 1)), ob_err=np.zeros(max(nt, 1)), ac_ext=np.zeros(max(i.nacx, 1), np.int32))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ctx._check(self._ctx._l.letkf_obs_table_download(
+            self._ctx._c, self._h, p(o["ensval"]), p(o["val"]), p(o["qc"]), p(o["ob_ri"]), p(o["ob_rj"]), p(o["ob_lev"]),
+            p(o["ob_dat"]), p(o["ob_err"]), p(o["ac_ext"])))
+        return {k: (v[:i.nacx] if k == "ac_ext" else v[:nt]) for k, v in o.items()}
+
+
 class StateConsts(C.Structure):
     """letkf_state_consts (include/letkf_amd.h section 4)"""
     _fields_ = [("rdry", C.c_double), ("rvap", C.c_double), ("cvdry", C.c_double), ("pre00", C.c_double),
@@ -142,6 +264,9 @@ EXPORTS = ["letkf_amd_abi_version", "letkf_amd_last_error", "letkf_ctx_create", 
            "letkf_var_local_classes", "letkf_ctype_merge_groups", "letkf_radar_only", "letkf_relax_beta_dev",
            "letkf_infl_init_dev", "letkf_obs_allgatherv_dev", "letkf_alltoallv_dev", "letkf_allreduce_sum_i32_dev",
            "letkf_members_alltoall_dev",
+           "letkf_obs_mesh_dims", "letkf_set_obs_local_dev", "letkf_set_obs_finish_dev", "letkf_set_obs_dev",
+           "letkf_obs_table_info_get", "letkf_obs_table_search", "letkf_obs_table_set_varloc", "letkf_obs_table_download",
+           "letkf_obs_table_destroy",
            "letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path", "letkf_sched_plan_check", "letkf_sched_plan_check_units"]
 
 _lib = None
@@ -366,6 +491,27 @@ class Context:
     def obs_gather_i32(self, src_row, src, dst):
         self._check(self._l.letkf_obs_gather_i32_dev(self._c, C.c_int64(src_row.numel()), _ptr(src_row), _ptr(src),
                                                      _ptr(dst)))
+
+    # ---- (9) set_letkf_obs behind one call
+    def _setobs_args(self, params, qcp, files, set_, idx, qc, ensval, kld):
+        return (self._c, C.byref(params), C.byref(qcp), C.byref(files), C.c_int64(set_.numel()), _ptr(set_), _ptr(idx), _ptr(qc),
+                _ptr(ensval), C.c_int64(kld))
+
+    def set_obs(self, params, qcp, files, set_, idx, qc, ensval, kld, keep=()):
+        """letkf_set_obs_dev (one rank).  `keep`: objects the table's file rows / params depend on."""
+        h = C.c_void_p()
+        self._check(self._l.letkf_set_obs_dev(*self._setobs_args(params, qcp, files, set_, idx, qc, ensval, kld), C.byref(h)))
+        return ObsTable(self, h, keep)
+
+    def set_obs_local(self, params, qcp, files, set_, idx, qc, ensval, kld, keep=()):
+        h = C.c_void_p()
+        self._check(self._l.letkf_set_obs_local_dev(*self._setobs_args(params, qcp, files, set_, idx, qc, ensval, kld), C.byref(h)))
+        return ObsTable(self, h, keep)
+
+    def set_obs_finish(self, table, n_all, recv, tot_g=None):
+        nrecv = recv.shape[0] if recv is not None else 0
+        self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g), C.c_int64(nrecv),
+                                                     _ptr(recv)))
 
     # ---- (6) after the loop
     def monit_dep(self, elem_uid, elm, dep, qc):

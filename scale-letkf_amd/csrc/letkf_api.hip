@@ -1226,6 +1226,85 @@ int letkf_obs_gather_i32_dev(letkf_ctx* c, int64_t nrows, const int32_t* src_row
   return LETKF_OK;
 }
 
+int letkf_obs_mesh_dims(int32_t nctype, const int32_t* typ_ctype, const double* hori_loc_ctype, int32_t nobtype,
+                        const double* obs_sort_grid_spacing, const int32_t* max_nobs_per_grid, const double* obs_min_spacing,
+                        double dx, double dy, int32_t nlon, int32_t nlat, int32_t* ngrd_i, int32_t* ngrd_j, double* grdspc_i,
+                        double* grdspc_j, int32_t* ngrdsch_i, int32_t* ngrdsch_j, int32_t* ngrdext_i, int32_t* ngrdext_j) {
+  if (nctype < 0 || nobtype < 1 || nlon < 1 || nlat < 1) return fail(LETKF_E_INVALID, "bad sizes");
+  if (nctype > 0 && (!typ_ctype || !hori_loc_ctype || !obs_sort_grid_spacing || !max_nobs_per_grid || !obs_min_spacing ||
+                     !ngrd_i || !ngrd_j || !grdspc_i || !grdspc_j || !ngrdsch_i || !ngrdsch_j || !ngrdext_i || !ngrdext_j))
+    return fail(LETKF_E_INVALID, "an array is NULL");
+  if (letkf::obs_mesh_dims(nctype, typ_ctype, hori_loc_ctype, nobtype, obs_sort_grid_spacing, max_nobs_per_grid,
+                           obs_min_spacing, dx, dy, nlon, nlat, ngrd_i, ngrd_j, grdspc_i, grdspc_j, ngrdsch_i, ngrdsch_j,
+                           ngrdext_i, ngrdext_j))
+    return fail(LETKF_E_INVALID, "a report type outside 1..nobtype or an empty mesh");
+  return LETKF_OK;
+}
+
+int letkf_set_obs_local_dev(letkf_ctx* c, const letkf_setobs_params* p, const letkf_qc_params* qcp, const letkf_obs_file_rows* files,
+                            int64_t nobs, const int32_t* set, const int32_t* idx, int32_t* qc, double* ensval, int64_t kld,
+                            letkf_obs_table** tab) {
+  if (int rc = check_ctx(c)) return rc;
+  std::string msg;
+  if (int rc = letkf::set_obs_local(c->device, c->stream, c->num_cu, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab, &msg))
+    return fail(rc, msg);
+  return LETKF_OK;
+}
+
+int letkf_set_obs_finish_dev(letkf_ctx* c, letkf_obs_table* tab, const int32_t* n_all, const int32_t* tot_g, int64_t nrecv,
+                             const double* recv) {
+  if (int rc = check_ctx(c)) return rc;
+  std::string msg;
+  if (int rc = letkf::set_obs_finish(c->stream, c->num_cu, tab, n_all, tot_g, nrecv, recv, &msg)) return fail(rc, msg);
+  return LETKF_OK;
+}
+
+int letkf_set_obs_dev(letkf_ctx* c, const letkf_setobs_params* p, const letkf_qc_params* qcp, const letkf_obs_file_rows* files,
+                      int64_t nobs, const int32_t* set, const int32_t* idx, int32_t* qc, double* ensval, int64_t kld,
+                      letkf_obs_table** tab) {
+  if (!p || p->nprocs != 1) return fail(LETKF_E_INVALID, "letkf_set_obs_dev is the one-rank call: nprocs must be 1");
+  if (int rc = letkf_set_obs_local_dev(c, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab)) return rc;
+  letkf_obs_table_info i;
+  letkf::obs_table_info(*tab, &i);
+  if (int rc = letkf_set_obs_finish_dev(c, *tab, i.n_cell, nullptr, i.nsorted, i.sendbuf)) {
+    letkf_obs_table_destroy(*tab);
+    *tab = nullptr;
+    return rc;
+  }
+  return LETKF_OK;
+}
+
+int letkf_obs_table_info_get(const letkf_obs_table* tab, letkf_obs_table_info* info) {
+  if (letkf::obs_table_info(tab, info)) return fail(LETKF_E_INVALID, "tab / info is NULL");
+  return LETKF_OK;
+}
+
+int letkf_obs_table_search(const letkf_obs_table* tab, letkf_search_tables* tables) {
+  if (letkf::obs_table_search(tab, tables)) return fail(LETKF_E_INVALID, "tab / tables is NULL or the finish half has not run");
+  return LETKF_OK;
+}
+
+int letkf_obs_table_set_varloc(letkf_ctx* c, letkf_obs_table* tab, const double* varloc) {
+  if (int rc = check_ctx(c)) return rc;
+  std::string msg;
+  if (int rc = letkf::obs_table_set_varloc(c->stream, tab, varloc, &msg)) return fail(rc, msg);
+  return LETKF_OK;
+}
+
+int letkf_obs_table_download(letkf_ctx* c, const letkf_obs_table* tab, double* ensval, double* val, int32_t* qc, double* ob_ri,
+                             double* ob_rj, double* ob_lev, double* ob_dat, double* ob_err, int32_t* ac_ext) {
+  if (int rc = check_ctx(c)) return rc;
+  std::string msg;
+  double* ob[5] = {ob_ri, ob_rj, ob_lev, ob_dat, ob_err};
+  if (int rc = letkf::obs_table_download(c->stream, tab, ensval, val, qc, ob, ac_ext, &msg)) return fail(rc, msg);
+  return LETKF_OK;
+}
+
+int letkf_obs_table_destroy(letkf_obs_table* tab) {
+  letkf::obs_table_destroy(tab);
+  return LETKF_OK;
+}
+
 int letkf_monit_dep_dev(letkf_ctx* c, int32_t nid, const int32_t* elem_uid, int64_t nn, const int32_t* elm,
                         const double* dep, const int32_t* qc, int32_t* nobs, double* bias, double* rmse) {
   if (int rc = check_ctx(c)) return rc;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/letkf_amd.h"
 
 namespace letkf {
@@ -232,5 +234,22 @@ hipError_t launch_member_points(int dir, int nlev, int nlon, long nxy, int nv3d,
 hipError_t launch_ens_spread(int k, int nv, long npts, const double* x, long sp, long sm, long sv, double* sprd,
                              hipStream_t st);
 hipError_t launch_ens_mean(int k, int nv, long npts, double* x, long sp, long sm, long sv, hipStream_t st);
+// set_letkf_obs behind one call (letkf_setobs.hip); int results are LETKF_OK / LETKF_E_*, *msg says why
+int obs_mesh_dims(int nctype, const int* typ_ctype, const double* hori_loc_ctype, int nobtype, const double* spacing,
+                  const int* max_nobs, const double* min_spacing, double dx, double dy, int nlon, int nlat, int* ngrd_i,
+                  int* ngrd_j, double* grdspc_i, double* grdspc_j, int* ngrdsch_i, int* ngrdsch_j, int* ngrdext_i,
+                  int* ngrdext_j);
+int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_params* p, const letkf_qc_params* qcp,
+                  const letkf_obs_file_rows* f,
+                  long nobs, const int* set, const int* idx, int* qc, double* ensval, long kld, letkf_obs_table** out,
+                  std::string* msg);
+int set_obs_finish(hipStream_t st, int num_cu, letkf_obs_table* t, const int* n_all, const int* tot_g, long nrecv,
+                   const double* recv, std::string* msg);
+int obs_table_search(const letkf_obs_table* t, letkf_search_tables* s);
+int obs_table_set_varloc(hipStream_t st, letkf_obs_table* t, const double* varloc, std::string* msg);
+int obs_table_info(const letkf_obs_table* t, letkf_obs_table_info* i);
+void obs_table_destroy(letkf_obs_table* t);
+int obs_table_download(hipStream_t st, const letkf_obs_table* t, double* ensval, double* val, int* qc, double* ob[5],
+                       int* ac_ext, std::string* msg);
 
 }  // namespace letkf

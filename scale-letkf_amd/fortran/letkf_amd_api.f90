@@ -85,6 +85,36 @@ MODULE letkf_amd_api
     TYPE(c_ptr)        :: ngrd_i, ngrd_j, ngrdsch_i, ngrdsch_j   ! HOST [nctype]
   END TYPE letkf_halo_layout
 
+  ! section 9 (ABI 8): set_letkf_obs behind one call
+  INTEGER, PARAMETER :: letkf_nid_obs = 16
+
+  TYPE, BIND(C) :: letkf_setobs_params
+    INTEGER(c_int32_t) :: nobtype, use_obserr_radar_ref, use_obserr_radar_vr
+    INTEGER(c_int32_t) :: nlon, nlat, ihalo, jhalo
+    INTEGER(c_int32_t) :: nprocs, prc_num_x, myrank, fix_ij_obsgrd, criterion
+    REAL(c_double)     :: min_radar_ref_dbz, low_ref_shift, obserr_radar_ref, obserr_radar_vr
+    REAL(c_double)     :: hori_local_radar_obsnoref, hori_local_radar_vr, vert_local_radar_vr
+    REAL(c_double)     :: dx, dy, rain_base
+    TYPE(c_ptr)        :: hori_local, vert_local, obs_sort_grid_spacing, obs_min_spacing   ! HOST [nobtype]
+    TYPE(c_ptr)        :: max_nobs_per_grid, ctype_merge                                  ! HOST
+  END TYPE letkf_setobs_params
+
+  TYPE, BIND(C) :: letkf_obs_file_rows
+    INTEGER(c_int32_t) :: nfile, reserved0
+    TYPE(c_ptr)        :: off                                                 ! HOST int64 [nfile + 1]
+    TYPE(c_ptr)        :: elm, typ, lev, dat, err, ri, rj                     ! dev
+  END TYPE letkf_obs_file_rows
+
+  TYPE, BIND(C) :: letkf_obs_table_info
+    INTEGER(c_int32_t) :: nctype, kld, finished, nobtype
+    INTEGER(c_int64_t) :: nobs, nsorted, ncell, nacx, nobstotal, ld_send
+    TYPE(c_ptr)        :: elm_ctype, elm_u_ctype, typ_ctype, hori_loc_ctype, vert_loc_ctype, ctype_elmtyp   ! HOST
+    TYPE(c_ptr)        :: ngrd_i, ngrd_j, ngrdsch_i, ngrdsch_j, ngrdext_i, ngrdext_j, grdspc_i, grdspc_j  ! HOST
+    TYPE(c_ptr)        :: ac_off, tot_sub, tot_g                                                         ! HOST
+    TYPE(c_ptr)        :: n_cell, key, sendbuf, row_elm, row_ctype, row_dat, row_err, row_ri, row_rj, row_lev   ! dev
+    TYPE(c_ptr)        :: val, ensval, val_sort, qc_sort                                                  ! dev
+  END TYPE letkf_obs_table_info
+
   INTERFACE
     ! das_letkf set-up (scale/letkf/letkf_tools.f90:130-267, relax_beta :1911-1948); the first three are host functions
     FUNCTION letkf_var_local_classes(nvar, nlt, var_local, n2nc, n2n, nclass) &
@@ -369,6 +399,74 @@ MODULE letkf_amd_api
     FUNCTION hipFree(ptr) BIND(C, name='hipFree') RESULT(rc)
       IMPORT :: c_int, c_ptr
       TYPE(c_ptr), VALUE :: ptr
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_mesh_dims(nctype, typ_ctype, hori_loc_ctype, nobtype, obs_sort_grid_spacing, max_nobs_per_grid, &
+                                 obs_min_spacing, dx, dy, nlon, nlat, ngrd_i, ngrd_j, grdspc_i, grdspc_j, ngrdsch_i, &
+                                 ngrdsch_j, ngrdext_i, ngrdext_j) BIND(C, name='letkf_obs_mesh_dims') RESULT(rc)
+      IMPORT :: c_int, c_int32_t, c_double
+      INTEGER(c_int32_t), VALUE :: nctype, nobtype, nlon, nlat
+      INTEGER(c_int32_t), INTENT(IN) :: typ_ctype(*), max_nobs_per_grid(*)
+      REAL(c_double), INTENT(IN) :: hori_loc_ctype(*), obs_sort_grid_spacing(*), obs_min_spacing(*)
+      REAL(c_double), VALUE :: dx, dy
+      INTEGER(c_int32_t), INTENT(OUT) :: ngrd_i(*), ngrd_j(*), ngrdsch_i(*), ngrdsch_j(*), ngrdext_i(*), ngrdext_j(*)
+      REAL(c_double), INTENT(OUT) :: grdspc_i(*), grdspc_j(*)
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_set_obs_local_dev(ctx, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab) &
+        BIND(C, name='letkf_set_obs_local_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int64_t, letkf_setobs_params, letkf_qc_params, letkf_obs_file_rows
+      TYPE(c_ptr), VALUE :: ctx, set, idx, qc, ensval
+      TYPE(letkf_setobs_params), INTENT(IN) :: p
+      TYPE(letkf_qc_params), INTENT(IN) :: qcp
+      TYPE(letkf_obs_file_rows), INTENT(IN) :: files
+      INTEGER(c_int64_t), VALUE :: nobs, kld
+      TYPE(c_ptr), INTENT(OUT) :: tab
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_set_obs_finish_dev(ctx, tab, n_all, tot_g, nrecv, recv) BIND(C, name='letkf_set_obs_finish_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int64_t
+      TYPE(c_ptr), VALUE :: ctx, tab, n_all, tot_g, recv
+      INTEGER(c_int64_t), VALUE :: nrecv
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_set_obs_dev(ctx, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab) BIND(C, name='letkf_set_obs_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int64_t, letkf_setobs_params, letkf_qc_params, letkf_obs_file_rows
+      TYPE(c_ptr), VALUE :: ctx, set, idx, qc, ensval
+      TYPE(letkf_setobs_params), INTENT(IN) :: p
+      TYPE(letkf_qc_params), INTENT(IN) :: qcp
+      TYPE(letkf_obs_file_rows), INTENT(IN) :: files
+      INTEGER(c_int64_t), VALUE :: nobs, kld
+      TYPE(c_ptr), INTENT(OUT) :: tab
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_table_info_get(tab, info) BIND(C, name='letkf_obs_table_info_get') RESULT(rc)
+      IMPORT :: c_int, c_ptr, letkf_obs_table_info
+      TYPE(c_ptr), VALUE :: tab
+      TYPE(letkf_obs_table_info), INTENT(OUT) :: info
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_table_search(tab, tables) BIND(C, name='letkf_obs_table_search') RESULT(rc)
+      IMPORT :: c_int, c_ptr, letkf_search_tables
+      TYPE(c_ptr), VALUE :: tab
+      TYPE(letkf_search_tables), INTENT(OUT) :: tables
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_table_set_varloc(ctx, tab, varloc) BIND(C, name='letkf_obs_table_set_varloc') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_double
+      TYPE(c_ptr), VALUE :: ctx, tab
+      REAL(c_double), INTENT(IN) :: varloc(*)
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_table_download(ctx, tab, ensval, val, qc, ob_ri, ob_rj, ob_lev, ob_dat, ob_err, ac_ext) &
+        BIND(C, name='letkf_obs_table_download') RESULT(rc)
+      IMPORT :: c_int, c_ptr
+      TYPE(c_ptr), VALUE :: ctx, tab, ensval, val, qc, ob_ri, ob_rj, ob_lev, ob_dat, ob_err, ac_ext   ! HOST or C_NULL_PTR
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_table_destroy(tab) BIND(C, name='letkf_obs_table_destroy') RESULT(rc)
+      IMPORT :: c_int, c_ptr
+      TYPE(c_ptr), VALUE :: tab
       INTEGER(c_int) :: rc
     END FUNCTION
     FUNCTION hipMemcpy(dst, src, nbytes, kind) BIND(C, name='hipMemcpy') RESULT(rc)

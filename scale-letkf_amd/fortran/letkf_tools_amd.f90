@@ -24,7 +24,7 @@ MODULE letkf_tools_amd
   USE letkf_amd_api
   IMPLICIT NONE
   PRIVATE
-  PUBLIC :: das_letkf_amd, letkf_das_nml, letkf_obs_tables, letkf_vmode
+  PUBLIC :: das_letkf_amd, letkf_das_nml, letkf_obs_tables, letkf_obs_tables_dev, letkf_vmode, letkf_obs_tables_dev_free
 
   INTEGER, PARAMETER :: r_size = c_double
   INTEGER, PARAMETER :: nlt = 9               ! columns of var_local: VAR_LOCAL_UV .. VAR_LOCAL_H08 (letkf_tools.f90:130-138)
@@ -72,7 +72,28 @@ MODULE letkf_tools_amd
     REAL(r_size), ALLOCATABLE :: val(:)                   ! obsda_sort%val
   END TYPE letkf_obs_tables
 
+  ! what set_letkf_obs_amd (letkf_obs_amd.f90) leaves behind: the observation table stays on the device in a library-owned
+  ! handle (include/letkf_amd.h section 9); `host` carries the small per-ctype tables (nctype, nobstotal, nensobs, *_ctype,
+  ! uid_varlocal_ctype, max_nobs_ctype, ngrd_*), its table arrays (ac_ext, ob_*, ensval, val) stay unallocated.
+  ! Released by letkf_obs_tables_dev_free.
+  TYPE :: letkf_obs_tables_dev
+    TYPE(c_ptr) :: handle = c_null_ptr
+    TYPE(letkf_obs_tables) :: host
+  END TYPE letkf_obs_tables_dev
+
+  ! CALL das_letkf_amd(ctx, nml, obs, ...) with a host letkf_obs_tables (uploaded per call) or a letkf_obs_tables_dev (no upload)
+  INTERFACE das_letkf_amd
+    MODULE PROCEDURE das_letkf_amd, das_letkf_amd_dev
+  END INTERFACE das_letkf_amd
+
 CONTAINS
+
+  SUBROUTINE letkf_obs_tables_dev_free(tabd)
+    TYPE(letkf_obs_tables_dev), INTENT(INOUT) :: tabd
+    INTEGER(c_int) :: rc
+    IF (c_associated(tabd%handle)) rc = letkf_obs_table_destroy(tabd%handle)
+    tabd%handle = c_null_ptr
+  END SUBROUTINE letkf_obs_tables_dev_free
 
   ! vertical coordinate of a combined type (obs_local_cal, letkf_tools.f90:1851-1865): 0 |dln p| (obs lev), 1 |dz| (type 22),
   ! 2 ps (obs dat), 3 rain base.  The -DH08 build's report type 23 (H08IRB, :1859-1861) is mode 0 as well: its rows carry
@@ -99,6 +120,42 @@ CONTAINS
     REAL(r_size), INTENT(IN), TARGET :: rig1(nij1), rjg1(nij1), hgt1(nij1, nlev)
     REAL(r_size), INTENT(INOUT), TARGET :: gues3d(nij1, nlev, nens, nv3d)
     REAL(r_size), INTENT(OUT), TARGET :: anal3d(nij1, nlev, nens, nv3d)
+    REAL(r_size), INTENT(IN), OPTIONAL, TARGET :: work3d_in(nij1, nlev, nv3d)
+    REAL(r_size), INTENT(OUT), OPTIONAL, TARGET :: work3d_out(nij1, nlev, nv3d)
+    INTEGER(c_int32_t), INTENT(OUT), OPTIONAL, TARGET :: nobs_point(nij1, nlev)
+    CALL das_body(ctx, nml, obs, c_null_ptr, nij1, nlev, nens, nv3d, rig1, rjg1, hgt1, gues3d, anal3d, work3d_in, work3d_out, &
+                  nobs_point)
+  END SUBROUTINE das_letkf_amd
+
+  ! the same with the observation table on the device (set_letkf_obs_amd): nothing of the table is uploaded
+  SUBROUTINE das_letkf_amd_dev(ctx, nml, tabd, nij1, nlev, nens, nv3d, rig1, rjg1, hgt1, gues3d, anal3d, work3d_in, work3d_out, &
+                               nobs_point)
+    TYPE(c_ptr), INTENT(IN) :: ctx
+    TYPE(letkf_das_nml), INTENT(IN) :: nml
+    TYPE(letkf_obs_tables_dev), INTENT(IN), TARGET :: tabd
+    INTEGER, INTENT(IN) :: nij1, nlev, nens, nv3d
+    REAL(r_size), INTENT(IN), TARGET :: rig1(nij1), rjg1(nij1), hgt1(nij1, nlev)
+    REAL(r_size), INTENT(INOUT), TARGET :: gues3d(nij1, nlev, nens, nv3d)
+    REAL(r_size), INTENT(OUT), TARGET :: anal3d(nij1, nlev, nens, nv3d)
+    REAL(r_size), INTENT(IN), OPTIONAL, TARGET :: work3d_in(nij1, nlev, nv3d)
+    REAL(r_size), INTENT(OUT), OPTIONAL, TARGET :: work3d_out(nij1, nlev, nv3d)
+    INTEGER(c_int32_t), INTENT(OUT), OPTIONAL, TARGET :: nobs_point(nij1, nlev)
+    IF (.NOT. c_associated(tabd%handle)) CALL fail('letkf_obs_tables_dev without a table (call set_letkf_obs_amd first)')
+    CALL das_body(ctx, nml, tabd%host, tabd%handle, nij1, nlev, nens, nv3d, rig1, rjg1, hgt1, gues3d, anal3d, work3d_in, &
+                  work3d_out, nobs_point)
+  END SUBROUTINE das_letkf_amd_dev
+
+  ! the body of both: tab = C_NULL_PTR uploads the host tables of obs, else the device table of the handle is read in place
+  SUBROUTINE das_body(ctx, nml, obs, tab, nij1, nlev, nens, nv3d, rig1, rjg1, hgt1, gues3d, anal3d, work3d_in, work3d_out, &
+                      nobs_point)
+    TYPE(c_ptr), INTENT(IN) :: ctx                        ! letkf_ctx_create
+    TYPE(letkf_das_nml), INTENT(IN) :: nml
+    TYPE(letkf_obs_tables), INTENT(IN), TARGET :: obs
+    TYPE(c_ptr), INTENT(IN) :: tab
+    INTEGER, INTENT(IN) :: nij1, nlev, nens, nv3d
+    REAL(r_size), INTENT(IN), TARGET :: rig1(nij1), rjg1(nij1), hgt1(nij1, nlev)
+    REAL(r_size), INTENT(INOUT), TARGET :: gues3d(nij1, nlev, nens, nv3d)
+    REAL(r_size), INTENT(OUT), TARGET :: anal3d(nij1, nlev, nens, nv3d)
     REAL(r_size), INTENT(IN), OPTIONAL, TARGET :: work3d_in(nij1, nlev, nv3d)    ! INFL_MUL_IN field (INFL_MUL <= 0)
     REAL(r_size), INTENT(OUT), OPTIONAL, TARGET :: work3d_out(nij1, nlev, nv3d)  ! the (adaptively updated) inflation field
     INTEGER(c_int32_t), INTENT(OUT), OPTIONAL, TARGET :: nobs_point(nij1, nlev)  ! local observations of the first class
@@ -117,7 +174,10 @@ CONTAINS
     TYPE(letkf_search_tables) :: t
     TYPE(letkf_beta_params) :: bp
     TYPE(letkf_das_args) :: a
+    TYPE(letkf_search_tables) :: td
+    TYPE(letkf_obs_table_info) :: ti
     INTEGER(c_int32_t) :: mask
+    LOGICAL :: own
 
     k = nml%member
     mmean = k + 1
@@ -156,27 +216,38 @@ CONTAINS
     d_rjg = up(c_loc(rjg1), 8_c_size_t*nij1)
     d_hgt = up(c_loc(hgt1), 8_c_size_t*npts)
     CALL chk(hipMalloc(d_beta, 8_c_size_t*npts), 'hipMalloc beta')
-    d_ens = up(c_loc(obs%ensval), 8_c_size_t*obs%nensobs*MAX(obs%nobstotal, 1))
-    d_val = up(c_loc(obs%val), 8_c_size_t*MAX(obs%nobstotal, 1))
     d_gs = up(c_loc(group_start), 4_c_size_t*(ngroup + 1))
     d_gm = up(c_loc(group_member), 4_c_size_t*MAX(obs%nctype, 1))
     d_vm = up(c_loc(vmode), 4_c_size_t*MAX(obs%nctype, 1))
-    d_hl = up(c_loc(obs%hori_loc_ctype), 8_c_size_t*MAX(obs%nctype, 1))
-    d_vl = up(c_loc(obs%vert_loc_ctype), 8_c_size_t*MAX(obs%nctype, 1))
     d_mx = up(c_loc(mx), 4_c_size_t*MAX(obs%nctype, 1))
-    d_gi = up(c_loc(obs%ngrd_i), 4_c_size_t*MAX(obs%nctype, 1))
-    d_gj = up(c_loc(obs%ngrd_j), 4_c_size_t*MAX(obs%nctype, 1))
-    d_si = up(c_loc(obs%ngrdsch_i), 4_c_size_t*MAX(obs%nctype, 1))
-    d_sj = up(c_loc(obs%ngrdsch_j), 4_c_size_t*MAX(obs%nctype, 1))
-    d_ei = up(c_loc(obs%ngrdext_i), 4_c_size_t*MAX(obs%nctype, 1))
-    d_ej = up(c_loc(obs%ngrdext_j), 4_c_size_t*MAX(obs%nctype, 1))
-    d_aco = up(c_loc(obs%ac_off), 8_c_size_t*MAX(obs%nctype, 1))
-    d_ace = up(c_loc(obs%ac_ext), 4_c_size_t*SIZE(obs%ac_ext))
-    d_ri = up(c_loc(obs%ob_ri), 8_c_size_t*MAX(obs%nobstotal, 1))
-    d_rj = up(c_loc(obs%ob_rj), 8_c_size_t*MAX(obs%nobstotal, 1))
-    d_lev = up(c_loc(obs%ob_lev), 8_c_size_t*MAX(obs%nobstotal, 1))
-    d_dat = up(c_loc(obs%ob_dat), 8_c_size_t*MAX(obs%nobstotal, 1))
-    d_err = up(c_loc(obs%ob_err), 8_c_size_t*MAX(obs%nobstotal, 1))
+    own = .NOT. c_associated(tab)
+    IF (own) THEN
+      d_ens = up(c_loc(obs%ensval), 8_c_size_t*obs%nensobs*MAX(obs%nobstotal, 1))
+      d_val = up(c_loc(obs%val), 8_c_size_t*MAX(obs%nobstotal, 1))
+      d_hl = up(c_loc(obs%hori_loc_ctype), 8_c_size_t*MAX(obs%nctype, 1))
+      d_vl = up(c_loc(obs%vert_loc_ctype), 8_c_size_t*MAX(obs%nctype, 1))
+      d_gi = up(c_loc(obs%ngrd_i), 4_c_size_t*MAX(obs%nctype, 1))
+      d_gj = up(c_loc(obs%ngrd_j), 4_c_size_t*MAX(obs%nctype, 1))
+      d_si = up(c_loc(obs%ngrdsch_i), 4_c_size_t*MAX(obs%nctype, 1))
+      d_sj = up(c_loc(obs%ngrdsch_j), 4_c_size_t*MAX(obs%nctype, 1))
+      d_ei = up(c_loc(obs%ngrdext_i), 4_c_size_t*MAX(obs%nctype, 1))
+      d_ej = up(c_loc(obs%ngrdext_j), 4_c_size_t*MAX(obs%nctype, 1))
+      d_aco = up(c_loc(obs%ac_off), 8_c_size_t*MAX(obs%nctype, 1))
+      d_ace = up(c_loc(obs%ac_ext), 4_c_size_t*SIZE(obs%ac_ext))
+      d_ri = up(c_loc(obs%ob_ri), 8_c_size_t*MAX(obs%nobstotal, 1))
+      d_rj = up(c_loc(obs%ob_rj), 8_c_size_t*MAX(obs%nobstotal, 1))
+      d_lev = up(c_loc(obs%ob_lev), 8_c_size_t*MAX(obs%nobstotal, 1))
+      d_dat = up(c_loc(obs%ob_dat), 8_c_size_t*MAX(obs%nobstotal, 1))
+      d_err = up(c_loc(obs%ob_err), 8_c_size_t*MAX(obs%nobstotal, 1))
+    ELSE                                            ! the library's device table (letkf_obs_table_search): read in place
+      CALL chk(letkf_obs_table_search(tab, td), 'letkf_obs_table_search')
+      CALL chk(letkf_obs_table_info_get(tab, ti), 'letkf_obs_table_info_get')
+      IF (ti%nctype /= obs%nctype .OR. ti%nobstotal /= obs%nobstotal) CALL fail('letkf_obs_tables_dev: host and device tables differ')
+      d_ens = ti%ensval; d_val = ti%val_sort
+      d_hl = td%hori_loc; d_vl = td%vert_loc; d_gi = td%ngrd_i; d_gj = td%ngrd_j; d_si = td%ngrdsch_i; d_sj = td%ngrdsch_j
+      d_ei = td%ngrdext_i; d_ej = td%ngrdext_j; d_aco = td%ac_off; d_ace = td%ac_ext
+      d_ri = td%ob_ri; d_rj = td%ob_rj; d_lev = td%ob_lev; d_dat = td%ob_dat; d_err = td%ob_err
+    END IF
     CALL chk(hipMalloc(d_varloc, 8_c_size_t*MAX(obs%nctype, 1)), 'hipMalloc varloc')
     CALL chk(hipMalloc(d_counts, 4_c_size_t*npts), 'hipMalloc counts')
     CALL chk(hipMalloc(d_status, 4_c_size_t*npts), 'hipMalloc status')
@@ -266,10 +337,10 @@ CONTAINS
     CALL chk(hipMemcpy(c_loc(gues3d), d_gues, nb_state, hipMemcpyDeviceToHost), 'download gues3d')
     IF (PRESENT(work3d_out)) CALL chk(hipMemcpy(c_loc(work3d_out), d_infl, 8_c_size_t*npts*nv3d, hipMemcpyDeviceToHost), &
                                       'download work3d')
-    CALL free_all((/d_gues, d_anal, d_rig, d_rjg, d_hgt, d_beta, d_infl, d_ens, d_val, d_counts, d_status, d_varloc, &
-                    d_gs, d_gm, d_vm, d_hl, d_vl, d_mx, d_gi, d_gj, d_si, d_sj, d_ei, d_ej, d_aco, d_ace, d_ri, d_rj, d_lev, &
-                    d_dat, d_err/))
-  END SUBROUTINE das_letkf_amd
+    CALL free_all((/d_gues, d_anal, d_rig, d_rjg, d_hgt, d_beta, d_infl, d_counts, d_status, d_varloc, d_gs, d_gm, d_vm, d_mx/))
+    IF (own) CALL free_all((/d_ens, d_val, d_hl, d_vl, d_gi, d_gj, d_si, d_sj, d_ei, d_ej, d_aco, d_ace, d_ri, d_rj, d_lev, &
+                             d_dat, d_err/))
+  END SUBROUTINE das_body
 
   ! device pointer + an offset in doubles
   FUNCTION off_ptr(base, ndbl) RESULT(p)
