@@ -102,8 +102,10 @@ int letkf_ctx_set_option(letkf_ctx *ctx, int option, int value);
  *                           transm,pao,rdiag_wloc,infl_update,depd,transmd)
  *     common/common_letkf.f90:52-68.  Absent OPTIONALs are NULL.  hdxb has
  *     leading dimension nobs, only rows 1..nobsl are read (:35-37).  transmd
- *     is computed only when depd AND transmd are given (:188); when transm is
- *     NULL, w-bar is added to every column of trans (:218-226).
+ *     is computed only when depd AND transmd are given (:188); a given transmd
+ *     is zeroed at nobsl == 0 whether depd is given or not (:97-99) and left
+ *     untouched at nobsl > 0 without depd (the batch entry below alike); when
+ *     transm is NULL, w-bar is added to every column of trans (:218-226).
  *     *status receives a LETKF_ST_* code (or a negative LETKF_E_*); NULL allowed.
  *     Thread-safe (the reference is called from inside an OpenMP region,
  *     scale/letkf/letkf_tools.f90:289): uses a per-thread context.
@@ -163,6 +165,9 @@ int letkf_core_batch_dev(letkf_ctx *ctx, const letkf_core_batch_args *args);
  *       alike; the reference's gues3d(nij1,nlev,nens,nv3d) is sp=1,
  *       sm=nij1*nlev, sv=nij1*nlev*nens.  anal slot k (mean) is NOT written
  *       (the reference fills it afterwards with ensmean_grd, letkf.f90:207).
+ *       anal may be gues itself (in place, same answer; at k <= 20 such a call
+ *       takes the one-wave kernel instead of three points per wave); other
+ *       overlaps of gues and anal are not allowed.
  *     infl: work3d(ij,ilev,n) at p + npts*v; INOUT when infl_adaptive.
  *-------------------------------------------------------------------------*/
 typedef struct {
@@ -190,14 +195,17 @@ typedef struct {
   const double *rdiag_l;     /* dev, same length */
   const double *rloc_l;      /* dev, same length */
   const double *ensval;      /* dev [nobs_tot][kld] */
-  int64_t kld;               /* >= k (+1 when det_run) */
+  int64_t kld;               /* >= k (+1 when det_run); only columns 0..k-1 (and k with det_run) are read */
   const double *dep;         /* dev [nobs_tot] */
   const double *beta;        /* dev [npts] or NULL (= 1 everywhere) */
   double *infl;              /* dev [npts*nv] */
   const double *gues;        /* dev */
   double *anal;              /* dev */
   int64_t sp, sm, sv;        /* strides in doubles */
-  double *trans_out;         /* dev [npts][k*k] or NULL (diagnostic / parity) */
+  double *trans_out;         /* dev [npts][k*k] or NULL (diagnostic / parity).  trans_out, transm_out, pa_out: letkf_core's
+                                T, w-bar, Pa at every point with beta != 0 (n = 0: sqrt(infl) I, 0, infl/(k-1) I,
+                                common_letkf.f90:89-107); NOT written at beta = 0 points, where the reference does not call
+                                letkf_core (letkf_tools.f90:333-359) */
   double *transm_out;        /* dev [npts][k] or NULL */
   double *pa_out;            /* dev [npts][k*k] or NULL */
   int32_t *status;           /* dev [npts] or NULL */

@@ -606,17 +606,19 @@ class Context:
 
 
 def letkf_core_host(ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_transm=True, want_pao=True,
-                    rdiag_wloc=None, infl_update=None, depd=None, want_transmd=False):
-    """The host-pointer drop-in letkf_core_c (what the Fortran shim calls), on numpy arrays."""
+                    rdiag_wloc=None, infl_update=None, depd=None, want_transmd=False, fill=0.0,
+                    transmd_without_depd=False):
+    """The host-pointer drop-in letkf_core_c (what the Fortran shim calls), on numpy arrays.  The outputs start as
+    `fill`; transmd is returned only with depd unless transmd_without_depd."""
     import numpy as np
     l = lib()
     dp = C.POINTER(C.c_double)
     f = lambda a: None if a is None else a.ctypes.data_as(dp)
     hdxb = np.asfortranarray(hdxb, dtype=np.float64)
-    trans = np.zeros((ne, ne), order="F")
-    transm = np.zeros(ne) if want_transm else None
-    pao = np.zeros((ne, ne), order="F") if want_pao else None
-    transmd = np.zeros(ne) if want_transmd else None
+    trans = np.full((ne, ne), fill, order="F")
+    transm = np.full(ne, fill) if want_transm else None
+    pao = np.full((ne, ne), fill, order="F") if want_pao else None
+    transmd = np.full(ne, fill) if want_transmd else None
     infl = C.c_double(parm_infl)
     wl = C.c_int(1 if rdiag_wloc else 0)
     iu = C.c_int(1 if infl_update else 0)
@@ -624,7 +626,8 @@ def letkf_core_host(ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_tra
     l.letkf_core_c(C.c_int(ne), C.c_int(nobs), C.c_int(nobsl), f(hdxb), f(rdiag), f(rloc), f(dep), C.byref(infl),
                    f(trans), f(transm), f(pao), C.byref(wl) if rdiag_wloc is not None else None,
                    C.byref(iu) if infl_update is not None else None, f(depd), f(transmd), C.byref(st))
-    return dict(trans=trans, transm=transm, pao=pao, transmd=transmd if depd is not None else None,
+    return dict(trans=trans, transm=transm, pao=pao,
+                transmd=transmd if (depd is not None or transmd_without_depd) else None,
                 parm_infl=infl.value, status=st.value)
 
 

@@ -575,6 +575,16 @@ int letkf_ctx_timing_read(letkf_ctx* c, double* avg_ms, int64_t* nlaunch, int re
   return LETKF_OK;
 }
 
+namespace {
+// transmd without depd: the reference zeroes a present transmd at nobsl == 0 whatever depd is (common_letkf.f90:97-99) and
+// leaves it untouched at nobsl > 0 (:188)
+__global__ void zero_transmd_where_nobsl_is_zero(int64_t nbatch, int ne, const int32_t* __restrict__ nobsl,
+                                                 double* __restrict__ transmd) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nbatch * ne && nobsl[i / ne] == 0) transmd[i] = 0.0;
+}
+}  // namespace
+
 int letkf_core_batch_dev(letkf_ctx* c, const letkf_core_batch_args* g) {
   if (int rc = check_ctx(c)) return rc;
   if (!g) return fail(LETKF_E_INVALID, "args is NULL");
@@ -607,7 +617,14 @@ int letkf_core_batch_dev(letkf_ctx* c, const letkf_core_batch_args* g) {
   a.add_wbar_to_trans = g->transm ? 0 : 1;                    // common_letkf.f90:218-226
   a.status = g->status;
   a.nsweep = g->nsweep;
-  return launch(c, a);
+  if (int rc = launch(c, a)) return rc;
+  if (g->transmd && !g->depd) {
+    const int64_t n = g->nbatch * (int64_t)g->ne;
+    hipLaunchKernelGGL(zero_transmd_where_nobsl_is_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, g->nbatch,
+                       g->ne, g->nobsl, g->transmd);
+    HIP_TRY(hipGetLastError());
+  }
+  return LETKF_OK;
 }
 
 namespace {
@@ -1574,7 +1591,7 @@ int core_host(int ne, int nobs, int nobsl, const double* hdxb, const double* rdi
   g.trans = d_trans;
   g.transm = transm ? d_transm : nullptr;
   g.pao = pao ? d_pao : nullptr;
-  g.transmd = det ? d_transmd : nullptr;
+  g.transmd = transmd ? d_transmd : nullptr;                // (without depd: zeroed at nobsl == 0 only, :97-99)
   g.rdiag_wloc = rdiag_wloc ? (*rdiag_wloc != 0) : 0;      // common_letkf.f90:84-85
   g.infl_update = infl_update ? (*infl_update != 0) : 0;   // :86-87
   g.status = d_i + 1;
@@ -1582,7 +1599,7 @@ int core_host(int ne, int nobs, int nobsl, const double* hdxb, const double* rdi
   HIP_TRY(hipMemcpyAsync(trans, d_trans, k * k * sizeof(double), hipMemcpyDeviceToHost, s));
   if (transm) HIP_TRY(hipMemcpyAsync(transm, d_transm, k * sizeof(double), hipMemcpyDeviceToHost, s));
   if (pao) HIP_TRY(hipMemcpyAsync(pao, d_pao, k * k * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (transmd && depd) HIP_TRY(hipMemcpyAsync(transmd, d_transmd, k * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (transmd && (depd || nobsl == 0)) HIP_TRY(hipMemcpyAsync(transmd, d_transmd, k * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(parm_infl, d_infl, sizeof(double), hipMemcpyDeviceToHost, s));
   int hst = 0;
   HIP_TRY(hipMemcpyAsync(&hst, d_i + 1, sizeof(int), hipMemcpyDeviceToHost, s));

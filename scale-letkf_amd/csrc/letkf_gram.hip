@@ -254,20 +254,26 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_gram_m
             if constexpr (DUAL) {
               const int b = item / Tc, t = item - b * Tc;
               const int i = 16 * b + col;
-              int e0 = (ch * Tc + t) * 8 + 2 * rq;
-              e0 = e0 < k - 1 ? e0 : k - 1;           // (a row holds k + 1 doubles)
-              st0[u] = *reinterpret_cast<const d2u*>(A.ensval + roff[i < n ? i : n - 1] + e0);
+              const int e0 = (ch * Tc + t) * 8 + 2 * rq;
+              // (a row may hold just k doubles, kld = k: a pair reaching past member k - 1 is fetched as [k - 2, k - 1]
+              // and its member k - 1 moved to .x; pairs beyond it are dropped in commit)
+              st0[u] = *reinterpret_cast<const d2u*>(A.ensval + roff[i < n ? i : n - 1] + (e0 < k - 1 ? e0 : k - 2));
+              if (e0 >= k - 1) st0[u].x = st0[u].y;
             } else if (item < NP * Tc) {
               const int g = item / Tc, t = item - g * Tc;
-              int mm = 32 * g + 2 * col;
-              mm = mm < k - 1 ? mm : k - 1;
+              const int mm = 32 * g + 2 * col;
+              const int ml = mm < k - 1 ? mm : k - 2;  // (as in the dual case: member k - 1 of a clamped pair moved to .x)
               const int r0 = (ch * rows_ch) % kGmSuper + 8 * t + 2 * rq;   // super-chunk-relative rows r0, r0 + 1
-              st0[u] = *reinterpret_cast<const d2u*>(A.ensval + roff[r0] + mm);
-              st1[u] = *reinterpret_cast<const d2u*>(A.ensval + roff[r0 + 1] + mm);
+              st0[u] = *reinterpret_cast<const d2u*>(A.ensval + roff[r0] + ml);
+              st1[u] = *reinterpret_cast<const d2u*>(A.ensval + roff[r0 + 1] + ml);
+              if (mm >= k - 1) {
+                st0[u].x = st0[u].y;
+                st1[u].x = st1[u].y;
+              }
             } else if (item < (NB - NP) * Tc) {       // the single last block: member 32 NP + col of rows r0, r0 + 1
               const int t = item - NP * Tc;
               int mm = 32 * NP + col;
-              mm = mm < k ? mm : k;                   // (a row holds k + 1 doubles)
+              mm = mm < k ? mm : k - 1;               // (a row may hold just k doubles; members >= k are dropped in commit)
               const int r0 = (ch * rows_ch) % kGmSuper + 8 * t + 2 * rq;
               st0[u].x = A.ensval[roff[r0] + mm];
               st1[u].x = A.ensval[roff[r0 + 1] + mm];
@@ -286,7 +292,7 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_gram_m
               const int e0 = (ch * Tc + t) * 8 + 2 * rq;
               const double sw = i < n ? swl[i] : 0.0;
               d2 v;
-              v.x = e0 < k ? st0[u].x * sw : 0.0;     // (e0 >= k - 1: the clamped load fetched [k - 1, k])
+              v.x = e0 < k ? st0[u].x * sw : 0.0;     // (e0 = k - 1: .x holds member k - 1 of the clamped pair)
               v.y = e0 + 1 < k ? st0[u].y * sw : 0.0;
               panel[(size_t)(b * Tc + t) * 64 + lane] = v;
             } else if (item >= NP * Tc && item < (NB - NP) * Tc) {
@@ -308,7 +314,7 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_gram_m
                 vo.x = st0[u].y * s0;
                 ve.y = st1[u].x * s1;
                 vo.y = st1[u].y * s1;
-              } else {                                // (the clamped loads fetched [k - 1, k])
+              } else {                                // (mm = k - 1: .x holds member k - 1 of the clamped pair)
                 ve.x = mm == k - 1 ? st0[u].x * s0 : 0.0;
                 ve.y = mm == k - 1 ? st1[u].x * s1 : 0.0;
                 vo.x = vo.y = 0.0;

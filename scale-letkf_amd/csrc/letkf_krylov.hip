@@ -78,7 +78,8 @@ struct KryLds {
 // in flight.  Every refill is unconditional: with a branch around a load hipcc can no longer count the loads in flight
 // and waits for all of them (vmcnt(0)) in front of every matrix-core step (found in the ISA); a padding step fetches
 // step 0 again.  wrap: the last refills fetch the FIRST steps again (the same product is repeated: CG on one matrix).
-// olim: largest element offset a lane may fetch from its row (clamped beyond: such columns meet zero rows of B).
+// olim: offset of the last element a lane's row holds for it (a pair at or beyond olim is fetched as [olim - 1, olim] and
+// element olim moved to .x: the row may end at olim, kld = k; columns beyond it meet zero rows of B).
 // RES (the product of the iteration at orders <= 128, r4): the ring holds the wave's WHOLE operand (T <= PF double-steps), filled
 // once per point -- no refill, the matrix stays in registers from the first iteration to the last.  The counters of the
 // streaming form (profiles/r04_k100_pmc_summary.json): 1.35 MB per point = 14 iterations x the 96 KB matrix through
@@ -103,10 +104,13 @@ __device__ __forceinline__ void ring_steps(d2u (&ring)[PF][BPW], const double* c
       int tn = t + PF;
       if (tn >= Tp) tn = wrap ? tn - Tp : 0;
       if (tn >= T) tn = 0;
-      int off = 8 * tn;
-      off = off < olim ? off : olim;
+      const int off = 8 * tn;
+      const bool sh = off >= olim;
 #pragma unroll
-      for (int bi = 0; bi < NA; ++bi) ring[u][bi] = *reinterpret_cast<const d2u*>(abase[bi] + off);
+      for (int bi = 0; bi < NA; ++bi) {
+        ring[u][bi] = *reinterpret_cast<const d2u*>(abase[bi] + (sh ? olim - 1 : off));
+        if (sh) ring[u][bi].x = ring[u][bi].y;
+      }
     }
   }
 }
@@ -114,10 +118,13 @@ template <int BPW, int PF>
 __device__ __forceinline__ void ring_fill(d2u (&ring)[PF][BPW], const double* const (&abase)[BPW], const int olim, const int T) {
 #pragma unroll
   for (int u = 0; u < PF; ++u) {
-    int off = 8 * (u < T ? u : 0);
-    off = off < olim ? off : olim;
+    const int off = 8 * (u < T ? u : 0);
+    const bool sh = off >= olim;
 #pragma unroll
-    for (int bi = 0; bi < BPW; ++bi) ring[u][bi] = *reinterpret_cast<const d2u*>(abase[bi] + off);
+    for (int bi = 0; bi < BPW; ++bi) {
+      ring[u][bi] = *reinterpret_cast<const d2u*>(abase[bi] + (sh ? olim - 1 : off));
+      if (sh) ring[u][bi].x = ring[u][bi].y;
+    }
   }
 }
 // nact (wave-uniform) of the BPW blocks are real: the instantiation without the idle ones
@@ -595,7 +602,7 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_krylov
           const double* zb[BPW];
 #pragma unroll
           for (int bi = 0; bi < BPW; ++bi) zb[bi] = zrow[bi] + c0;
-          const int olim = k - 1 - c0 - 2 * rq;              // (a row holds k + 1 doubles: the last pair fetched is [k - 1, k])
+          const int olim = k - 1 - c0 - 2 * rq;              // (member k - 1: the row may end there, kld = k)
           d2u zring[PF][BPW];
           ring_fill<BPW, PF>(zring, zb, olim, kc16 >> 3);
           ring_product<BPW, PF>(nact, zring, zb, olim, kc16 >> 3, false, xl, lane, zacc);

@@ -653,9 +653,10 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
         const int Tp = (T + ZR - 1) / ZR * ZR;
         for (int g = wv; g < ng; g += nwv) {
           const int mm0 = 32 * g;
-          int eo = mm0 + 2 * col;
-          if (eo > k - 1) eo = k - 1;                     // (a row holds k + 1 doubles; such members are dropped below)
-          const double* ebase = A.ensval + eo;
+          // (a row may hold just k doubles, kld = k: a pair reaching past member k - 1 is fetched as [k - 2, k - 1] and its
+          // member k - 1 taken from .y; members >= k are dropped below)
+          const bool sh = mm0 + 2 * col >= k - 1;
+          const double* ebase = A.ensval + (sh ? k - 2 : mm0 + 2 * col);
           d2u ring[ZR];
 #pragma unroll
           for (int u = 0; u < ZR; ++u) ring[u] = *reinterpret_cast<const d2u*>(ebase + roff[4 * (u < T ? u : 0) + rq]);
@@ -666,7 +667,7 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
               const int s_ = s0 + u;
               if (s_ < T) {
                 const double bq = qb[(size_t)(4 * s_) * 16 + lane];
-                ae = __builtin_amdgcn_mfma_f64_16x16x4f64(ring[u].x, bq, ae, 0, 0, 0);
+                ae = __builtin_amdgcn_mfma_f64_16x16x4f64(sh ? ring[u].y : ring[u].x, bq, ae, 0, 0, 0);
                 ao = __builtin_amdgcn_mfma_f64_16x16x4f64(ring[u].y, bq, ao, 0, 0, 0);
               }
               int sn = s_ + ZR;

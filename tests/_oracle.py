@@ -67,15 +67,17 @@ def _flags(transm, pao, rdiag_wloc, infl_update, depd, transmd):
 
 
 def letkf_core(which, ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_transm=True,
-               want_pao=True, rdiag_wloc=None, infl_update=None, depd=None, want_transmd=False):
+               want_pao=True, rdiag_wloc=None, infl_update=None, depd=None, want_transmd=False, fill=0.0,
+               transmd_without_depd=False):
     """Run letkf_core through `which` in {"oracle", "ref"}.  hdxb is (nobs, ne) Fortran-ordered.
-    Returns dict(trans, transm, pao, transmd, parm_infl, rc)."""
+    Returns dict(trans, transm, pao, transmd, parm_infl, rc).  The outputs start as `fill` (what an element holds when
+    it is not written); transmd is returned only with depd unless transmd_without_depd."""
     hdxb = np.asfortranarray(hdxb, dtype=np.float64)
     assert hdxb.shape == (nobs, ne)
-    trans = np.zeros((ne, ne), order="F")
-    transm = np.zeros(ne)
-    pao = np.zeros((ne, ne), order="F")
-    transmd = np.zeros(ne)
+    trans = np.full((ne, ne), fill, order="F")
+    transm = np.full(ne, fill)
+    pao = np.full((ne, ne), fill, order="F")
+    transmd = np.full(ne, fill)
     infl = C.c_double(parm_infl)
     dd = depd if depd is not None else np.zeros(max(nobs, 1))
     if which == "ref":
@@ -96,7 +98,8 @@ def letkf_core(which, ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_t
             C.byref(wl) if rdiag_wloc is not None else None, C.byref(iu) if infl_update is not None else None,
             _dp(depd) if depd is not None else None, _dp(transmd) if want_transmd else None)
     return dict(trans=trans, transm=transm if want_transm else None, pao=pao if want_pao else None,
-                transmd=transmd if (want_transmd and depd is not None) else None, parm_infl=infl.value, rc=rc)
+                transmd=transmd if (want_transmd and (depd is not None or transmd_without_depd)) else None,
+                parm_infl=infl.value, rc=rc)
 
 
 def mtx_eigen(which, a):
