@@ -1,8 +1,8 @@
 // letkf_api.hip -- host side of the C ABI declared in include/letkf_amd.h.
 //
-// Thin by design: argument checking, launch planning (LDS carve, Jacobi variant, grid),
-// the large-k workspace, optional HIP-event timing for bench.py, and the host-pointer
-// compatibility entry letkf_core_c that the Fortran shim (scale-letkf_amd/fortran) calls.
+// Thin by design: argument checking, the choice of kernels (pick_route), the workspaces,
+// optional HIP-event timing for bench.py, and the host-pointer compatibility entry
+// letkf_core_c that the Fortran shim (scale-letkf_amd/fortran) calls.
 // There is no CPU fallback anywhere in this file: without a device every compute entry
 // returns LETKF_E_NO_DEVICE.
 
@@ -45,7 +45,7 @@ struct letkf_ctx {
   size_t lds_max = 160 * 1024;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
-  double* ws = nullptr;       // large-k workspace
+  char* ws = nullptr;         // letkf_point_kernel<BIG>: its per-workgroup matrices
   size_t ws_bytes = 0;
   char* warm_ws = nullptr;    // wave kernel: eigenvectors handed from point to point inside a run
   unsigned* sched = nullptr;  // wave kernel: the 8 run counters of the dynamic scheduling (512 bytes)
@@ -86,98 +86,26 @@ struct letkf_ctx {
 
 namespace {
 
-int ensure_bytes(letkf_ctx* c, char** buf, size_t* have, size_t need) {
+// Grows one of the context's device buffers to at least `need` bytes: a quarter more than that (+ 4 KiB), or exactly `need`
+// without slack.  The buffer it replaces may still be read by work on the stream: that work is waited for first.
+int grow(letkf_ctx* c, char** buf, size_t* have, size_t need, bool slack = true) {
   if (need <= *have) return LETKF_OK;
-  if (*buf) HIP_TRY(hipFree(*buf));
-  *buf = nullptr;
-  *have = 0;
-  size_t cap = need + need / 4 + 4096;
+  if (*buf) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+  }
+  const size_t cap = slack ? need + need / 4 + 4096 : need;
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), cap));
   *have = cap;
-  (void)c;
   return LETKF_OK;
 }
 
-struct Plan {
-  letkf::LaunchPlan lp;
-  int ldg, ldy, tn;
-  long ws_per_block;
-};
-
-// LDS carve in doubles; must mirror letkf_point_kernel's carve.
-size_t lds_doubles(bool big, int k, int nv, int ldg, int ldy, int tn) {
-  const int nb = nv + 2;
-  size_t fixed = 7 * (size_t)k + 6 * (size_t)nv + 16 + 3 * (size_t)tn + 1;
-  if (big) return fixed + (size_t)tn * ldy;
-  size_t g = (size_t)k * ldg;
-  g += g & 1;
-  size_t tile = (size_t)tn * ldy;
-  size_t ux = (size_t)k * nb + (size_t)nv * k;
-  return fixed + g + (tile > ux ? tile : ux);
-}
-
-int make_plan(const letkf_ctx* c, int k, int nv, long npts, Plan* p) {
-  if (k < 2) return fail(LETKF_E_INVALID, "ensemble size must be >= 2");
-  if (nv < 0 || npts < 0) return fail(LETKF_E_INVALID, "negative size");
-  p->ldg = k | 1;
-  p->ldy = (k + 3) & ~3;
-  bool big = k > 128;
-  if (!big) {
-    p->tn = 32;
-    size_t bytes = 8 * lds_doubles(false, k, nv, p->ldg, p->ldy, p->tn);
-    if (bytes > c->lds_max) big = true;
-    else {
-      p->lp.big = false;
-      p->lp.rmax = (k <= 32) ? 4 : (k <= 56) ? 7 : (k <= 64) ? 8 : (k <= 104) ? 13 : 16;
-      p->lp.block = 256;
-      p->lp.lds_bytes = bytes;
-      long g = (long)c->num_cu * 32;
-      p->lp.grid = (int)(npts < g ? (npts > 0 ? npts : 1) : g);
-      p->ws_per_block = 0;
-      return LETKF_OK;
-    }
-  }
-  // large-k spill path: G, U, X in a per-workgroup HBM workspace, obs tile sized to what LDS is left
-  p->lp.big = true;
-  p->lp.rmax = 0;
-  // one wave per block pair of the block Jacobi (k/32 pairs per round), 4..12 waves: 12 waves = 3 per SIMD keeps
-  // 170 VGPRs per lane for the in-register 32 x 32 eigensolver; one workgroup per CU
-  const int nblk = (k + 15) / 16, nbe = nblk + (nblk & 1);
-  int waves = nbe / 2;
-  if (waves < 4) waves = 4;
-  if (waves > 12) waves = 12;
-  p->lp.block = 64 * waves;
-  const size_t budget = 128 * 1024 / 8;  // doubles of LDS we allow ourselves
-  size_t fixed = lds_doubles(true, k, nv, p->ldg, p->ldy, 0);
-  long tn = fixed < budget ? (long)((budget - fixed) / (p->ldy + 3)) : 0;
-  if (tn > 32) tn = 32;
-  if (tn < 4) tn = 4;
-  // the obs tile region doubles as the per-wave scratch of the block Jacobi
-  while ((size_t)tn * p->ldy < (size_t)waves * letkf::kBlockJacobiScratch) ++tn;
-  p->tn = (int)tn;
-  p->lp.lds_bytes = 8 * lds_doubles(true, k, nv, p->ldg, p->ldy, p->tn);
-  if (p->lp.lds_bytes > c->lds_max) return fail(LETKF_E_INVALID, "ensemble size too large for the LDS vectors");
-  long g = (long)c->num_cu;
-  p->lp.grid = (int)(npts < g ? (npts > 0 ? npts : 1) : g);
-  const int nb = nv + 2;
-  long w = (long)k * p->ldg + (long)k * nb + (long)nv * k;
-  p->ws_per_block = (w + 1) & ~1L;
-  return LETKF_OK;
-}
-
-int ensure_ws(letkf_ctx* c, const Plan& p) {
-  if (!p.lp.big) return LETKF_OK;
-  size_t need = (size_t)p.lp.grid * (size_t)p.ws_per_block * sizeof(double);
-  if (need <= c->ws_bytes) return LETKF_OK;
-  if (c->ws) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipFree(c->ws));
-    c->ws = nullptr;
-    c->ws_bytes = 0;
-  }
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ws), need));
-  c->ws_bytes = need;
-  return LETKF_OK;
+// int32 counts -> int64 exclusive offsets (rocprim) with the scan's storage at temp; temp == nullptr: *temp_bytes = its size
+hipError_t count_scan(void* temp, size_t* temp_bytes, const int32_t* counts, int64_t* off, size_t n, hipStream_t st) {
+  auto in = rocprim::make_transform_iterator(counts, [] __device__(int32_t v) { return (int64_t)v; });
+  return rocprim::exclusive_scan(temp, *temp_bytes, in, off, (int64_t)0, n, rocprim::plus<int64_t>(), st);
 }
 
 // Measurement-only knobs exist in the PROF twin of the library (make PROF=1) and nowhere else: the production build
@@ -196,158 +124,119 @@ struct EventPair {   // timing events that do not outlive a failed launch
   }
 };
 
-int launch_staged(letkf_ctx* c, letkf::PointArgs& a);
+// The route of a loop-body / letkf_core call.  pick_route decides it, and nothing else does:
+//
+//   family  serves                                                       kernels
+//   trio    mode 0, nv = 11, k <= 20, no per-point outputs (T, Pa,        letkf_trio_kernel (letkf_trio.hip): three points per wave
+//           w-bar), the trivial pre-pass ran; LETKF_OPT_SMALL_K_TRIO
+//   wave    k <= 100 and nv = 11 (modes 0, 2, 3) or nv = 0 (mode 1),      letkf_wave_kernel (letkf_wave.hip): one wave per point to
+//           but not the staged path's eigen-free calls below               k = 62, two from 63
+//   staged  every other call with nv + 2 <= 16 right-hand sides;          Gram (matrix cores for mode 0, letkf_stage_gram_kernel for
+//           from k = 63 also mode 0 without T / Pa where                  the other modes and beyond k = 512) -> eigen-free stage
+//           LETKF_OPT_STAGED_POLY (eigen-free: 1.07 M solves/s against    (mode 0 without T / Pa, LETKF_OPT_STAGED_POLY) -> eigen
+//           0.64 M on the two-wave kernel at k = 100)                     stage (workgroup Jacobi to order 208, block Jacobi beyond)
+//                                                                          -> apply (letkf_gram / krylov / eig / staged.hip)
+//   point   nv + 2 > 16                                                   letkf_point_kernel (letkf_kernels.hip): LDS, or BIG with its
+//                                                                          matrices in an HBM workspace where they do not fit
+//
+// The streaming pre-pass (letkf_trivial.hip: points without observations or with beta = 0) runs in front of the trio, wave and
+// staged families wherever trivial_pass_supports.
+enum class Family { trio, wave, staged, point };
+struct Route {
+  Family family = Family::wave;
+  bool trivial = false;       // the pre-pass runs first, and the solve skips its points
+  letkf::GramKernels gram{};  // staged: the Gram kernel(s) ...
+  bool krylov = false;        // ... the eigen-free stage ...
+  int eig_wg_order = 0;       // ... the order cap of the workgroup Jacobi ...
+  bool eig_block = false;     // ... and the block Jacobi behind it
+  letkf::PointPlan plan{};    // point: LDS or BIG, and its launch shape
+};
 
-int launch(letkf_ctx* c, letkf::PointArgs& a, int warm_run = 0, long warm_stride = 1) {
-  if (a.k < 2) return fail(LETKF_E_INVALID, "ensemble size must be >= 2");
-  if (a.nv < 0 || a.npts < 0) return fail(LETKF_E_INVALID, "negative size");
-  a.max_sweep = 60;
-  if (const char* e = LETKF_KNOB("LETKF_AMD_MAX_SWEEP")) {   // PROF knob: time the non-eigensolve phases
-    int v = std::atoi(e);
-    if (v >= 0 && v < 60) a.max_sweep = v;   // 0: skip the eigensolve entirely (timing only, results invalid)
-  }
-  // k <= 64: one wavefront per grid point, matrix in registers (letkf_wave.hip); otherwise one workgroup per
-  // point with the matrix in LDS, or in the HBM workspace for large k (letkf_kernels.hip)
-  const bool force_block = LETKF_KNOB("LETKF_AMD_FORCE_BLOCK") != nullptr;
-  if (a.mode == 2 && force_block) return fail(LETKF_E_INVALID, "LETKF_AMD_FORCE_BLOCK: the workgroup kernel has no fused search");
-  bool wave = !force_block && letkf::wave_kernel_supports(a.k, a.nv, a.mode);
-  if (const char* e = LETKF_KNOB("LETKF_AMD_STAGED_MIN_K"))   // PROF knob: A/B the staged path against the two-wave kernel
-    if (a.mode != 2 && a.k >= std::atoi(e)) wave = false;
-  // 63 <= k <= 100, loop body without k x k outputs: the staged path analyses such a point without an eigen-decomposition
-  // (letkf_staged.hip poly_apply; MEMBER = 100: 1.07 M solves/s against 0.64 M on the two-wave Jacobi kernel, same result to
-  // rounding).  The two-wave kernel keeps the calls that return T / Pa, and everything when LETKF_OPT_STAGED_POLY is 0.
-  if (wave && a.k >= 63 && a.mode == 0 && !a.trans_out && !a.pa_out && c->staged_poly && a.nv + 2 <= 16) wave = false;
-#ifdef LETKF_STAGED_MIN_K   // A/B twins (make VARIANT=...): the same switch at compile time
-  if (a.mode != 2 && a.k >= LETKF_STAGED_MIN_K) wave = false;
-#endif
-  // beyond the register kernels: the staged three-kernel path (the monolithic workgroup kernel below stays reachable
-  // through the PROF twin's LETKF_AMD_FORCE_BLOCK / LETKF_AMD_MONOLITHIC knobs for A/B measurements)
-  if (!wave && !force_block && a.mode != 2 && a.nv + 2 <= 16 && !LETKF_KNOB("LETKF_AMD_MONOLITHIC")) return launch_staged(c, a);
-  // the route is decided: only now the plan (and, for large k, the workspace) of the monolithic workgroup kernel -- the
-  // staged path above has its own slabs and serves ensemble sizes whose vectors this kernel's LDS carve would refuse
-  Plan p;
-  if (int rc = make_plan(c, a.k, a.nv, a.npts, &p)) return rc;
-  if (!wave)
-    if (int rc = ensure_ws(c, p)) return rc;
-  a.ldg = p.ldg;
-  a.ldy = p.ldy;
-  a.tn = p.tn;
-  a.ws = c->ws;
-  a.ws_per_block = p.ws_per_block;
-  a.big_block = (p.lp.big && !LETKF_KNOB("LETKF_AMD_BIG_STREAM")) ? 1 : 0;   // PROF knob: the older streaming Jacobi
+int pick_route(const letkf_ctx* c, const letkf::PointArgs& a, Route* r) {
+  *r = Route{};
+  const bool kkout = a.trans_out || a.pa_out;
+  const bool staged_ok = a.mode != 2 && a.nv + 2 <= 16;
+  bool wave = letkf::wave_kernel_supports(a.k, a.nv, a.mode);
+  if (wave && a.k >= 63 && a.mode == 0 && !kkout && c->staged_poly && staged_ok) wave = false;
+  if (wave || staged_ok) r->trivial = letkf::trivial_pass_supports(a) && !LETKF_KNOB("LETKF_AMD_NO_TRIVIAL_PASS");
   if (wave) {
-    int run_req = warm_run;
-    if (const char* e = LETKF_KNOB("LETKF_AMD_RUN_LEN")) run_req = std::atoi(e);   // PROF knob: 1 = all cold
-    size_t wbytes = 0;
-    a.warm_stride = warm_stride > 1 ? warm_stride : 1;
-    if (a.npts % a.warm_stride != 0) return fail(LETKF_E_INVALID, "warm_stride does not divide npts");
-    letkf::wave_launch_shape(a.k, a.mode, a.npts, c->num_cu, run_req, a.warm_stride, &a.run_len, &a.wave_grid, &wbytes);
-    if (wbytes > c->warm_ws_bytes) HIP_TRY(hipStreamSynchronize(c->stream));   // old buffer may still be in use
-    if (int rc = ensure_bytes(c, &c->warm_ws, &c->warm_ws_bytes, wbytes)) return rc;
-    a.warm_ws = reinterpret_cast<double*>(c->warm_ws);
-    if (a.mode == 3) {   // one local-list slot per wave of the grid (4 waves per workgroup): idx | rdiag | rloc
-      const size_t nslot = (size_t)a.wave_grid * 4, cap = 2 * (size_t)(a.sl_cap > 0 ? a.sl_cap : 4);   // (two lists per wave: this level's and the next one's)
-      const size_t o_rd = (nslot * cap * 4 + 255) & ~(size_t)255, o_rl = o_rd + nslot * cap * 8;
-      const size_t need = o_rl + nslot * cap * 8 + 256;
-      if (need > c->slot_ws_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-      if (int rc = ensure_bytes(c, &c->slot_ws, &c->slot_ws_bytes, need)) return rc;
-      a.sl_idx = reinterpret_cast<int*>(c->slot_ws);
-      a.sl_rd = reinterpret_cast<double*>(c->slot_ws + o_rd);
-      a.sl_rl = reinterpret_cast<double*>(c->slot_ws + o_rl);
-      a.obs_idx = a.sl_idx;
-      a.rdiag_l = a.sl_rd;
-      a.rloc_l = a.sl_rl;
-    }
-    if (!c->sched) {
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->sched), 512));
-      HIP_TRY(hipMemsetAsync(c->sched, 0, 512, c->stream));   // (later launches reset it themselves when they draw)
-    }
-    a.sched = LETKF_KNOB("LETKF_AMD_STATIC_SCHED") ? nullptr : c->sched;   // PROF knob: the static dealing, for A/B runs
-    a.warm_dbg = 0;
-    if (const char* e = LETKF_KNOB("LETKF_AMD_WARM_DBG")) a.warm_dbg = std::atoi(e);
-    a.prof = nullptr;
-#ifdef LETKF_CHECKED
-    {   // the violation record of the checked build (letkf_wave.hip LETKF_CHECK): code | workgroup | value | bound
-      static unsigned long long* rec = nullptr;
-      if (!rec) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rec), 4 * sizeof(unsigned long long)));
-      HIP_TRY(hipMemsetAsync(rec, 0, 4 * sizeof(unsigned long long), c->stream));
-      a.prof = rec;
-    }
-#endif
-  }
-  // every argument check is behind us: only now create the timing events (destroyed again if the launch fails)
-  EventPair ev;
-  if (c->timing) {
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
-    HIP_TRY(hipEventRecord(ev.e0, c->stream));
-  }
-  if (wave) {
-#ifdef LETKF_WAVE_PROF
-    static unsigned long long* prof_dev = nullptr;
-    if (!prof_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&prof_dev), 26 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(prof_dev, 0, 26 * sizeof(unsigned long long), c->stream));
-    a.prof = prof_dev;
-#endif
-    // points without observations / with beta = 0: one streaming pass, thread per point (letkf_trivial.hip)
-    if (letkf::trivial_pass_supports(a) && !LETKF_KNOB("LETKF_AMD_NO_TRIVIAL_PASS")) {
-      HIP_TRY(letkf::launch_trivial_points(a, c->stream));
-      a.skip_trivial = 1;
-    }
-    if (c->trio && letkf::trio_kernel_supports(a)) {
-      HIP_TRY(letkf::launch_trio_kernel(a, c->num_cu, c->stream));
-      c->last_path = std::string("letkf_trio_kernel<KR=") + (a.k <= 16 ? "16" : "20") + ",P=" + std::to_string(letkf::trio_points_per_wave(a.k)) + ">";
-    } else {
-    HIP_TRY(letkf::launch_wave_kernel(a, c->num_cu, c->stream));
-    c->last_path = "letkf_wave_kernel<KR=" + std::to_string(letkf::wave_kernel_kr(a.k)) + ",NV=" + std::to_string(a.nv) +
-                   ",NW=" + (a.k <= 62 ? "1" : "2") + (a.mode == 2 ? ",FUSED" : a.mode == 3 ? ",FUSED: column survivors" : "") + ">";
-    }
-#ifdef LETKF_WAVE_PROF
-    {
-      unsigned long long h[26];
-      HIP_TRY(hipMemcpyAsync(h, prof_dev, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      unsigned long long tot = 0;
-      for (int i = 0; i < 10; ++i) tot += h[i];
-      std::fprintf(stderr, "[letkf prof] wave-time share by phase (s_memtime ticks, all waves):");
-      for (int i = 0; i < 10; ++i) std::fprintf(stderr, " p%d=%.1f%%", i, tot ? 100.0 * (double)h[i] / (double)tot : 0.0);
-      std::fprintf(stderr, " total=%llu\n", tot);
-      std::fprintf(stderr, "[letkf prof] first wave start .. last wave end: %llu ticks; waves by units done (0..11+):", h[11] - ~h[10]);
-      for (int i = 12; i < 24; ++i) std::fprintf(stderr, " %llu", h[i]);
-      std::fprintf(stderr, "; units done in all: %llu\n", h[24]);
-    }
-#endif
+    r->family = c->trio && r->trivial && letkf::trio_kernel_supports(a) ? Family::trio : Family::wave;
+  } else if (staged_ok) {
+    r->family = Family::staged;
+    r->gram = letkf::stage_gram_kernels(a.k, a.mode);
+    r->krylov = a.mode == 0 && !kkout && c->staged_poly;
+    r->eig_wg_order = std::min(a.k, letkf::eig_wg_max_order());
+    r->eig_block = a.k > letkf::eig_wg_max_order();
   } else {
-    HIP_TRY(letkf::launch_point_kernel(a, p.lp, c->stream));
-    c->last_path = p.lp.big ? "letkf_point_kernel<BIG>" : "letkf_point_kernel<LDS>";
+    r->family = Family::point;
+    if (!letkf::point_kernel_plan(a.k, a.nv, a.npts, c->num_cu, c->lds_max, &r->plan))
+      return fail(LETKF_E_INVALID, "ensemble size too large for the LDS vectors");
   }
-  if (c->timing) {
-    HIP_TRY(hipEventRecord(ev.e1, c->stream));
-    c->events.emplace_back(ev.e0, ev.e1);
-    ev.e0 = ev.e1 = nullptr;   // owned by the context from here
+  return LETKF_OK;
+}
+
+std::string route_path(const letkf::PointArgs& a, const Route& r) {
+  switch (r.family) {
+    case Family::trio:
+      return "letkf_trio_kernel<KR=" + std::to_string(letkf::trio_kernel_kr(a.k)) + ",P=" + std::to_string(letkf::trio_points_per_wave(a.k)) + ">";
+    case Family::wave:
+      return "letkf_wave_kernel<KR=" + std::to_string(letkf::wave_kernel_kr(a.k)) + ",NV=" + std::to_string(a.nv) +
+             ",NW=" + std::to_string(letkf::wave_kernel_nw(a.k)) + (a.mode == 2 ? ",FUSED" : a.mode == 3 ? ",FUSED: column survivors" : "") + ">";
+    case Family::point: return r.plan.big ? "letkf_point_kernel<BIG>" : "letkf_point_kernel<LDS>";
+    case Family::staged: break;
   }
+  std::string eig = letkf::eig_wg_kernel_name(r.eig_wg_order) + (r.eig_block ? " / letkf_eig_block_kernel" : "");
+  if (r.krylov) eig = "letkf_stage_krylov_kernel (CG + Lanczos; points it gives up: " + eig + ")";
+  return std::string("staged: ") + (r.gram.mfma ? "letkf_stage_gram_mfma_kernel + " : "") + (r.gram.plain ? "letkf_stage_gram_kernel + " : "") +
+         eig + " + letkf_stage_apply_kernel";
+}
+
+// Register kernels (trio, wave): run length, grid, the warm-start, local-list slot and scheduling workspaces
+int prepare_wave(letkf_ctx* c, letkf::PointArgs& a, const Route& r, int warm_run, long warm_stride) {
+  int run_req = warm_run;
+  if (const char* e = LETKF_KNOB("LETKF_AMD_RUN_LEN")) run_req = std::atoi(e);   // PROF knob: 1 = all cold
+  size_t wbytes = 0;
+  a.warm_stride = warm_stride > 1 ? warm_stride : 1;
+  if (a.npts % a.warm_stride != 0) return fail(LETKF_E_INVALID, "warm_stride does not divide npts");
+  letkf::wave_launch_shape(a.k, a.mode, a.npts, c->num_cu, run_req, a.warm_stride, &a.run_len, &a.wave_grid, &wbytes);
+  if (r.family == Family::wave) {   // (the trio kernel parks its eigenvectors in LDS)
+    if (int rc = grow(c, &c->warm_ws, &c->warm_ws_bytes, wbytes)) return rc;
+    a.warm_ws = reinterpret_cast<double*>(c->warm_ws);
+  }
+  if (a.mode == 3) {   // one local-list slot per wave of the grid (4 waves per workgroup): idx | rdiag | rloc
+    const size_t nslot = (size_t)a.wave_grid * 4, cap = 2 * (size_t)(a.sl_cap > 0 ? a.sl_cap : 4);   // (two lists per wave: this level's and the next one's)
+    const size_t o_rd = (nslot * cap * 4 + 255) & ~(size_t)255, o_rl = o_rd + nslot * cap * 8;
+    if (int rc = grow(c, &c->slot_ws, &c->slot_ws_bytes, o_rl + nslot * cap * 8 + 256)) return rc;
+    a.sl_idx = reinterpret_cast<int*>(c->slot_ws);
+    a.sl_rd = reinterpret_cast<double*>(c->slot_ws + o_rd);
+    a.sl_rl = reinterpret_cast<double*>(c->slot_ws + o_rl);
+    a.obs_idx = a.sl_idx;
+    a.rdiag_l = a.sl_rd;
+    a.rloc_l = a.sl_rl;
+  }
+  if (!c->sched) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->sched), 512));
+    HIP_TRY(hipMemsetAsync(c->sched, 0, 512, c->stream));   // (later launches reset it themselves when they draw)
+  }
+  a.sched = LETKF_KNOB("LETKF_AMD_STATIC_SCHED") ? nullptr : c->sched;   // PROF knob: the static dealing, for A/B runs
+  a.warm_dbg = 0;
+  if (const char* e = LETKF_KNOB("LETKF_AMD_WARM_DBG")) a.warm_dbg = std::atoi(e);
+  a.prof = nullptr;
 #ifdef LETKF_CHECKED
-  if (wave && a.prof) {
-    unsigned long long h[4];
-    HIP_TRY(hipMemcpyAsync(h, a.prof, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (h[0])
-      return fail(LETKF_E_HIP, "checked build: bound " + std::to_string(h[0]) + " violated in workgroup " + std::to_string(h[1]) + ": value " +
-                                   std::to_string((long long)h[2]) + " against " + std::to_string((long long)h[3]));
+  {   // the violation record of the checked build (letkf_wave.hip LETKF_CHECK): code | workgroup | value | bound
+    static unsigned long long* rec = nullptr;
+    if (!rec) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rec), 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(rec, 0, 4 * sizeof(unsigned long long), c->stream));
+    a.prof = rec;
   }
 #endif
   return LETKF_OK;
 }
 
-// Staged path (letkf_staged.hip): k beyond the register kernels.  The points are processed in batches whose slabs
-// fit a fixed workspace budget; per batch: Gram stage, eigen stage (workgroup Jacobi for orders <= 208, block Jacobi
-// above), apply stage -- all on the context's stream, no host synchronisation in between.
-int launch_staged(letkf_ctx* c, letkf::PointArgs& a) {
+// Staged path: the points go in batches whose slabs fit a fixed workspace budget; grows that workspace
+int prepare_staged(letkf_ctx* c, const letkf::PointArgs& a, const Route& r, long* nb_out, long* wpp_out) {
   const int kkout = (a.trans_out || a.pa_out) ? 1 : 0;
-  // eigen-free stage (letkf_krylov.hip): the loop body without k x k outputs, any k whose point matrices (order min(n, k))
-  // fit the stage (<= 512 rows; larger orders keep the eigen stage)
-  const bool krylov = a.mode == 0 && !kkout && c->staged_poly;
-  const long hist = krylov ? letkf::stage_krylov_hist_doubles(a.k) : 0;
+  const long hist = r.krylov ? letkf::stage_krylov_hist_doubles(a.k) : 0;
   const long wpp = letkf::staged_ws_per_point(a.k, a.nv, kkout, hist);
   // slabs of one batch: at most 6 GiB (+ as much again per 2 MB of residual history per point, up to 24 GiB)
   size_t budget = (size_t)6 << 30;
@@ -361,49 +250,41 @@ int launch_staged(letkf_ctx* c, letkf::PointArgs& a) {
     const long nbat = (a.npts + nb - 1) / nb;
     const long cap = nb;
     nb = (a.npts + nbat - 1) / nbat;
-#ifndef STAGED_BATCH_ROUND
-#define STAGED_BATCH_ROUND 1
-#endif
     // ... of whole rounds of workgroups: the stages run 2 (Gram, eigen-free stage at small orders) to 4 (apply) workgroups per CU,
     // and a batch that is no multiple of 2 x #CU ends every one of its kernels on a partly filled round (27648 points in 7
     // batches of 3950 = 7.7 rounds of 512: r4, MEMBER = 100)
-    if (STAGED_BATCH_ROUND) {
-      const long q = 2L * c->num_cu;
-      const long up = (nb + q - 1) / q * q;
-      if (up <= cap) nb = up;
-    }
+    const long q = 2L * c->num_cu;
+    const long up = (nb + q - 1) / q * q;
+    if (up <= cap) nb = up;
   }
+  const size_t need = (size_t)nb * (size_t)wpp * sizeof(double) + (size_t)nb * 4 * sizeof(int) + 256;
+  if (int rc = grow(c, &c->staged_ws, &c->staged_ws_bytes, need)) return rc;
+  *nb_out = nb;
+  *wpp_out = wpp;
+  return LETKF_OK;
+}
+
+// ... and per batch: Gram stage, eigen-free stage, eigen stage, apply stage -- all on the context's stream, no host
+// synchronisation in between
+int launch_staged(letkf_ctx* c, const letkf::PointArgs& a, const Route& r, long nb, long wpp) {
   const size_t slab_bytes = (size_t)nb * (size_t)wpp * sizeof(double);
-  const size_t need = slab_bytes + (size_t)nb * 4 * sizeof(int) + 256;
-  if (need > c->staged_ws_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (int rc = ensure_bytes(c, &c->staged_ws, &c->staged_ws_bytes, need)) return rc;
   letkf::StagedArgs s;
   s.A = a;
   s.A.ws = reinterpret_cast<double*>(c->staged_ws);
   s.A.ws_per_block = wpp;
+  s.A.max_sweep = 60;
   s.meta = reinterpret_cast<int*>(c->staged_ws + slab_bytes);
   s.info = s.meta + 2 * nb;
-  s.kkout = kkout;
+  s.kkout = (a.trans_out || a.pa_out) ? 1 : 0;
   s.wg_max_order = letkf::eig_wg_max_order();
-  s.poly_max_n = krylov ? letkf::stage_krylov_max_n(a.k) : 0;
-  s.gram_mfma = a.mode == 0 ? 1 : 0;   // stage 1 on the matrix cores (letkf_gram.hip); the older kernel takes what that one leaves
-  s.A.max_sweep = 60;
-  EventPair ev;
-  if (c->timing) {
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
-    HIP_TRY(hipEventRecord(ev.e0, c->stream));
-  }
-  if (letkf::trivial_pass_supports(a) && !LETKF_KNOB("LETKF_AMD_NO_TRIVIAL_PASS")) {   // as in launch()
-    HIP_TRY(letkf::launch_trivial_points(a, c->stream));
-    s.A.skip_trivial = 1;
-  }
+  s.poly_max_n = r.krylov ? letkf::stage_krylov_max_n(a.k) : 0;
+  s.gram_mfma = r.gram.mfma ? 1 : 0;
   for (long p0 = 0; p0 < a.npts; p0 += nb) {
     s.pt0 = p0;
     s.nbatch = (a.npts - p0 < nb) ? a.npts - p0 : nb;
-    if (s.gram_mfma) HIP_TRY(letkf::launch_stage_gram_mfma(s, c->stream));
-    if (!s.gram_mfma || a.k > 512) HIP_TRY(letkf::launch_stage_gram(s, c->lds_max, c->stream));   // (k <= 512: every point is the first kernel's)
-    if (s.poly_max_n > 0) HIP_TRY(letkf::launch_stage_krylov(s, c->lds_max, c->stream));   // (points it gives up: eigen stage, next)
+    if (r.gram.mfma) HIP_TRY(letkf::launch_stage_gram_mfma(s, c->stream));
+    if (r.gram.plain) HIP_TRY(letkf::launch_stage_gram(s, c->lds_max, c->stream));
+    if (r.krylov) HIP_TRY(letkf::launch_stage_krylov(s, c->lds_max, c->stream));   // (points it gives up: eigen stage, next)
     letkf::EigArgs e;
     e.ws = s.A.ws;
     e.ws_per_point = wpp;
@@ -412,18 +293,96 @@ int launch_staged(letkf_ctx* c, letkf::PointArgs& a) {
     e.meta = s.meta;
     e.info = s.info;
     e.max_sweep = 60;
-    HIP_TRY(letkf::launch_eig_wg(e, a.k < s.wg_max_order ? a.k : s.wg_max_order, c->num_cu, c->stream));
-    if (a.k > s.wg_max_order) HIP_TRY(letkf::launch_eig_block(e, a.k, c->num_cu, c->stream));
+    HIP_TRY(letkf::launch_eig_wg(e, r.eig_wg_order, c->num_cu, c->stream));
+    if (r.eig_block) HIP_TRY(letkf::launch_eig_block(e, a.k, c->num_cu, c->stream));
     HIP_TRY(letkf::launch_stage_apply(s, c->stream));
   }
+  return LETKF_OK;
+}
+
+int launch(letkf_ctx* c, letkf::PointArgs& a, int warm_run = 0, long warm_stride = 1) {
+  if (a.k < 2) return fail(LETKF_E_INVALID, "ensemble size must be >= 2");
+  if (a.nv < 0 || a.npts < 0) return fail(LETKF_E_INVALID, "negative size");
+  a.max_sweep = 60;
+  if (const char* e = LETKF_KNOB("LETKF_AMD_MAX_SWEEP")) {   // PROF knob: time the non-eigensolve phases
+    int v = std::atoi(e);
+    if (v >= 0 && v < 60) a.max_sweep = v;   // 0: skip the eigensolve entirely (timing only, results invalid)
+  }
+  Route r;
+  if (int rc = pick_route(c, a, &r)) return rc;
+  const bool reg = r.family == Family::trio || r.family == Family::wave;
+  long nb = 0, wpp = 0;
+  if (reg) {
+    if (int rc = prepare_wave(c, a, r, warm_run, warm_stride)) return rc;
+  } else if (r.family == Family::staged) {
+    if (int rc = prepare_staged(c, a, r, &nb, &wpp)) return rc;
+  } else {
+    if (int rc = grow(c, &c->ws, &c->ws_bytes, r.plan.ws_bytes(), false)) return rc;
+    a.ldg = r.plan.ldg;
+    a.ldy = r.plan.ldy;
+    a.tn = r.plan.tn;
+    a.ws = reinterpret_cast<double*>(c->ws);
+    a.ws_per_block = r.plan.ws_per_block;
+    a.big_block = (r.plan.big && !LETKF_KNOB("LETKF_AMD_BIG_STREAM")) ? 1 : 0;   // PROF knob: the older streaming Jacobi
+  }
+  // every argument check is behind us: only now create the timing events (destroyed again if the launch fails)
+  EventPair ev;
+  if (c->timing) {
+    HIP_TRY(hipEventCreate(&ev.e0));
+    HIP_TRY(hipEventCreate(&ev.e1));
+    HIP_TRY(hipEventRecord(ev.e0, c->stream));
+  }
+#ifdef LETKF_WAVE_PROF
+  static unsigned long long* prof_dev = nullptr;
+  if (reg) {
+    if (!prof_dev) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&prof_dev), 26 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(prof_dev, 0, 26 * sizeof(unsigned long long), c->stream));
+    a.prof = prof_dev;
+  }
+#endif
+  if (r.trivial) {
+    HIP_TRY(letkf::launch_trivial_points(a, c->stream));
+    a.skip_trivial = 1;
+  }
+  switch (r.family) {
+    case Family::trio: HIP_TRY(letkf::launch_trio_kernel(a, c->num_cu, c->stream)); break;
+    case Family::wave: HIP_TRY(letkf::launch_wave_kernel(a, c->num_cu, c->stream)); break;
+    case Family::staged:
+      if (int rc = launch_staged(c, a, r, nb, wpp)) return rc;
+      break;
+    case Family::point: HIP_TRY(letkf::launch_point_kernel(a, r.plan, c->stream)); break;
+  }
+#ifdef LETKF_WAVE_PROF
+  if (reg) {
+    unsigned long long h[26];
+    HIP_TRY(hipMemcpyAsync(h, prof_dev, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot = 0;
+    for (int i = 0; i < 10; ++i) tot += h[i];
+    std::fprintf(stderr, "[letkf prof] wave-time share by phase (s_memtime ticks, all waves):");
+    for (int i = 0; i < 10; ++i) std::fprintf(stderr, " p%d=%.1f%%", i, tot ? 100.0 * (double)h[i] / (double)tot : 0.0);
+    std::fprintf(stderr, " total=%llu\n", tot);
+    std::fprintf(stderr, "[letkf prof] first wave start .. last wave end: %llu ticks; waves by units done (0..11+):", h[11] - ~h[10]);
+    for (int i = 12; i < 24; ++i) std::fprintf(stderr, " %llu", h[i]);
+    std::fprintf(stderr, "; units done in all: %llu\n", h[24]);
+  }
+#endif
   if (c->timing) {
     HIP_TRY(hipEventRecord(ev.e1, c->stream));
     c->events.emplace_back(ev.e0, ev.e1);
-    ev.e0 = ev.e1 = nullptr;
+    ev.e0 = ev.e1 = nullptr;   // owned by the context from here
   }
-  c->last_path = std::string(s.gram_mfma ? "staged: letkf_stage_gram_mfma_kernel + " : "staged: letkf_stage_gram_kernel + ") + (s.poly_max_n > 0 ? "letkf_stage_krylov_kernel (CG + Lanczos; points it gives up: " : "") +
-                 (a.k <= 128 ? "letkf_eig_wg_kernel<4,32,32,1>" : "letkf_eig_wg_kernel<4,52,16,2>") +
-                 (a.k > s.wg_max_order ? " / letkf_eig_block_kernel" : "") + (s.poly_max_n > 0 ? ")" : "") + " + letkf_stage_apply_kernel";
+  c->last_path = route_path(a, r);
+#ifdef LETKF_CHECKED
+  if (reg && a.prof) {
+    unsigned long long h[4];
+    HIP_TRY(hipMemcpyAsync(h, a.prof, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h[0])
+      return fail(LETKF_E_HIP, "checked build: bound " + std::to_string(h[0]) + " violated in workgroup " + std::to_string(h[1]) + ": value " +
+                                   std::to_string((long long)h[2]) + " against " + std::to_string((long long)h[3]));
+  }
+#endif
   return LETKF_OK;
 }
 
@@ -778,24 +737,15 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     if (!limited) {
       // workspace: counts [nij1 + 1] int32 | sv_off [nij1 + 1] int64 | scan scratch
       size_t scan_b = 0;
-      {
-        auto in = rocprim::make_transform_iterator(static_cast<const int32_t*>(nullptr), [] __device__(int32_t v) { return (int64_t)v; });
-        HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, in, static_cast<int64_t*>(nullptr), (int64_t)0, (size_t)nij1 + 1,
-                                        rocprim::plus<int64_t>(), c->stream));
-      }
+      HIP_TRY(count_scan(nullptr, &scan_b, nullptr, nullptr, (size_t)nij1 + 1, c->stream));
       const size_t o_off = ((size_t)(nij1 + 1) * 4 + 255) & ~(size_t)255;
       const size_t o_scan = o_off + (((size_t)(nij1 + 1) * 8 + 255) & ~(size_t)255);
-      if (o_scan + scan_b > c->scratch_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-      if (int rc = ensure_bytes(c, &c->scratch, &c->scratch_bytes, o_scan + scan_b + 256)) return rc;
+      if (int rc = grow(c, &c->scratch, &c->scratch_bytes, o_scan + scan_b + 256)) return rc;
       int32_t* cnt = reinterpret_cast<int32_t*>(c->scratch);
       int64_t* soff = reinterpret_cast<int64_t*>(c->scratch + o_off);
       HIP_TRY(hipMemsetAsync(cnt + nij1, 0, 4, c->stream));
       HIP_TRY(letkf::launch_survivors(*t, 0, nij1, rig, rjg, 0, cnt, nullptr, nullptr, c->num_cu, c->stream));
-      {
-        auto in = rocprim::make_transform_iterator(static_cast<const int32_t*>(cnt), [] __device__(int32_t v) { return (int64_t)v; });
-        HIP_TRY(rocprim::exclusive_scan(c->scratch + o_scan, scan_b, in, soff, (int64_t)0, (size_t)nij1 + 1, rocprim::plus<int64_t>(),
-                                        c->stream));
-      }
+      HIP_TRY(count_scan(c->scratch + o_scan, &scan_b, cnt, soff, (size_t)nij1 + 1, c->stream));
       std::vector<int64_t> hoff((size_t)nij1 + 1);
       HIP_TRY(hipMemcpyAsync(hoff.data(), soff, ((size_t)nij1 + 1) * 8, hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -811,8 +761,7 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
         while (c1 < nij1 && (hoff[c1 + 1] - hoff[c0]) * 32 <= list_bytes) ++c1;
         const int64_t nsv = hoff[c1] - hoff[c0];
         const size_t need = (size_t)(nsv > 0 ? nsv : 1) * 32 + 256;
-        if (need > c->list_ws_bytes) HIP_TRY(hipStreamSynchronize(c->stream));   // (the previous batch's solve may still read the old buffer)
-        if (int rc = ensure_bytes(c, &c->list_ws, &c->list_ws_bytes, need)) return rc;
+        if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, need)) return rc;
         // entry e of column b is addressed as sv[4 * sv_off[b] + ...] with the GLOBAL offsets: shift the base
         double* sv = reinterpret_cast<double*>(c->list_ws) - 4 * hoff[c0];
         HIP_TRY(letkf::launch_survivors(*t, c0, c1 - c0, rig, rjg, 1, nullptr, reinterpret_cast<const long*>(soff + c0), sv, c->num_cu,
@@ -851,15 +800,10 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
   } ring_keep_guard(c);
   // workspace: counts [npts] int32 | obs_off [npts + 1] int64 | scan scratch
   size_t scan_bytes = 0;
-  {
-    auto in = rocprim::make_transform_iterator(static_cast<const int32_t*>(nullptr), [] __device__(int32_t v) { return (int64_t)v; });
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, in, static_cast<int64_t*>(nullptr), (int64_t)0, (size_t)npts + 1,
-                                    rocprim::plus<int64_t>(), c->stream));
-  }
+  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, (size_t)npts + 1, c->stream));
   const size_t off_counts = 0, off_off = ((size_t)(npts + 1) * 4 + 255) & ~(size_t)255;
   const size_t off_scan = off_off + (((size_t)(npts + 1) * 8 + 255) & ~(size_t)255);
-  if (off_scan + scan_bytes > c->scratch_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (int rc = ensure_bytes(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
   int32_t* counts = reinterpret_cast<int32_t*>(c->scratch + off_counts);
   int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
   // ---- count pass over all levels, prefix sum, level boundaries back to the host
@@ -867,11 +811,7 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
   if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, counts, nullptr, nullptr, nullptr, nullptr,
                                             nullptr, nullptr))
     return rc;
-  {
-    auto in = rocprim::make_transform_iterator(static_cast<const int32_t*>(counts), [] __device__(int32_t v) { return (int64_t)v; });
-    HIP_TRY(rocprim::exclusive_scan(c->scratch + off_scan, scan_bytes, in, off, (int64_t)0, (size_t)npts + 1,
-                                    rocprim::plus<int64_t>(), c->stream));
-  }
+  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, (size_t)npts + 1, c->stream));
   if (nobs_out) {
     HIP_TRY(hipMemcpyAsync(nobs_out, counts, (size_t)npts * 4, hipMemcpyDeviceToDevice, c->stream));
     // (as the list-free route reports them: the reference does not run obs_local where beta = 0, letkf_tools.f90:333-359)
@@ -892,8 +832,7 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     const size_t n1 = (size_t)(nnz > 0 ? nnz : 1);
     const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
     const size_t need = o_rl + n1 * 8 + 256;
-    if (need > c->list_ws_bytes) HIP_TRY(hipStreamSynchronize(c->stream));   // (the previous slab's solve may still read the old buffer)
-    if (int rc = ensure_bytes(c, &c->list_ws, &c->list_ws_bytes, need)) return rc;
+    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, need)) return rc;
     // the kernels address list entry e of point p as base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
     int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - lev_off[l0];
     double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - lev_off[l0];
@@ -1018,19 +957,14 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
   const size_t ncg = (size_t)nij1 * ng;
   // aux: counts [ncg + 1] int32 | goff [ncg + 1] int64 | scan scratch | roff [batch]
   size_t scan_b = 0;
-  {
-    auto in = rocprim::make_transform_iterator(static_cast<const int32_t*>(nullptr), [] __device__(int32_t v) { return (int64_t)v; });
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_b, in, static_cast<int64_t*>(nullptr), (int64_t)0, ncg + 1, rocprim::plus<int64_t>(),
-                                    c->stream));
-  }
+  HIP_TRY(count_scan(nullptr, &scan_b, nullptr, nullptr, ncg + 1, c->stream));
   const size_t o_off = ((ncg + 1) * 4 + 255) & ~(size_t)255, o_scan = o_off + (((ncg + 1) * 8 + 255) & ~(size_t)255);
   const size_t o_roff = o_scan + ((scan_b + 255) & ~(size_t)255);
   const size_t nring1 = (size_t)letkf::search_rings_count() + 1;   // ring starts per (column, group)
   const size_t roff_b = (ncg * nring1 * 4 + 255) & ~(size_t)255;
   const size_t o_kref = o_roff + roff_b;                            // kref [ngroup] | min err [nctype] (general ring key)
   const size_t need_aux = o_kref + ((size_t)ng + (size_t)t->nctype) * 8 + 256;
-  if (need_aux > c->ring_aux_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (int rc = ensure_bytes(c, &c->ring_aux, &c->ring_aux_bytes, need_aux)) return rc;
+  if (int rc = grow(c, &c->ring_aux, &c->ring_aux_bytes, need_aux)) return rc;
   int32_t* cnt = reinterpret_cast<int32_t*>(c->ring_aux);
   int64_t* goff = reinterpret_cast<int64_t*>(c->ring_aux + o_off);
   int32_t* roff = reinterpret_cast<int32_t*>(c->ring_aux + o_roff);
@@ -1068,10 +1002,7 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
   }
   HIP_TRY(hipMemsetAsync(cnt + ncg, 0, 4, c->stream));
   HIP_TRY(letkf::launch_ring_survivors(*t, 0, nij1, rig, rjg, 0, cnt, nullptr, nullptr, nullptr, nullptr, c->num_cu, c->stream));
-  {
-    auto in = rocprim::make_transform_iterator(static_cast<const int32_t*>(cnt), [] __device__(int32_t v) { return (int64_t)v; });
-    HIP_TRY(rocprim::exclusive_scan(c->ring_aux + o_scan, scan_b, in, goff, (int64_t)0, ncg + 1, rocprim::plus<int64_t>(), c->stream));
-  }
+  HIP_TRY(count_scan(c->ring_aux + o_scan, &scan_b, cnt, goff, ncg + 1, c->stream));
   std::vector<int64_t> hoff(ncg + 1);
   HIP_TRY(hipMemcpyAsync(hoff.data(), goff, (ncg + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1104,7 +1035,7 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
     const size_t want = (size_t)hoff[ncg] * 32 + 256;
     keep = want <= c->ring_ws_bytes + fr / 2;
     if (keep && want > c->ring_ws_bytes) {
-      // the exact size (ensure_bytes would ask for a quarter more), and a failure is no error: the batches below need 8 GiB
+      // the exact size (grow would ask for a quarter more), and a failure is no error: the batches below need 8 GiB
       HIP_TRY(hipStreamSynchronize(c->stream));
       if (c->ring_ws) HIP_TRY(hipFree(c->ring_ws));
       c->ring_ws = nullptr;
@@ -1125,8 +1056,7 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
     while (c1 < nij1 && (hoff[(size_t)(c1 + 1) * ng] - hoff[(size_t)c0 * ng]) * 32 <= budget) ++c1;
     const int64_t nsv = hoff[(size_t)c1 * ng] - hoff[(size_t)c0 * ng];
     const size_t need = (size_t)(nsv > 0 ? nsv : 1) * 32 + 256;
-    if (need > c->ring_ws_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int rc = ensure_bytes(c, &c->ring_ws, &c->ring_ws_bytes, need)) return rc;
+    if (int rc = grow(c, &c->ring_ws, &c->ring_ws_bytes, need)) return rc;
     double* sv = reinterpret_cast<double*>(c->ring_ws) - 4 * hoff[(size_t)c0 * ng];
     const long* gq = reinterpret_cast<const long*>(goff + (size_t)c0 * ng);
     int32_t* rq = roff + (size_t)c0 * ng * nring1;
@@ -1200,8 +1130,7 @@ int letkf_obs_mesh_sort_dev(letkf_ctx* c, const letkf_mesh* m, int64_t nobs, con
   size_t need = 0;
   long ns = 0;
   HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, nullptr, &need, c->num_cu, c->stream));
-  if (need > c->scratch_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (int rc = ensure_bytes(c, &c->scratch, &c->scratch_bytes, need)) return rc;
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
   size_t have = c->scratch_bytes;
   HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, c->scratch, &have, c->num_cu, c->stream));
   *nsorted = ns;
@@ -1329,8 +1258,7 @@ int letkf_monit_dep_dev(letkf_ctx* c, int32_t nid, const int32_t* elem_uid, int6
     return fail(LETKF_E_INVALID, "bad element table / outputs");
   if (nn > 0 && (!elm || !dep || !qc)) return fail(LETKF_E_INVALID, "an observation array is NULL");
   const size_t need = letkf::monit_scratch_bytes(nid, c->num_cu);
-  if (need > c->scratch_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (int rc = ensure_bytes(c, &c->scratch, &c->scratch_bytes, need)) return rc;
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
   HIP_TRY(letkf::launch_monit_dep(nid, elem_uid, nn, elm, dep, qc, nobs, bias, rmse, c->scratch, c->num_cu, c->stream));
   return LETKF_OK;
 }
@@ -1440,8 +1368,7 @@ int letkf_members_alltoall_dev(letkf_ctx* c, void* nccl_comm, int32_t nranks, in
     ptot += pc[r];
   }
   const size_t need = (size_t)(ftot + ptot) * sizeof(double) + 256;
-  if (need > c->scratch_bytes) HIP_TRY(hipStreamSynchronize(c->stream));
-  if (int rc = ensure_bytes(c, &c->scratch, &c->scratch_bytes, need)) return rc;
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
   double* fbuf = reinterpret_cast<double*>(c->scratch);
   double* pbuf = fbuf + ftot;
   const char* what = "";
@@ -1550,7 +1477,7 @@ int core_host(int ne, int nobs, int nobsl, const double* hdxb, const double* rdi
   // scratch layout (doubles): hdxb[n*k] rdiag[n] rloc[n] dep[n] depd[n] infl[1] trans[k*k] pao[k*k] transm[k] transmd[k] | ints: nobsl, status
   const size_t nd = n * k + 4 * n + 1 + 2 * k * k + 2 * k;
   const size_t bytes = nd * sizeof(double) + 4 * sizeof(int);
-  if (int rc = ensure_bytes(c, &c->scratch, &c->scratch_bytes, bytes)) return rc;
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, bytes)) return rc;
   double* d = reinterpret_cast<double*>(c->scratch);
   double* d_h = d;
   double* d_rdiag = d_h + n * k;

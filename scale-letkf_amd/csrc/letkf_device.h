@@ -4,15 +4,42 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
 #include <string>
+#include <utility>
 
 #include "../../include/letkf_amd.h"
 
 namespace letkf {
 
-// LDS scratch of the block Jacobi (letkf_kernels.hip, jacobi_block_mfma), doubles per wave: 512 of the in-register
-// 32 x 32 solver + its packed triangular factor (528).  The host sizes the obs tile region of the one-block kernel by it.
-constexpr int kBlockJacobiScratch = 512 + 528;
+// Dynamic LDS beyond 48 KiB needs the kernel's opt-in.  Applied on every launch: the attribute is per device, and the
+// contexts of one process may live on different devices.
+template <class K>
+inline hipError_t lds_opt_in(K kern, size_t lds) {
+  if (lds <= 48 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// Workgroups of kern resident per CU at `block` threads and `lds` bytes of dynamic LDS on the current device (an
+// instantiation's block and LDS are fixed): queried once per (kernel, device), `fallback` where the query fails.
+inline std::mutex g_resident_mu;
+inline std::map<std::pair<const void*, int>, int> g_resident;
+template <class K>
+inline int resident_blocks(K kern, int block, size_t lds, int fallback) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const std::pair<const void*, int> key(reinterpret_cast<const void*>(kern), dev);
+  std::lock_guard<std::mutex> lock(g_resident_mu);
+  auto it = g_resident.find(key);
+  if (it != g_resident.end()) return it->second;
+  int nb = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, block, lds);
+  (void)hipGetLastError();
+  const int v = (e == hipSuccess && nb > 0) ? nb : fallback;
+  g_resident.emplace(key, v);
+  return v;
+}
 
 // Plan of the solve kernel's dynamic run scheduling (letkf_wave.hip), worked out on the host for the grid that is
 // launched and read by the kernel from its arguments (scalar loads): per XCD range x of the unit ids
@@ -133,19 +160,33 @@ long stage_krylov_hist_doubles(int k);
 hipError_t launch_stage_krylov(const StagedArgs& s, size_t lds_max, hipStream_t st);
 size_t eig_wg_lds_bytes(int NP, int RP, int RBR, int SB);
 int eig_wg_max_order();
+std::string eig_wg_kernel_name(int mcap);   // the instantiation launch_eig_wg launches for order cap mcap
 hipError_t launch_eig_wg(const EigArgs& e, int mcap, int num_cu, hipStream_t st);
 hipError_t launch_eig_block(const EigArgs& e, int kmax, int num_cu, hipStream_t st);
 long staged_ws_per_point(int k, int nv, int kkout, long hist);
 hipError_t launch_stage_gram(const StagedArgs& s, size_t lds_max, hipStream_t st);
 hipError_t launch_stage_gram_mfma(const StagedArgs& s, hipStream_t st);
+// the Gram kernels of a staged call: the matrix-core one for the loop body (mode 0), letkf_stage_gram_kernel for every other
+// mode and for the points the first one leaves
+struct GramKernels {
+  bool mfma, plain;
+};
+GramKernels stage_gram_kernels(int k, int mode);
 hipError_t launch_stage_apply(const StagedArgs& s, hipStream_t st);
 
-struct LaunchPlan {
+// Launch plan of letkf_point_kernel (letkf_kernels.hip point_kernel_plan): the LDS instantiation, or BIG with G, U, X in a
+// per-workgroup HBM workspace of ws_per_block doubles
+struct PointPlan {
   bool big;
   int rmax;
   int grid, block;
   size_t lds_bytes;
+  int ldg, ldy, tn;
+  long ws_per_block;
+  size_t ws_bytes() const { return big ? (size_t)grid * (size_t)ws_per_block * sizeof(double) : 0; }
 };
+// false: the ensemble's vectors do not fit the LDS even with G, U, X in HBM
+bool point_kernel_plan(int k, int nv, long npts, int num_cu, size_t lds_max, PointPlan* p);
 
 struct SearchArgs {
   letkf_search_tables t;
@@ -185,15 +226,17 @@ hipError_t launch_search_columns_limited(const letkf_search_tables& t, long nij1
                                          const double* rjg, const double* rlev, const double* rz, int fill, int* counts,
                                          const long* obs_off, int* obs_idx, double* rdiag_l, double* rloc_l,
                                          int* nobs_ctype, double* cutd_ctype, int num_cu, hipStream_t st);
-hipError_t launch_point_kernel(const PointArgs& a, const LaunchPlan& p, hipStream_t st);
+hipError_t launch_point_kernel(const PointArgs& a, const PointPlan& p, hipStream_t st);
 bool wave_kernel_supports(int k, int nv, int mode);
 int wave_kernel_kr(int k);   // rows of the instantiation that serves k
+int wave_kernel_nw(int k);   // ... and its wavefronts per point
 void wave_launch_shape(int k, int mode, long npts, int num_cu, int run_req, long stride, int* run_len, int* grid,
                        size_t* ws_bytes);
 hipError_t launch_wave_kernel(const PointArgs& a, int num_cu, hipStream_t st);
 // three points per wave for k <= 20 (letkf_trio.hip)
 bool trio_kernel_supports(const PointArgs& a);
 hipError_t launch_trio_kernel(const PointArgs& a, int num_cu, hipStream_t st);
+int trio_kernel_kr(int k);
 int trio_points_per_wave(int k);
 int sched_plan_check(long npts, long stride, int run_len, int grid, int ppw, int resident_per_xcd, int ub_of);
 bool trivial_pass_supports(const PointArgs& a);

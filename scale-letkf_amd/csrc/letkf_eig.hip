@@ -513,11 +513,7 @@ template <int NP, int RP, int RBR, int SB>
 static hipError_t launch_eig_one(const EigArgs& e, int grid, hipStream_t st) {
   const size_t lds = eig_wg_lds_bytes(NP, RP, RBR, SB);
   auto kern = letkf_eig_wg_kernel<NP, RP, RBR, SB>;
-  if (lds > 48 * 1024) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds);
-    if (err != hipSuccess) return err;
-  }
+  if (hipError_t err = lds_opt_in(kern, lds)) return err;
 #ifdef LETKF_WAVE_PROF
   unsigned long long z[8] = {0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_eig_prof), z, sizeof z);
@@ -537,18 +533,19 @@ static hipError_t launch_eig_one(const EigArgs& e, int grid, hipStream_t st) {
 #endif
 int eig_wg_max_order() { return 208; }
 
+std::string eig_wg_kernel_name(int mcap) {
+  return mcap <= 128 ? "letkf_eig_wg_kernel<4,32,32,1>" : "letkf_eig_wg_kernel<4,52," + std::to_string(EIG_RBR2) + ",2>";
+}
+
 // mcap: upper bound of the matrix orders in this batch (the instantiation is chosen once per launch; points whose
 // order does not fit skip themselves and are left to the block Jacobi)
 hipError_t launch_eig_wg(const EigArgs& e, int mcap, int num_cu, hipStream_t st) {
   const int grid = (int)(e.npts < 4L * num_cu ? (e.npts > 0 ? e.npts : 1) : 4L * num_cu);
   if (mcap <= 128) return launch_eig_one<4, 32, 32, 1>(e, grid, st);
   // (an <8, 26, RBR, 2> shape -- 16 waves, a quarter of the LDS rows per lane -- was tried for this range: 128 VGPRs per
-  // lane do not hold the two columns and the prefetch rings, 130-200 B/lane of scratch, C3-slab 171 ms against 107 ms)
-#ifdef EIG_SHAPE6
-  return launch_eig_one<6, 35, EIG_SHAPE6, 2>(e, grid, st);   // 12 waves = 3 per SIMD (168 VGPRs), EIG_SHAPE6 of the 35 rows of B in registers
-#else
+  // lane do not hold the two columns and the prefetch rings, 130-200 B/lane of scratch, C3-slab 171 ms against 107 ms; a
+  // <6, 35, RBR, 2> shape, 12 waves = 3 per SIMD, spills 60-100 registers: profiles/HISTORY.md)
   return launch_eig_one<4, 52, EIG_RBR2, 2>(e, grid, st);
-#endif
 }
 
 }  // namespace letkf

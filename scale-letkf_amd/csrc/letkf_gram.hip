@@ -464,11 +464,16 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_gram_m
   }
 }
 
+// the loop body's points are this kernel's but for orders beyond 512 (gram_mfma_takes), which only k > 512 has
+GramKernels stage_gram_kernels(int k, int mode) {
+  if (mode != 0) return {false, true};
+  return {true, !gram_mfma_takes(k, k)};
+}
+
 hipError_t launch_stage_gram_mfma(const StagedArgs& s, hipStream_t st) {
   auto go = [&](auto kern, int nwv) -> hipError_t {
     const size_t lds = ((size_t)(nwv == 4 ? kGmPanelSmall : kGmPanelBig) * 128 + 4 * (size_t)(nwv == 4 ? 512 : 1024) + 8) * sizeof(double);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = lds_opt_in(kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)s.nbatch), dim3(64 * nwv), lds, st, s);
     return hipGetLastError();
   };

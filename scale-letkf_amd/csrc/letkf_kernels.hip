@@ -241,7 +241,7 @@ __device__ __forceinline__ int jacobi_stream(double* __restrict__ G, const int l
 // arithmetic on the matrix pipe, three 64-lane shuffle reductions per column pair gone, fewer outer sweeps.
 // A sweep counts as converged when none of its block pairs needed more than the verification cycle of the inner solve.
 // wscr: kBlkScr doubles of LDS per wave (512 of the inner solver + the packed 32 x 32 triangular factor).
-constexpr int kBlkScr = kBlockJacobiScratch;
+constexpr int kBlkScr = 512 + 528;   // (point_kernel_plan sizes the one-block kernel's obs tile region by it)
 // (the inner solves stop at the point kernels' |cos| <= 1e-12: with round 2's 1e-10 the block iteration alone "converges" at
 // cond(A) ~ 1e2 with an analysis 180 cond eps off the oracle; at 1e-12 it hands over to the scalar iteration there: 1.6 cond eps)
 constexpr int kBlkFlat = 3, kBlkSweepCap = 16;
@@ -966,11 +966,7 @@ hipError_t launch_eig_block(const EigArgs& e, int kmax, int num_cu, hipStream_t 
   if (waves < 4) waves = 4;
   if (waves > 12) waves = 12;
   const size_t lds = (size_t)waves * kBlkScr * sizeof(double);
-  if (lds > 48 * 1024) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_eig_block_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return err;
-  }
+  if (hipError_t err = lds_opt_in(&letkf_eig_block_kernel, lds)) return err;
   const long g = e.npts < 2L * num_cu ? (e.npts > 0 ? e.npts : 1) : 2L * num_cu;
   hipLaunchKernelGGL(letkf_eig_block_kernel, dim3((unsigned)g), dim3(64 * waves), lds, st, e);
   return hipGetLastError();
@@ -1107,18 +1103,72 @@ __global__ void ens_spread_kernel(int k, int nv, long npts, const double* x, lon
 }
 
 // ------------------------------------------------------------------ host-callable launchers
+// LDS of letkf_point_kernel in doubles: its carve (vectors, per-variable scalars, obs-tile weights, then G and the obs tile
+// that U and X alias -- or, BIG, the obs tile alone)
+static size_t point_lds_doubles(bool big, int k, int nv, int ldg, int ldy, int tn) {
+  const int nb = nv + 2;
+  size_t fixed = 7 * (size_t)k + 6 * (size_t)nv + 16 + 3 * (size_t)tn + 1;
+  if (big) return fixed + (size_t)tn * ldy;
+  size_t g = (size_t)k * ldg;
+  g += g & 1;
+  size_t tile = (size_t)tn * ldy;
+  size_t ux = (size_t)k * nb + (size_t)nv * k;
+  return fixed + g + (tile > ux ? tile : ux);
+}
+
+bool point_kernel_plan(int k, int nv, long npts, int num_cu, size_t lds_max, PointPlan* p) {
+  p->ldg = k | 1;
+  p->ldy = (k + 3) & ~3;
+  if (k <= 128) {
+    p->tn = 32;
+    const size_t bytes = 8 * point_lds_doubles(false, k, nv, p->ldg, p->ldy, p->tn);
+    if (bytes <= lds_max) {
+      p->big = false;
+      p->rmax = (k <= 32) ? 4 : (k <= 56) ? 7 : (k <= 64) ? 8 : (k <= 104) ? 13 : 16;
+      p->block = 256;
+      p->lds_bytes = bytes;
+      const long g = (long)num_cu * 32;
+      p->grid = (int)(npts < g ? (npts > 0 ? npts : 1) : g);
+      p->ws_per_block = 0;
+      return true;
+    }
+  }
+  // large-k spill path: G, U, X in a per-workgroup HBM workspace, obs tile sized to what LDS is left
+  p->big = true;
+  p->rmax = 0;
+  // one wave per block pair of the block Jacobi (k/32 pairs per round), 4..12 waves: 12 waves = 3 per SIMD keeps
+  // 170 VGPRs per lane for the in-register 32 x 32 eigensolver; one workgroup per CU
+  const int nblk = (k + 15) / 16, nbe = nblk + (nblk & 1);
+  int waves = nbe / 2;
+  if (waves < 4) waves = 4;
+  if (waves > 12) waves = 12;
+  p->block = 64 * waves;
+  const size_t budget = 128 * 1024 / 8;  // doubles of LDS we allow ourselves
+  const size_t fixed = point_lds_doubles(true, k, nv, p->ldg, p->ldy, 0);
+  long tn = fixed < budget ? (long)((budget - fixed) / (p->ldy + 3)) : 0;
+  if (tn > 32) tn = 32;
+  if (tn < 4) tn = 4;
+  // the obs tile region doubles as the per-wave scratch of the block Jacobi
+  while ((size_t)tn * p->ldy < (size_t)waves * kBlkScr) ++tn;
+  p->tn = (int)tn;
+  p->lds_bytes = 8 * point_lds_doubles(true, k, nv, p->ldg, p->ldy, p->tn);
+  if (p->lds_bytes > lds_max) return false;
+  const long g = (long)num_cu;
+  p->grid = (int)(npts < g ? (npts > 0 ? npts : 1) : g);
+  const int nb = nv + 2;
+  const long w = (long)k * p->ldg + (long)k * nb + (long)nv * k;
+  p->ws_per_block = (w + 1) & ~1L;
+  return true;
+}
+
 template <bool BIG, int RMAX, int MAXT>
 static hipError_t launch_one(const PointArgs& a, int grid, int block, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_point_kernel<BIG, RMAX, MAXT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = lds_opt_in(&letkf_point_kernel<BIG, RMAX, MAXT>, lds)) return e;
   hipLaunchKernelGGL((letkf_point_kernel<BIG, RMAX, MAXT>), dim3(grid), dim3(block), lds, st, a);
   return hipGetLastError();
 }
 
-hipError_t launch_point_kernel(const PointArgs& a, const LaunchPlan& p, hipStream_t st) {
+hipError_t launch_point_kernel(const PointArgs& a, const PointPlan& p, hipStream_t st) {
   if (p.big) return launch_one<true, 0, 1>(a, p.grid, p.block, p.lds_bytes, st);
   switch (p.rmax) {
     case 4: return launch_one<false, 4, 1>(a, p.grid, p.block, p.lds_bytes, st);

@@ -654,10 +654,7 @@ hipError_t launch_stage_krylov(const StagedArgs& s, size_t lds_max, hipStream_t 
   if (lds_of(kDcap) > budget) return hipErrorInvalidValue;
   auto go = [&](auto kern, int nthr, int dcap, int cls) -> hipError_t {
     const size_t lds = lds_of(dcap);
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)s.nbatch), dim3(nthr), lds, st, s, nr16cap, (int)r0, dcap, cls);
     return hipGetLastError();
   };

@@ -210,11 +210,7 @@ hipError_t launch_obs_departure(const letkf_qc_params& p, long nobs, const int* 
                                 double* ensval, long kld, double* val, int* qc, int num_cu, hipStream_t st) {
   if (nobs <= 0) return hipSuccess;
   const size_t lds = (size_t)kDepRows * (size_t)(kld | 1) * sizeof(double);
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&departure_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = lds_opt_in(&departure_kernel, lds)) return e;
   const int grid = grid_for((nobs + kDepRows - 1) / kDepRows, 1, num_cu);
   hipLaunchKernelGGL(departure_kernel, dim3(grid), dim3(64), lds, st, p, nobs, elm, dat, err, ensval, kld, val, qc);
   return hipGetLastError();

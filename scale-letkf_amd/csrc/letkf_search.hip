@@ -1183,9 +1183,7 @@ hipError_t launch_search_columns_limited(const letkf_search_tables& t, long nij1
   ColLimArgs a{{t, nij1, nlev, rig, rjg, rlev, rz, fill, counts, obs_off, obs_idx, rdiag_l, rloc_l, nobs_ctype},
                cutd_ctype};
   const size_t lds = (size_t)4 * (4 * kSurvL + ((nlev + 1) & ~1)) * sizeof(double);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_search_columns_limited_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
+  if (hipError_t e = lds_opt_in(&letkf_search_columns_limited_kernel, lds)) return e;
   const long nwg = (nij1 + 3) / 4;
   const long g = (long)num_cu * 8;
   const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
@@ -1793,10 +1791,7 @@ hipError_t launch_search_columns(const letkf_search_tables& t, long nij1, int nl
   ColArgs a{t, nij1, nlev, rig, rjg, rlev, rz, fill, counts, obs_off, obs_idx, rdiag_l, rloc_l, nobs_ctype};
   const size_t lds = (size_t)4 * (4 * kSurv + 2 * ((nlev + 1) & ~1)) * sizeof(double);
   auto kern = fill ? &letkf_search_columns_kernel<true> : &letkf_search_columns_kernel<false>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = lds_opt_in(kern, lds)) return e;
   const long nwg = (nij1 + 3) / 4;
   const long g = (long)num_cu * 8;
   const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
@@ -1810,9 +1805,7 @@ hipError_t launch_search(const SearchArgs& a, int num_cu, hipStream_t st) {
   const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
   // the candidate cache is only touched in limited mode: without a limit the kernel keeps its full occupancy
   const size_t lds = a.limited ? (size_t)4 * 4 * kCacheCap * sizeof(double) : 0;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_search_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
+  if (hipError_t e = lds_opt_in(&letkf_search_kernel, lds)) return e;
   hipLaunchKernelGGL(letkf_search_kernel, dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }

@@ -873,11 +873,7 @@ hipError_t launch_stage_gram(const StagedArgs& s, size_t lds_max, hipStream_t st
   int tn = 32;
   while (tn > 4 && fixed + (size_t)tn * ldmax * sizeof(double) > budget) tn -= 4;
   const size_t lds = fixed + (size_t)tn * ldmax * sizeof(double);
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_stage_gram_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = lds_opt_in(&letkf_stage_gram_kernel, lds)) return e;
   hipLaunchKernelGGL(letkf_stage_gram_kernel, dim3((unsigned)s.nbatch), dim3(kGBlock), lds, st, s, tn, ldmax);
   return hipGetLastError();
 }
@@ -898,10 +894,7 @@ hipError_t launch_stage_apply(const StagedArgs& s, hipStream_t st) {
   const size_t pcq = (size_t)stage_apply_pcq_doubles(k, s.A.nv);
   const size_t lds = (fixed + pcq) * sizeof(double);
   auto go = [&](auto kern, int nthr) -> hipError_t {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kern, lds)) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)s.nbatch), dim3(nthr), lds, st, s, (int)pcq);
     return hipGetLastError();
   };

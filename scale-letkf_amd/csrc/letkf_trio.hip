@@ -912,29 +912,13 @@ template <int KR, int P>
 hipError_t launch_trio(const PointArgs& a, int num_cu, hipStream_t st) {
   using L = TrioLds<KR, P>;
   const size_t lds = (size_t)4 * L::total * sizeof(double);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_trio_kernel<KR, P>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  static int occ = 0;
-  if (occ == 0) {
-    int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, letkf_trio_kernel<KR, P>, 256, lds);
-    occ = (e == hipSuccess && nb > 0) ? nb : 2;
-    (void)hipGetLastError();
-  }
+  if (hipError_t e = lds_opt_in(&letkf_trio_kernel<KR, P>, lds)) return e;
+  const int occ = resident_blocks(&letkf_trio_kernel<KR, P>, 256, lds, 2);
   if (!a.sched) return hipErrorInvalidValue;
   const long res = (long)occ * num_cu;
-#ifndef TRIO_MIN_RUN
-#define TRIO_MIN_RUN 4
-#endif
-#ifndef TRIO_UNITS_PER_WAVE
-#define TRIO_UNITS_PER_WAVE 2
-#endif
-  long rl_ = a.npts / (P * TRIO_UNITS_PER_WAVE * res * 4);
-  if (rl_ < TRIO_MIN_RUN) rl_ = TRIO_MIN_RUN;
+  constexpr long kMinRun = 4, kUnitsPerWave = 2;
+  long rl_ = a.npts / (P * kUnitsPerWave * res * 4);
+  if (rl_ < kMinRun) rl_ = kMinRun;
   if (rl_ > a.run_len) rl_ = a.run_len;
   const long S = a.warm_stride > 1 ? a.warm_stride : 1, rl = rl_ > 1 ? rl_ : 1;
   const long nruns = S * ((a.npts / S + rl - 1) / rl);
@@ -947,8 +931,8 @@ hipError_t launch_trio(const PointArgs& a, int num_cu, hipStream_t st) {
   // shorter runs then (the first point of a run starts cold), down to 4 points, until there are two units per wave
   {
     const long slots = res * 4;
-    long want = a.npts / (P * TRIO_UNITS_PER_WAVE * slots);
-    if (want < TRIO_MIN_RUN) want = TRIO_MIN_RUN;
+    long want = a.npts / (P * kUnitsPerWave * slots);
+    if (want < kMinRun) want = kMinRun;
     if (b.run_len > want) b.run_len = (int)want;
   }
   sched_make_plan(b.plan, a.npts, a.warm_stride, b.run_len, grid, 4, 256, P);   // units of P runs
@@ -964,17 +948,20 @@ hipError_t launch_trio(const PointArgs& a, int num_cu, hipStream_t st) {
 
 }  // namespace
 
-// the calls this kernel serves (launch() of letkf_api.hip asks before it takes the register kernel's route)
+// the calls this kernel serves once the streaming pre-pass (letkf_trivial.hip) has done the trivial points -- pick_route of
+// letkf_api.hip adds that condition
 bool trio_kernel_supports(const PointArgs& a) {
-  return a.mode == 0 && a.nv == 11 && a.k >= 2 && a.k <= 20 && a.skip_trivial && !a.trans_out && !a.pa_out && !a.transm_out && !a.transmd_out &&
+  return a.mode == 0 && a.nv == 11 && a.k >= 2 && a.k <= 20 && !a.trans_out && !a.pa_out && !a.transm_out && !a.transmd_out &&
          a.gues && a.anal;
 }
+
+int trio_kernel_kr(int k) { return k <= 16 ? 16 : 20; }
 
 hipError_t launch_trio_kernel(const PointArgs& a, int num_cu, hipStream_t st) {
   // (P = 5 for k <= 10 -- five segments of <= 5 slots on the line of 32, staging batches of 192 -- was measured, A/B in one call:
   // C2's grid at MEMBER = 10 44.0 -> 43.5 ms, at MEMBER = 3 37.1 -> 38.7 ms: the group waits for the slowest of five, the parks
   // crowd the staging area.  Three everywhere.)
-  if (a.k <= 16) return launch_trio<16, 3>(a, num_cu, st);
+  if (trio_kernel_kr(a.k) == 16) return launch_trio<16, 3>(a, num_cu, st);
   return launch_trio<20, 3>(a, num_cu, st);
 }
 int trio_points_per_wave(int) { return 3; }

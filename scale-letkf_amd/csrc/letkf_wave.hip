@@ -1936,30 +1936,15 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, NW == 1 ? wave_occupancy(
 // ------------------------------------------------------------------ host launcher
 template <int KR, int NV, bool KKOUT, int NW, int FUSED = 0>
 static hipError_t launch_wave(const PointArgs& a, int num_cu, hipStream_t st) {
-#ifdef LETKF_LDS_PAD   // A/B knob (make VARIANT=...): extra LDS per workgroup -- what does a workgroup less per CU cost?
-  const size_t lds = (size_t)(NW == 1 ? 4 : 1) * wave_slice_doubles(KR, NV, NW) * sizeof(double) + LETKF_LDS_PAD;
-#else
   const size_t lds = (size_t)(NW == 1 ? 4 : 1) * wave_slice_doubles(KR, NV, NW) * sizeof(double);
-#endif
   if (a.k < wave_kmin(KR, NW) || a.k > KR) return hipErrorInvalidValue;   // the Gram assumes its full member blocks
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = lds_opt_in(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, lds)) return e;
   // Dynamic scheduling: a grid of exactly the workgroups that are resident together (every wave owns its first unit by
   // its position, the rest is drawn; a workgroup that had to wait for a slot would sit on its first unit until the others
   // have drawn everything else).  The PROF twin's static dealing keeps round 1's oversubscribed grid.
   int grid = a.wave_grid;
   if (a.sched) {
-    static int occ = 0;                        // (per instantiation)
-    if (occ == 0) {
-      int nb = 0;
-      hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>,
-                                                                  NW == 1 ? 256 : 128, lds);
-      occ = (e == hipSuccess && nb > 0) ? nb : (NW == 1 ? 2 : 1);
-      (void)hipGetLastError();
-    }
+    const int occ = resident_blocks(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, NW == 1 ? 256 : 128, lds, NW == 1 ? 2 : 1);
     const long res = (long)occ * num_cu;
     const long S = a.warm_stride > 1 ? a.warm_stride : 1, rl = a.run_len > 1 ? a.run_len : 1;
     const long nruns = S * ((a.npts / S + rl - 1) / rl);
@@ -2007,13 +1992,14 @@ static int wave_kr(int k) { return wave_kernel_kr(k); }
 int wave_kernel_kr(int k) {
   return k <= 16 ? 16 : k <= 20 ? 20 : k <= 32 ? 32 : k <= 48 ? 48 : k <= 50 ? 50 : k <= 62 ? 64 : k <= 64 ? 64 : k <= 80 ? 80 : 100;
 }
+int wave_kernel_nw(int k) { return k <= 62 ? 1 : 2; }
 
 // Launch shape of the wave kernel: run length of the warm-started runs, grid, and the bytes of warm-start workspace
 // (one [KR][64] slot per resident-or-not wave of the grid).  run_req: 0 = library default, 1 = every point cold,
 // n > 1 = runs of n points.
 void wave_launch_shape(int k, int mode, long npts, int num_cu, int run_req, long stride, int* run_len, int* grid,
                        size_t* ws_bytes) {
-  const bool one_wave = k <= 62;
+  const bool one_wave = wave_kernel_nw(k) == 1;
   const long ppw = one_wave ? 4 : 1;           // points in flight per workgroup
   int R = 1;
   if (mode != 1) {

@@ -11,7 +11,7 @@ CANARY = 0x7FF4DEADBEEF0001
 TAIL = 64                                   # NaN doubles behind the observation table (over-reads land there)
 
 # route name -> (k, nv, k x k outputs requested, substrings ctx().last_path() must contain, ... it must not contain).
-# Where each route begins: letkf_api.hip launch() / launch_staged(), letkf_trio.hip trio_kernel_supports.
+# Where each route is decided: letkf_api.hip pick_route.
 ROUTES = {
     "trio16": (9, 11, None, ["letkf_trio_kernel<KR=16"], []),
     "trio16_k16": (16, 11, None, ["letkf_trio_kernel<KR=16"], []),
@@ -34,6 +34,7 @@ ROUTES = {
     "staged_wg": (144, 11, "trans", ["staged:", "letkf_eig_wg_kernel"], ["letkf_eig_block_kernel", "krylov"]),
     "staged_block": (250, 11, None, ["staged:", "letkf_eig_block_kernel"], []),
     "point": (20, 15, None, ["letkf_point_kernel"], []),
+    "point_big": (144, 15, None, ["letkf_point_kernel<BIG>"], []),
 }
 # one representative of every route for the per-axis tests (each axis reaches every route at least once)
 AXIS_ROUTES = ["trio16", "trio20", "wave1", "wave1_trans_k20", "wave2_pa", "staged_poly", "staged_poly_nv7", "staged_wg",
