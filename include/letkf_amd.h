@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LETKF_AMD_ABI_VERSION 8
+#define LETKF_AMD_ABI_VERSION 9
 
 /* host-side errors (function return values) */
 #define LETKF_OK 0
@@ -722,8 +722,72 @@ int letkf_obs_table_download(letkf_ctx *ctx, const letkf_obs_table *tab, double 
                              double *ob_rj, double *ob_lev, double *ob_dat, double *ob_err, int32_t *ac_ext);
 int letkf_obs_table_destroy(letkf_obs_table *tab);
 
-/* Name(s) of the kernel(s) the context's last letkf_das_points*_dev / letkf_core_batch_dev call went through, as a
- * NUL-terminated string (truncated to len): what bench.py reports as roofline.kernel. */
+/*---------------------------------------------------------------------------
+ * (10, ABI 9) Ensemble forecast sensitivity to observations (EFSO): the loop of das_efso,
+ *     scale/letkf/letkf_tools.f90:1158-1302 (commented out in the reference, ported there from the SPEEDY/GFS system
+ *     of scale/letkf/efso.f90), for SCALE's point layout.  For every point p and every entry (row j, rdiag, rloc) of
+ *     its local list L_p:
+ *       w_p(t, m)  = sum over v with term_of_var[v] = t (and v in var_mask) of fcst(p, m, v) * fcer(p, v)   ("work1")
+ *       djdy(t, j) += (rloc / rdiag) * sum_m ensval[j*kld + m] * w_p(t, m)                                ("djdy")
+ *     and afterwards obsense(t, j) = djdy(t, j) * dep[j] (:1283-1290).  t = 0..nterm-1 counts the energy terms
+ *     (das_efso's 1 = U/V, 2 = T, 3 = Q; the map is the caller's), m = 0..k-1 the members.
+ *     Inputs the host prepares, as the reference does before das_efso (efso.f90:100-120, lnorm in efso_tools.f90):
+ *       fcst   C^1/2 X^f_t, the normed forecast perturbations, element (p, m, v) at p*sp + m*sm + v*sv
+ *       fcer   C^1/2 (e^f + e^g) / (2 (K-1)), element (p, v) at p*fsp + v*fsv
+ *       ensval Y^a = H X^a, the analysis ensemble's perturbations in observation space, row j member-fastest
+ *              (e.g. H(x) of the analysis members through letkf_obs_departure_dev), only columns 0..k-1 are read
+ *       dep    y - H(mean of the background) (obsda_sort%val)
+ *     rdiag_l / rloc_l are the lists' entries as obs_local returns them (the loop body's lists, section 2), so
+ *     rloc / rdiag is the rho R^-1 of the analysis.  One call per variable-localisation class with that class's lists
+ *     and var_mask; djdy accumulates across the calls (INOUT: the caller zeroes it first).  2-D variables (nv2d = 0
+ *     in the reference's SCALE build) can be a further call with nlev = 1.
+ *     djdy and obsense: dev, element (t, j) at j*nterm + t -- the reference's djdy(nterm, nobstotal).
+ *     Deterministic: no floating-point atomics; each row's contributions are added to djdy(:, j) in ascending point
+ *     order, so two identical calls give identical bits, and letkf_efso_columns_dev gives the bits of
+ *     letkf_efso_points_dev on the same lists whatever list_bytes / pair_bytes cut them into.  Rows no point reaches
+ *     are not written.  Rows outside [0, nobs) in obs_idx are skipped.
+ *     LETKF_E_INVALID: nterm outside 1..4, k < 2, nv outside 1..32, kld < k, a term_of_var value outside
+ *     -1..nterm-1, a required pointer NULL, or 4 * nterm * k doubles (w_p of the four waves of a workgroup) beyond
+ *     the device's LDS per workgroup: k <= 1280 at nterm = 4 with 160 KiB.
+ *-------------------------------------------------------------------------*/
+typedef struct {
+  int32_t k;                 /* MEMBER */
+  int32_t nv;                /* variables of fcst / fcer, 1..32 */
+  int32_t nterm;             /* energy terms, 1..4 */
+  uint32_t var_mask;         /* variables (bit v) of THIS variable-localisation class; 0 = all */
+  const int32_t *term_of_var;   /* HOST [nv]: term of variable v, -1 = in no term */
+  int64_t npts;
+  const int64_t *obs_off;    /* dev [npts+1] (letkf_efso_points_dev; ignored by letkf_efso_columns_dev) */
+  const int32_t *obs_idx;    /* dev, rows of ensval */
+  const double *rdiag_l;     /* dev */
+  const double *rloc_l;      /* dev */
+  const double *ensval;      /* dev [nobs][kld]: Y^a */
+  int64_t kld;               /* >= k */
+  int64_t nobs;              /* rows of ensval and djdy */
+  const double *fcst;        /* dev */
+  int64_t sp, sm, sv;        /* strides of fcst in doubles */
+  const double *fcer;        /* dev */
+  int64_t fsp, fsv;          /* strides of fcer in doubles */
+  double *djdy;              /* dev [nobs][nterm] INOUT */
+  int64_t pair_bytes;        /* letkf_efso_points_dev: workspace budget of the pair contributions (8 nterm + 20 B per list
+                                entry), 0 = 8 GiB; lists beyond it run in chunks of points */
+} letkf_efso_args;
+
+/* On caller-built CSR lists (letkf_obs_search_dev / _columns_dev, or the host's).  Synchronises the stream once (the list
+ * length is read back). */
+int letkf_efso_points_dev(letkf_ctx *ctx, const letkf_efso_args *args);
+/* For the points p = ij + nij1*lev of a subdomain (npts = nij1*nlev): the column search (3a) and the EFSO passes by slabs
+ * of levels whose lists and pair workspace fit list_bytes (0 = 8 GiB; 20 + 8 nterm + 20 B per list entry; a single level
+ * that exceeds it still runs), as the list route of letkf_das_columns_dev.  With localisation advection the host passes the
+ * advected rig / rjg.  Synchronises the stream once besides the search's own. */
+int letkf_efso_columns_dev(letkf_ctx *ctx, const letkf_efso_args *args, const letkf_search_tables *tables, int64_t nij1,
+                           int32_t nlev, const double *rig, const double *rjg, const double *rlev, const double *rz,
+                           int64_t list_bytes);
+/* obsense(t, j) = djdy(t, j) * dep[j]; all dev, [nobs][nterm] as djdy.  obsense may be djdy. */
+int letkf_efso_obsense_dev(letkf_ctx *ctx, int32_t nterm, int64_t nobs, const double *djdy, const double *dep, double *obsense);
+
+/* Name(s) of the kernel(s) the context's last letkf_das_points*_dev / letkf_core_batch_dev / letkf_efso_*_dev call went
+ * through, as a NUL-terminated string (truncated to len): what bench.py reports as roofline.kernel. */
 int letkf_ctx_last_path(letkf_ctx *ctx, char *buf, int32_t len);
 /* Kernel timing helper for bench.py: average duration (ms) of the last
  * letkf_das_points_dev / letkf_core_batch_dev launches measured with HIP events on the

@@ -58,6 +58,15 @@ class DasArgs(C.Structure):
                 ("warm_run", C.c_int32), ("var_mask", C.c_uint32), ("infl_sv", C.c_int64)]
 
 
+class EfsoArgs(C.Structure):
+    _fields_ = [("k", C.c_int32), ("nv", C.c_int32), ("nterm", C.c_int32), ("var_mask", C.c_uint32),
+                ("term_of_var", C.c_void_p), ("npts", C.c_int64), ("obs_off", C.c_void_p), ("obs_idx", C.c_void_p),
+                ("rdiag_l", C.c_void_p), ("rloc_l", C.c_void_p), ("ensval", C.c_void_p), ("kld", C.c_int64),
+                ("nobs", C.c_int64), ("fcst", C.c_void_p), ("sp", C.c_int64), ("sm", C.c_int64), ("sv", C.c_int64),
+                ("fcer", C.c_void_p), ("fsp", C.c_int64), ("fsv", C.c_int64), ("djdy", C.c_void_p),
+                ("pair_bytes", C.c_int64)]
+
+
 class SearchTables(C.Structure):
     """letkf_search_tables (include/letkf_amd.h section 3)"""
     _fields_ = [("nctype", C.c_int32), ("ngroup", C.c_int32), ("criterion", C.c_int32), ("nlon", C.c_int32),
@@ -266,7 +275,7 @@ EXPORTS = ["letkf_amd_abi_version", "letkf_amd_last_error", "letkf_ctx_create", 
            "letkf_members_alltoall_dev",
            "letkf_obs_mesh_dims", "letkf_set_obs_local_dev", "letkf_set_obs_finish_dev", "letkf_set_obs_dev",
            "letkf_obs_table_info_get", "letkf_obs_table_search", "letkf_obs_table_set_varloc", "letkf_obs_table_download",
-           "letkf_obs_table_destroy",
+           "letkf_obs_table_destroy", "letkf_efso_points_dev", "letkf_efso_columns_dev", "letkf_efso_obsense_dev",
            "letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path", "letkf_sched_plan_check", "letkf_sched_plan_check_units"]
 
 _lib = None
@@ -455,6 +464,42 @@ class Context:
                       _ptr(rz), C.c_int32(1), None, _ptr(obs_off), _ptr(obs_idx), _ptr(rdiag), _ptr(rloc), _ptr(nobs_ctype),
                       _ptr(cutd_ctype)))    # (diagnostics with the fill pass: the count pass then needs no selection)
         return obs_off, obs_idx[:nnz], rdiag[:nnz], rloc[:nnz]
+
+    # ---- (10) EFSO: das_efso's loop on device tensors
+    def _efso_args(self, k, nv, term_of_var, nterm, npts, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp, fsv, djdy,
+                   var_mask, obs_off=None, obs_idx=None, rdiag_l=None, rloc_l=None, pair_bytes=0):
+        import numpy as np
+        tv = np.ascontiguousarray(np.asarray(term_of_var, dtype=np.int32))
+        a = EfsoArgs()
+        a.k, a.nv, a.nterm, a.var_mask = k, nv, nterm, int(var_mask)
+        a.term_of_var = tv.ctypes.data if tv.size else None
+        a.npts = npts
+        a.obs_off, a.obs_idx, a.rdiag_l, a.rloc_l = _ptr(obs_off), _ptr(obs_idx), _ptr(rdiag_l), _ptr(rloc_l)
+        a.ensval, a.kld, a.nobs = _ptr(ensval), kld, nobs
+        a.fcst, a.sp, a.sm, a.sv = _ptr(fcst), sp, sm, sv
+        a.fcer, a.fsp, a.fsv = _ptr(fcer), fsp, fsv
+        a.djdy, a.pair_bytes = _ptr(djdy), int(pair_bytes)
+        return a, tv
+
+    def efso_points(self, k, nv, term_of_var, nterm, obs_off, obs_idx, rdiag_l, rloc_l, ensval, kld, nobs, fcst, sp, sm, sv,
+                    fcer, fsp, fsv, djdy, var_mask=0, pair_bytes=0):
+        """letkf_efso_points_dev: djdy[j*nterm + t] += das_efso's contributions of the points of the CSR lists (INOUT)."""
+        a, keep = self._efso_args(k, nv, term_of_var, nterm, obs_off.numel() - 1, ensval, kld, nobs, fcst, sp, sm, sv, fcer,
+                                  fsp, fsv, djdy, var_mask, obs_off, obs_idx, rdiag_l, rloc_l, pair_bytes)
+        self._check(self._l.letkf_efso_points_dev(self._c, C.byref(a)))
+
+    def efso_columns(self, k, nv, term_of_var, nterm, tables, nij1, nlev, rig, rjg, rlev, rz, ensval, kld, nobs, fcst, sp, sm,
+                     sv, fcer, fsp, fsv, djdy, var_mask=0, list_bytes=0):
+        """letkf_efso_columns_dev: the column search and EFSO for the points p = ij + nij1*lev, by slabs of levels."""
+        a, keep = self._efso_args(k, nv, term_of_var, nterm, nij1 * nlev, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp, fsv,
+                                  djdy, var_mask)
+        self._check(self._l.letkf_efso_columns_dev(self._c, C.byref(a), C.byref(tables), C.c_int64(nij1), C.c_int32(nlev),
+                                                   _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), C.c_int64(list_bytes)))
+
+    def efso_obsense(self, nterm, djdy, dep, obsense):
+        """letkf_efso_obsense_dev: obsense[j*nterm + t] = djdy[j*nterm + t] * dep[j]."""
+        self._check(self._l.letkf_efso_obsense_dev(self._c, C.c_int32(nterm), C.c_int64(dep.numel()), _ptr(djdy), _ptr(dep),
+                                                   _ptr(obsense)))
 
     # ---- (5) set_letkf_obs on the device
     def obs_departure(self, params, elm, dat, err, ensval, kld, val, qc):

@@ -21,6 +21,16 @@
 #include "../../include/letkf_amd.h"
 #include "letkf_device.h"
 
+namespace letkf {
+
+// int32 counts -> int64 exclusive offsets (rocprim) with the scan's storage at temp; temp == nullptr: *temp_bytes = its size
+hipError_t count_scan(void* temp, size_t* temp_bytes, const int32_t* counts, int64_t* off, size_t n, hipStream_t st) {
+  auto in = rocprim::make_transform_iterator(counts, [] __device__(int32_t v) { return (int64_t)v; });
+  return rocprim::exclusive_scan(temp, *temp_bytes, in, off, (int64_t)0, n, rocprim::plus<int64_t>(), st);
+}
+
+}  // namespace letkf
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -74,6 +84,8 @@ struct letkf_ctx {
   int ring_batch_mb = 8192;   // LETKF_OPT_RING_BATCH_MB
   bool ring_release = false;  // LETKF_OPT_RING_RELEASE
   int limited_rings = 2;      // LETKF_OPT_LIMITED_RINGS: 0 never, 1 wherever eligible, 2 where a group's survivors overflow the column kernel's buffer
+  char* efso_ws = nullptr;    // EFSO: the pair contributions of a slab, their sort by observation row and the row offsets
+  size_t efso_ws_bytes = 0;
   char* staged_ws = nullptr;  // staged path: per-point slabs of a batch + meta / info words
   size_t staged_ws_bytes = 0;
   std::string last_path;      // kernels the last loop-body / letkf_core launch went through (bench.py reports it)
@@ -102,11 +114,7 @@ int grow(letkf_ctx* c, char** buf, size_t* have, size_t need, bool slack = true)
   return LETKF_OK;
 }
 
-// int32 counts -> int64 exclusive offsets (rocprim) with the scan's storage at temp; temp == nullptr: *temp_bytes = its size
-hipError_t count_scan(void* temp, size_t* temp_bytes, const int32_t* counts, int64_t* off, size_t n, hipStream_t st) {
-  auto in = rocprim::make_transform_iterator(counts, [] __device__(int32_t v) { return (int64_t)v; });
-  return rocprim::exclusive_scan(temp, *temp_bytes, in, off, (int64_t)0, n, rocprim::plus<int64_t>(), st);
-}
+using letkf::count_scan;
 
 // Measurement-only knobs exist in the PROF twin of the library (make PROF=1) and nowhere else: the production build
 // reads no environment variable that could change a result.
@@ -386,12 +394,90 @@ int launch(letkf_ctx* c, letkf::PointArgs& a, int warm_run = 0, long warm_stride
   return LETKF_OK;
 }
 
+// Inside letkf_das_columns_dev / letkf_efso_columns_dev: the column searches of one entry (a count pass, a fill pass per
+// slab) share the ring-ordered survivors of the dense limited case; the guard drops them when the entry returns.
+struct RingKeep {
+  letkf_ctx* c;
+  explicit RingKeep(letkf_ctx* c_) : c(c_) { c->ring_keep = true; c->ring_ready = false; c->ring_no_n = -1; }
+  ~RingKeep() {
+    c->ring_keep = false;
+    c->ring_ready = false;
+    c->ring_no_n = -1;
+    // the kept survivors can be a large part of the device (configs[3] with two limited types: 128 GiB).  By default the buffer
+    // stays with the context for the next analysis (allocating and freeing 64 GB per call cost the MEMBER = 100 tile 1.7 s of a
+    // 4 s analysis); LETKF_OPT_RING_RELEASE = 1 hands back whatever exceeds the batch budget when the entry returns, for a host
+    // model that needs the memory between analyses (hipFree waits for the work that still reads the buffer)
+    if (c->ring_release && c->ring_ws && c->ring_ws_bytes > ((size_t)c->ring_batch_mb << 20) + ((size_t)c->ring_batch_mb << 18) + 8192) {
+      (void)hipFree(c->ring_ws);
+      c->ring_ws = nullptr;
+      c->ring_ws_bytes = 0;
+    }
+  }
+};
+
 int check_ctx(letkf_ctx* c) {
   if (!c || c->device < 0) return fail(LETKF_E_NO_DEVICE, "context is not bound to a device");
   HIP_TRY(hipSetDevice(c->device));
   return LETKF_OK;
 }
 
+
+// ---- EFSO (letkf_efso.hip).  Workspace per list entry besides the lists: nterm contributions, the sort's keys (in and
+// out) and entry numbers, and about as much again of sort scratch.
+int64_t efso_entry_bytes(int nterm) { return 8 * (int64_t)nterm + 20; }
+constexpr int64_t kEfsoMaxSlab = (int64_t)1 << 31;   // entry numbers of a slab are 32-bit in the sort
+
+int efso_check(letkf_ctx* c, const letkf_efso_args* g, bool lists, letkf::EfsoArgs* a) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!g) return fail(LETKF_E_INVALID, "args is NULL");
+  if (g->nterm < 1 || g->nterm > 4) return fail(LETKF_E_INVALID, "nterm must be 1..4");
+  if (g->k < 2) return fail(LETKF_E_INVALID, "ensemble size must be >= 2");
+  if (g->nv < 1 || g->nv > 32) return fail(LETKF_E_INVALID, "nv must be 1..32");
+  if (g->npts < 0 || g->nobs < 0) return fail(LETKF_E_INVALID, "negative npts / nobs");
+  if (g->nobs > 0x7fffffff) return fail(LETKF_E_INVALID, "more than 2^31 observation rows");
+  if (g->kld < g->k) return fail(LETKF_E_INVALID, "kld must be >= k");
+  if (!g->term_of_var || !g->ensval || !g->fcst || !g->fcer || !g->djdy)
+    return fail(LETKF_E_INVALID, "a required pointer is NULL (term_of_var, ensval, fcst, fcer, djdy)");
+  if (lists && (!g->obs_off || !g->obs_idx || !g->rdiag_l || !g->rloc_l))
+    return fail(LETKF_E_INVALID, "a list pointer is NULL (obs_off, obs_idx, rdiag_l, rloc_l)");
+  if (letkf::efso_pair_lds(g->k, g->nterm) > c->lds_max) return fail(LETKF_E_INVALID, "ensemble size too large for the LDS of w_p");
+  *a = letkf::EfsoArgs{};
+  a->k = g->k;
+  a->nv = g->nv;
+  a->nterm = g->nterm;
+  for (int v = 0; v < 32; ++v) a->term[v] = -1;
+  for (int v = 0; v < g->nv; ++v) {
+    const int t = g->term_of_var[v];
+    if (t < -1 || t >= g->nterm) return fail(LETKF_E_INVALID, "term_of_var values must be -1..nterm-1");
+    a->term[v] = (signed char)((g->var_mask == 0 || ((g->var_mask >> v) & 1u)) ? t : -1);
+  }
+  a->nobs = g->nobs;
+  a->kld = g->kld;
+  a->obs_off = reinterpret_cast<const long*>(g->obs_off);
+  a->obs_idx = g->obs_idx;
+  a->rdiag_l = g->rdiag_l;
+  a->rloc_l = g->rloc_l;
+  a->ensval = g->ensval;
+  a->fcst = g->fcst;
+  a->sp = g->sp;
+  a->sm = g->sm;
+  a->sv = g->sv;
+  a->fcer = g->fcer;
+  a->fsp = g->fsp;
+  a->fsv = g->fsv;
+  a->djdy = g->djdy;
+  return LETKF_OK;
+}
+
+// One slab: points [0, npts) of a, entries [e0, e1) of its lists
+int efso_run_slab(letkf_ctx* c, const letkf::EfsoArgs& a, int64_t npts, int64_t e0, int64_t e1) {
+  if (npts <= 0 || e1 <= e0 || a.nobs == 0) return LETKF_OK;
+  letkf::EfsoWs ws;
+  HIP_TRY(letkf::efso_ws_layout(e1 - e0, a.nobs, a.nterm, c->stream, &ws));
+  if (int rc = grow(c, &c->efso_ws, &c->efso_ws_bytes, ws.total)) return rc;
+  HIP_TRY(letkf::efso_slab(a, npts, e0, e1, c->efso_ws, ws, c->num_cu, c->stream));
+  return LETKF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -451,6 +537,7 @@ int letkf_ctx_destroy(letkf_ctx* c) {
     if (c->slot_ws) (void)hipFree(c->slot_ws);
     if (c->ring_ws) (void)hipFree(c->ring_ws);
     if (c->ring_aux) (void)hipFree(c->ring_aux);
+    if (c->efso_ws) (void)hipFree(c->efso_ws);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   }
   delete c;
@@ -780,24 +867,7 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     }
   }
   // (the searches below -- one count pass, a fill pass per slab -- share the ring-ordered survivors of the dense limited case)
-  struct RingKeep {
-    letkf_ctx* c;
-    explicit RingKeep(letkf_ctx* c_) : c(c_) { c->ring_keep = true; c->ring_ready = false; c->ring_no_n = -1; }
-    ~RingKeep() {
-      c->ring_keep = false;
-      c->ring_ready = false;
-      c->ring_no_n = -1;
-      // the kept survivors can be a large part of the device (configs[3] with two limited types: 128 GiB).  By default the buffer
-      // stays with the context for the next analysis (allocating and freeing 64 GB per call cost the MEMBER = 100 tile 1.7 s of a
-      // 4 s analysis); LETKF_OPT_RING_RELEASE = 1 hands back whatever exceeds the batch budget when the entry returns, for a host
-      // model that needs the memory between analyses (hipFree waits for the work that still reads the buffer)
-      if (c->ring_release && c->ring_ws && c->ring_ws_bytes > ((size_t)c->ring_batch_mb << 20) + ((size_t)c->ring_batch_mb << 18) + 8192) {
-        (void)hipFree(c->ring_ws);
-        c->ring_ws = nullptr;
-        c->ring_ws_bytes = 0;
-      }
-    }
-  } ring_keep_guard(c);
+  RingKeep ring_keep_guard(c);
   // workspace: counts [npts] int32 | obs_off [npts + 1] int64 | scan scratch
   size_t scan_bytes = 0;
   HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, (size_t)npts + 1, c->stream));
@@ -859,6 +929,105 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     if (int rc = das_points_impl(c, &a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
     l0 = l1;
   }
+  return LETKF_OK;
+}
+
+// EFSO, das_efso's loop (scale/letkf/letkf_tools.f90:1158-1302) on caller-built lists: points in chunks whose pair
+// workspace fits pair_bytes (the offsets are read back only when the lists do not fit at once)
+int letkf_efso_points_dev(letkf_ctx* c, const letkf_efso_args* g) {
+  letkf::EfsoArgs a;
+  if (int rc = efso_check(c, g, true, &a)) return rc;
+  c->last_path = letkf::efso_path_name(g->nterm);
+  if (g->npts == 0 || g->nobs == 0) return LETKF_OK;
+  const int64_t budget = g->pair_bytes > 0 ? g->pair_bytes : ((int64_t)8 << 30);
+  const int64_t cap = std::max<int64_t>(1, std::min(budget / efso_entry_bytes(g->nterm), kEfsoMaxSlab));
+  int64_t ends[2];
+  HIP_TRY(hipMemcpyAsync(&ends[0], g->obs_off, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&ends[1], g->obs_off + g->npts, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (ends[1] - ends[0] <= cap) return efso_run_slab(c, a, g->npts, ends[0], ends[1]);
+  std::vector<int64_t> off((size_t)g->npts + 1);
+  HIP_TRY(hipMemcpyAsync(off.data(), g->obs_off, off.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int64_t p0 = 0; p0 < g->npts;) {
+    int64_t p1 = p0 + 1;   // at least one point, however long its list
+    while (p1 < g->npts && off[p1 + 1] - off[p0] <= cap) ++p1;
+    if (off[p1] - off[p0] > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a point with more than 2^31 local observations");
+    letkf::EfsoArgs s = a;
+    s.obs_off = a.obs_off + p0;
+    s.fcst = a.fcst + p0 * a.sp;
+    s.fcer = a.fcer + p0 * a.fsp;
+    if (int rc = efso_run_slab(c, s, p1 - p0, off[p0], off[p1])) return rc;
+    p0 = p1;
+  }
+  return LETKF_OK;
+}
+
+// EFSO for a whole subdomain: the column search (3a) by slabs of levels whose lists and pair workspace fit list_bytes,
+// then the EFSO passes on each slab -- the list route of letkf_das_columns_dev
+int letkf_efso_columns_dev(letkf_ctx* c, const letkf_efso_args* g, const letkf_search_tables* t, int64_t nij1, int32_t nlev,
+                           const double* rig, const double* rjg, const double* rlev, const double* rz, int64_t list_bytes) {
+  letkf::EfsoArgs a;
+  if (int rc = efso_check(c, g, false, &a)) return rc;
+  if (!t) return fail(LETKF_E_INVALID, "tables is NULL");
+  if (nij1 < 1 || nlev < 1 || g->npts != nij1 * (int64_t)nlev) return fail(LETKF_E_INVALID, "npts must be nij1 * nlev");
+  if (!rig || !rjg || !rlev || !rz) return fail(LETKF_E_INVALID, "a point coordinate array is NULL");
+  c->last_path = std::string("search_columns + ") + letkf::efso_path_name(g->nterm);
+  if (list_bytes <= 0) list_bytes = (int64_t)8 << 30;
+  const int64_t npts = g->npts, per_entry = 20 + efso_entry_bytes(g->nterm);
+  RingKeep ring_keep_guard(c);
+  // workspace: counts [npts] int32 | obs_off [npts + 1] int64 | scan scratch
+  size_t scan_bytes = 0;
+  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, (size_t)npts + 1, c->stream));
+  const size_t off_off = ((size_t)(npts + 1) * 4 + 255) & ~(size_t)255;
+  const size_t off_scan = off_off + (((size_t)(npts + 1) * 8 + 255) & ~(size_t)255);
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
+  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch);
+  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
+  HIP_TRY(hipMemsetAsync(counts + npts, 0, 4, c->stream));
+  if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, counts, nullptr, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr))
+    return rc;
+  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, (size_t)npts + 1, c->stream));
+  std::vector<int64_t> lev_off((size_t)nlev + 1);
+  HIP_TRY(hipMemcpy2DAsync(lev_off.data(), 8, off, (size_t)nij1 * 8, 8, (size_t)nlev + 1, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int l0 = 0;
+  while (l0 < nlev) {
+    int l1 = l0 + 1;
+    while (l1 < nlev && (lev_off[l1 + 1] - lev_off[l0]) * per_entry <= list_bytes && lev_off[l1 + 1] - lev_off[l0] <= kEfsoMaxSlab) ++l1;
+    const int64_t nnz = lev_off[l1] - lev_off[l0], p0 = (int64_t)l0 * nij1, np = (int64_t)(l1 - l0) * nij1;
+    if (nnz > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a level with more than 2^31 local observations");
+    const size_t n1 = (size_t)(nnz > 0 ? nnz : 1);
+    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
+    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, o_rl + n1 * 8 + 256)) return rc;
+    // list entry e of the slab's point p at base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
+    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - lev_off[l0];
+    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - lev_off[l0];
+    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - lev_off[l0];
+    if (int rc = letkf_obs_search_columns_dev(c, t, nij1, l1 - l0, rig, rjg, rlev + p0, rz + p0, 1, nullptr, off + p0, idx, rd, rl,
+                                              nullptr, nullptr))
+      return rc;
+    letkf::EfsoArgs s = a;
+    s.obs_off = reinterpret_cast<const long*>(off + p0);
+    s.obs_idx = idx;
+    s.rdiag_l = rd;
+    s.rloc_l = rl;
+    s.fcst = a.fcst + p0 * a.sp;
+    s.fcer = a.fcer + p0 * a.fsp;
+    if (int rc = efso_run_slab(c, s, np, lev_off[l0], lev_off[l1])) return rc;
+    l0 = l1;
+  }
+  return LETKF_OK;
+}
+
+// obsense(t, j) = djdy(t, j) * dep(j), das_efso :1283-1290
+int letkf_efso_obsense_dev(letkf_ctx* c, int32_t nterm, int64_t nobs, const double* djdy, const double* dep, double* obsense) {
+  if (int rc = check_ctx(c)) return rc;
+  if (nterm < 1 || nterm > 4) return fail(LETKF_E_INVALID, "nterm must be 1..4");
+  if (nobs < 0) return fail(LETKF_E_INVALID, "negative nobs");
+  if (nobs > 0 && (!djdy || !dep || !obsense)) return fail(LETKF_E_INVALID, "a required pointer is NULL (djdy, dep, obsense)");
+  HIP_TRY(letkf::launch_efso_obsense(nterm, nobs, djdy, dep, obsense, c->stream));
   return LETKF_OK;
 }
 

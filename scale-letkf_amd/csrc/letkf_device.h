@@ -295,4 +295,33 @@ void obs_table_destroy(letkf_obs_table* t);
 int obs_table_download(hipStream_t st, const letkf_obs_table* t, double* ensval, double* val, int* qc, double* ob[5],
                        int* ac_ext, std::string* msg);
 
+// int32 counts -> int64 exclusive offsets (rocprim, letkf_api.hip); temp == nullptr: *temp_bytes = the scratch it needs
+hipError_t count_scan(void* temp, size_t* temp_bytes, const int32_t* counts, int64_t* off, size_t n, hipStream_t st);
+
+// EFSO (letkf_efso.hip): das_efso's loop, scale/letkf/letkf_tools.f90:1158-1302, on the local lists
+struct EfsoArgs {
+  int k, nv, nterm;
+  signed char term[32];      // per variable: energy term 0..nterm-1, or -1 (no term / outside the call's var_mask)
+  long nobs, kld;
+  const long* obs_off;       // [npts + 1] of the slab's points (global entry numbers)
+  const int* obs_idx;
+  const double* rdiag_l;
+  const double* rloc_l;
+  const double* ensval;      // Y^a rows [nobs][kld]
+  const double* fcst;        // (p, m, v) at p*sp + m*sm + v*sv
+  long sp, sm, sv;
+  const double* fcer;        // (p, v) at p*fsp + v*fsv
+  long fsp, fsv;
+  double* djdy;              // (t, j) at j*nterm + t, INOUT
+};
+struct EfsoWs {
+  size_t o_contrib, o_keys_in, o_keys, o_perm, o_cnt, o_start, o_sort, o_scan, sort_bytes, scan_bytes, total;
+};
+size_t efso_pair_lds(int k, int nterm);
+hipError_t efso_ws_layout(long n, long nobs, int nterm, hipStream_t st, EfsoWs* ws);
+hipError_t efso_slab(const EfsoArgs& a, long npts, long e_base, long e_end, char* base, const EfsoWs& ws, int num_cu,
+                     hipStream_t st);
+hipError_t launch_efso_obsense(int nterm, long nobs, const double* djdy, const double* dep, double* obsense, hipStream_t st);
+const char* efso_path_name(int nterm);
+
 }  // namespace letkf

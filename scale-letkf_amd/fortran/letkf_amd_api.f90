@@ -26,6 +26,22 @@ MODULE letkf_amd_api
     INTEGER(c_int64_t) :: infl_sv
   END TYPE letkf_das_args
 
+  ! include/letkf_amd.h section 10: EFSO (das_efso, scale/letkf/letkf_tools.f90:1158-1302)
+  TYPE, BIND(C) :: letkf_efso_args
+    INTEGER(c_int32_t) :: k, nv, nterm
+    INTEGER(c_int32_t) :: var_mask
+    TYPE(c_ptr)        :: term_of_var
+    INTEGER(c_int64_t) :: npts
+    TYPE(c_ptr)        :: obs_off, obs_idx, rdiag_l, rloc_l, ensval
+    INTEGER(c_int64_t) :: kld, nobs
+    TYPE(c_ptr)        :: fcst
+    INTEGER(c_int64_t) :: sp, sm, sv
+    TYPE(c_ptr)        :: fcer
+    INTEGER(c_int64_t) :: fsp, fsv
+    TYPE(c_ptr)        :: djdy
+    INTEGER(c_int64_t) :: pair_bytes
+  END TYPE letkf_efso_args
+
   ! include/letkf_amd.h section 7
   TYPE, BIND(C) :: letkf_beta_params
     INTEGER(c_int32_t) :: radar_only, ihalo, jhalo, nlong, nlatg, reserved0
@@ -294,6 +310,30 @@ MODULE letkf_amd_api
       TYPE(letkf_search_tables), INTENT(IN) :: tables
       INTEGER(c_int64_t), VALUE :: nij1, list_bytes
       INTEGER(c_int32_t), VALUE :: nlev
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    ! ---- section 10: EFSO on the local lists (das_efso), by the column search, and obsense = djdy * dep
+    FUNCTION letkf_efso_points_dev(ctx, args) BIND(C, name='letkf_efso_points_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, letkf_efso_args
+      TYPE(c_ptr), VALUE :: ctx
+      TYPE(letkf_efso_args), INTENT(IN) :: args
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_efso_columns_dev(ctx, args, tables, nij1, nlev, rig, rjg, rlev, rz, list_bytes) &
+        BIND(C, name='letkf_efso_columns_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int32_t, c_int64_t, letkf_efso_args, letkf_search_tables
+      TYPE(c_ptr), VALUE :: ctx, rig, rjg, rlev, rz
+      TYPE(letkf_efso_args), INTENT(IN) :: args
+      TYPE(letkf_search_tables), INTENT(IN) :: tables
+      INTEGER(c_int64_t), VALUE :: nij1, list_bytes
+      INTEGER(c_int32_t), VALUE :: nlev
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_efso_obsense_dev(ctx, nterm, nobs, djdy, dep, obsense) BIND(C, name='letkf_efso_obsense_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int32_t, c_int64_t
+      TYPE(c_ptr), VALUE :: ctx, djdy, dep, obsense
+      INTEGER(c_int32_t), VALUE :: nterm
+      INTEGER(c_int64_t), VALUE :: nobs
       INTEGER(c_int) :: rc
     END FUNCTION
     ! ---- section 4: the steps either side of the loop (row f3)

@@ -14,6 +14,8 @@
 !   :313-527  main loop: obs_local + letkf_core + relaxation + transform, per variable-localisation class
 !                                                      letkf_das_columns_dev (column search + loop body by slabs of levels)
 !   letkf.f90:207  ensmean_grd on the analysis          letkf_ens_mean_dev
+! das_efso_amd is the same for das_efso (:1158-1302, commented out in the reference): obs_local and the EFSO contraction
+! for every point (letkf_efso_columns_dev), then obsense = djdy * dep (letkf_efso_obsense_dev).
 ! gues3d / anal3d keep the reference's shape and meaning: gues3d(nij1,nlev,nens,nv3d) INOUT (members 1..MEMBER come back
 ! as perturbations, slot mmean = MEMBER+1 holds the mean, mmdet = MEMBER+2 the deterministic member), anal3d OUT.
 ! 2-D variables: the reference is built with nv2d = 0 (common_scale.f90:53); they are not arguments here (INTEGRATION.md
@@ -24,7 +26,7 @@ MODULE letkf_tools_amd
   USE letkf_amd_api
   IMPLICIT NONE
   PRIVATE
-  PUBLIC :: das_letkf_amd, letkf_das_nml, letkf_obs_tables, letkf_obs_tables_dev, letkf_vmode, letkf_obs_tables_dev_free
+  PUBLIC :: das_letkf_amd, das_efso_amd, letkf_das_nml, letkf_obs_tables, letkf_obs_tables_dev, letkf_vmode, letkf_obs_tables_dev_free
 
   INTEGER, PARAMETER :: r_size = c_double
   INTEGER, PARAMETER :: nlt = 9               ! columns of var_local: VAR_LOCAL_UV .. VAR_LOCAL_H08 (letkf_tools.f90:130-138)
@@ -341,6 +343,78 @@ CONTAINS
     IF (own) CALL free_all((/d_ens, d_val, d_hl, d_vl, d_gi, d_gj, d_si, d_sj, d_ei, d_ej, d_aco, d_ace, d_ri, d_rj, d_lev, &
                              d_dat, d_err/))
   END SUBROUTINE das_body
+
+  ! das_efso (scale/letkf/letkf_tools.f90:1158-1302) on the device for one variable-localisation class: tables = the
+  ! search tables with DEVICE pointers (letkf_obs_table_search of set_letkf_obs_amd's table, varloc of the class set);
+  ! fcst3d = C^1/2 X^f_t, fcer3d = C^1/2 (e^f + e^g) / (2 (K-1)) (efso.f90:100-120, lnorm: the host's share);
+  ! term_of_var(v) = energy term 1..nterm of variable v, 0 = none (das_efso's iterm); ya(kld, nobs) = H X^a (member
+  ! perturbations in observation space, obsda_sort order), dep(nobs) = y - H(xmean^b).  djdy(nterm, nobs) INOUT
+  ! accumulates over the calls of several classes (var_mask: bit v-1 for variable v, 0 = all); obsense = djdy * dep.
+  SUBROUTINE das_efso_amd(ctx, tables, nij1, nlev, member, nv3d, rig1, rjg1, rlev, hgt1, fcst3d, fcer3d, nterm, term_of_var, &
+                          kld, nobs, ya, dep, djdy, obsense, var_mask)
+    TYPE(c_ptr), INTENT(IN) :: ctx
+    TYPE(letkf_search_tables), INTENT(IN) :: tables
+    INTEGER, INTENT(IN) :: nij1, nlev, member, nv3d, nterm, kld, nobs
+    REAL(r_size), INTENT(IN), TARGET :: rig1(nij1), rjg1(nij1), rlev(nij1, nlev), hgt1(nij1, nlev)
+    REAL(r_size), INTENT(IN), TARGET :: fcst3d(nij1, nlev, member, nv3d), fcer3d(nij1, nlev, nv3d)
+    INTEGER, INTENT(IN) :: term_of_var(nv3d)
+    REAL(r_size), INTENT(IN), TARGET :: ya(kld, nobs), dep(nobs)
+    REAL(r_size), INTENT(INOUT), TARGET :: djdy(nterm, nobs)
+    REAL(r_size), INTENT(OUT), TARGET :: obsense(nterm, nobs)
+    INTEGER, INTENT(IN), OPTIONAL :: var_mask
+    INTEGER(c_int32_t), TARGET :: tv(nv3d)
+    TYPE(letkf_efso_args) :: a
+    TYPE(c_ptr) :: d_rig, d_rjg, d_rlev, d_rz, d_fcst, d_fcer, d_ya, d_dep, d_djdy, d_obsense
+    INTEGER(c_int64_t) :: npts
+    INTEGER(c_size_t) :: nb_dj
+
+    npts = INT(nij1, c_int64_t)*nlev
+    nb_dj = 8_c_size_t*nterm*nobs
+    tv = INT(term_of_var, c_int32_t) - 1
+    d_rig = up(c_loc(rig1), 8_c_size_t*nij1)
+    d_rjg = up(c_loc(rjg1), 8_c_size_t*nij1)
+    d_rlev = up(c_loc(rlev), 8_c_size_t*npts)
+    d_rz = up(c_loc(hgt1), 8_c_size_t*npts)
+    d_fcst = up(c_loc(fcst3d), 8_c_size_t*npts*member*nv3d)
+    d_fcer = up(c_loc(fcer3d), 8_c_size_t*npts*nv3d)
+    d_ya = up(c_loc(ya), 8_c_size_t*kld*nobs)
+    d_dep = up(c_loc(dep), 8_c_size_t*nobs)
+    d_djdy = up(c_loc(djdy), nb_dj)
+    CALL chk(hipMalloc(d_obsense, MAX(nb_dj, 8_c_size_t)), 'hipMalloc obsense')
+    a%k = member
+    a%nv = nv3d
+    a%nterm = nterm
+    a%var_mask = 0
+    IF (PRESENT(var_mask)) a%var_mask = INT(var_mask, c_int32_t)
+    a%term_of_var = c_loc(tv)
+    a%npts = npts
+    a%obs_off = c_null_ptr
+    a%obs_idx = c_null_ptr
+    a%rdiag_l = c_null_ptr
+    a%rloc_l = c_null_ptr
+    a%ensval = d_ya
+    a%kld = kld
+    a%nobs = nobs
+    a%fcst = d_fcst
+    a%sp = 1
+    a%sm = npts
+    a%sv = npts*member
+    a%fcer = d_fcer
+    a%fsp = 1
+    a%fsv = npts
+    a%djdy = d_djdy
+    a%pair_bytes = 0
+    CALL chk(letkf_efso_columns_dev(ctx, a, tables, INT(nij1, c_int64_t), INT(nlev, c_int32_t), d_rig, d_rjg, d_rlev, d_rz, &
+                                    0_c_int64_t), 'letkf_efso_columns_dev')
+    CALL chk(letkf_efso_obsense_dev(ctx, INT(nterm, c_int32_t), INT(nobs, c_int64_t), d_djdy, d_dep, d_obsense), &
+             'letkf_efso_obsense_dev')
+    CALL chk(letkf_ctx_synchronize(ctx), 'letkf_ctx_synchronize')
+    IF (nb_dj > 0) THEN
+      CALL chk(hipMemcpy(c_loc(djdy), d_djdy, nb_dj, hipMemcpyDeviceToHost), 'download djdy')
+      CALL chk(hipMemcpy(c_loc(obsense), d_obsense, nb_dj, hipMemcpyDeviceToHost), 'download obsense')
+    END IF
+    CALL free_all([d_rig, d_rjg, d_rlev, d_rz, d_fcst, d_fcer, d_ya, d_dep, d_djdy, d_obsense])
+  END SUBROUTINE das_efso_amd
 
   ! device pointer + an offset in doubles
   FUNCTION off_ptr(base, ndbl) RESULT(p)
