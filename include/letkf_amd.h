@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LETKF_AMD_ABI_VERSION 9
+#define LETKF_AMD_ABI_VERSION 10
 
 /* host-side errors (function return values) */
 #define LETKF_OK 0
@@ -785,6 +785,87 @@ int letkf_efso_columns_dev(letkf_ctx *ctx, const letkf_efso_args *args, const le
                            int64_t list_bytes);
 /* obsense(t, j) = djdy(t, j) * dep[j]; all dev, [nobs][nterm] as djdy.  obsense may be djdy. */
 int letkf_efso_obsense_dev(letkf_ctx *ctx, int32_t nterm, int64_t nobs, const double *djdy, const double *dep, double *obsense);
+
+/*---------------------------------------------------------------------------
+ * (11, ABI 10) The analysis ensemble in observation space: das_letkf_obs, scale/letkf/letkf_tools.f90:933-1156
+ *     (commented out in the reference).  The LETKF runs at every target observation's own location, and the analysis
+ *     of the target is  obsanal(m) = H xbar^b + Y^b (wbar + T)(:, m)  -- the reference's obs-space analysis, NOT H(x^a)
+ *     of the analysed grid (the two differ for a nonlinear H and through localisation).  It is the Y^a that section (10)
+ *     contracts: ya_table is set_efso_obs's obshdxf (letkf_obs.f90:1503ff, commented out there).
+ *     One call handles the targets regarded as ONE grid variable tvar (letkf_obs_target_var below).  Target t is row
+ *     j = tgt_row[t] of obsda_sort, and its analysis is what the loop body (section 2) gives at a point with
+ *       coordinates   ri = ob_ri[j], rj = ob_rj[j]; the vertical one by the target ctype's vmode: 0 rlev = ob_lev[j]
+ *                     (H08 rows too), 1 rz = ob_lev[j], 2 rlev = ob_dat[j] (das_letkf_obs: rlev = obsdat), 3 rlev =
+ *                     rain_base.  The other coordinate is read from rlev_tgt / rz_tgt where the tables hold a ctype that
+ *                     uses it (the host derives it with its phys2ijk / phys2ijkz); the target's ctype is the ctype block of
+ *                     ac_ext that holds row j.
+ *       local list    obs_local at those coordinates with the tables' CURRENT varloc, which the caller sets for tvar as for
+ *                     a variable class (var_local(tvar, uid_obs_varlocal(elm)); all ones for tvar = -1, the reference's
+ *                     nvar = 0); every selection mode, MAX_NOBS_PER_GRID included
+ *       background    members ensval[j*kld + m] (m < k), mean ob_dat[j] - dep[j], with det_run the deterministic member
+ *                     ob_dat[j] - ensval[j*kld + k]
+ *       inflation     infl[t], or infl_mul where infl is NULL; read only (the adaptive update is not run, nor is it in
+ *                     das_letkf_obs)
+ *       relaxation    RTPP / RTPS / RELAX_TO_INFLATED_PRIOR on the target's own obs-space spread; beta[t] (NULL = 1),
+ *                     beta = 0 returns the background; n = 0 gives T = sqrt(rho) I
+ *       q rules       Q_UPDATE_TOP when iv_q_first <= tvar <= iv_q_last (a target with rlev < q_update_top keeps its
+ *                     background), Q_SPRD_MAX when tvar == iv_q_first
+ *     Outputs per target t (all dev; each but ya may be NULL):
+ *       ya        [ntgt][lda]  the k analysis members as full values (obsanalNNN); column k the deterministic member with
+ *                              det_run
+ *       ya_mean   [ntgt]       their mean (obsanal_me)
+ *       ya_table  [nobs][kld]  row tgt_row[t] gets ya - ya_mean in columns 0..k-1 (and with det_run the analysis departure
+ *                              ob_dat - ya(k) in column k, the table's det convention); other rows are not touched.  This is
+ *                              the ensval letkf_efso_*_dev reads
+ *       dep_a     [ntgt]       ob_dat - ya_mean, the analysis departure (O - A; letkf_monit_dep_dev summarises it)
+ *       nobs_out  [ntgt]       local observation count (0 where beta = 0, as letkf_das_columns_dev reports it)
+ *       status    [ntgt]       the loop body's status
+ *     Duplicate targets are allowed: they give identical rows.
+ *     Route: the search (3) on the targets' coordinates (count, device scan, fill), then the loop body through the staged
+ *     family (two variables, section 2's route choice unchanged), in chunks of targets whose lists fit list_bytes of
+ *     workspace (0 = 8 GiB, 20 B per list entry; one target always fits).  The results do not depend on the chunks, bit for
+ *     bit.  Synchronisations: one read-back of the list offsets and the argument flags after the count pass, besides the
+ *     search's own (none when tables->limit_hint is set); none per chunk.
+ *     LETKF_E_INVALID: k < 2; ntgt < 0; lda < k (+1 with det_run); kld < k (+1 with det_run); nobs < 1 with targets; a
+ *     tgt_row entry outside [0, nobs) (NULL: target t is row t, so ntgt <= nobs); a row in no ctype block of the tables; a
+ *     required pointer NULL (args, tables, ensval, dep, ya); a vertical coordinate the tables need that rlev_tgt / rz_tgt does
+ *     not give (also rlev where Q_UPDATE_TOP applies).  Nothing is written then except workspace.
+ *-------------------------------------------------------------------------*/
+typedef struct {
+  int32_t k;                 /* MEMBER */
+  int32_t det_run;           /* DET_RUN */
+  int32_t tvar;              /* 0-based grid variable the targets are regarded as, -1 = none (letkf_obs_target_var) */
+  int32_t relax_to_inflated_prior; /* RELAX_TO_INFLATED_PRIOR */
+  int32_t iv_q_first, iv_q_last;   /* 0-based inclusive iv3d_q .. iv3d_qg */
+  double relax_alpha;        /* RELAX_ALPHA (RTPP), 0 = off */
+  double relax_alpha_spread; /* RELAX_ALPHA_SPREAD (RTPS), 0 = off; RTPP wins when both set */
+  double q_update_top;       /* Q_UPDATE_TOP, <= 0 = off */
+  double q_sprd_max;         /* Q_SPRD_MAX, <= 0 = off */
+  int64_t ntgt;
+  const int32_t *tgt_row;    /* dev [ntgt]: 0-based rows of obsda_sort, or NULL (target t = row t) */
+  const double *ensval;      /* dev [nobs][kld]: obsda_sort%ensval (perturbations; column k the det departure) */
+  int64_t kld;               /* >= k (+1 with det_run) */
+  const double *dep;         /* dev [nobs]: obsda_sort%val */
+  int64_t nobs;              /* rows of the table */
+  const double *rlev_tgt;    /* dev [ntgt] or NULL: pressure of targets whose own coordinate is a height (vmode 1) */
+  const double *rz_tgt;      /* dev [ntgt] or NULL: height of targets whose own coordinate is a pressure (vmode 0, 2, 3) */
+  const double *beta;        /* dev [ntgt] or NULL (= 1) */
+  const double *infl;        /* dev [ntgt] or NULL (= infl_mul) */
+  double infl_mul;           /* COV_INFL_MUL where infl is NULL */
+  double *ya;                /* dev [ntgt][lda] */
+  int64_t lda;               /* >= k (+1 with det_run) */
+  double *ya_mean;           /* dev [ntgt] or NULL */
+  double *ya_table;          /* dev [nobs][kld] or NULL */
+  double *dep_a;             /* dev [ntgt] or NULL */
+  int32_t *nobs_out;         /* dev [ntgt] or NULL */
+  int32_t *status;           /* dev [ntgt] or NULL */
+  int64_t list_bytes;        /* list workspace per chunk of targets, 0 = 8 GiB */
+} letkf_das_obs_args;
+int letkf_das_obs_dev(letkf_ctx *ctx, const letkf_das_obs_args *args, const letkf_search_tables *tables);
+/* das_letkf_obs's SELECT CASE in SCALE's 0-based variable numbers (common_scale.f90:41-51, common_obs_scale.f90:48-68):
+ * u -> 0 (U), v -> 1 (V), t and tv -> 3 (T), q and rh -> 5 (QV), every other element (ps, radar, H08, TC, ...) -> -1.
+ * (SCALE has nv2d = 0: ps has no 2-D variable to map to.)  Host only. */
+int letkf_obs_target_var(int32_t elm);
 
 /* Name(s) of the kernel(s) the context's last letkf_das_points*_dev / letkf_core_batch_dev / letkf_efso_*_dev call went
  * through, as a NUL-terminated string (truncated to len): what bench.py reports as roofline.kernel. */

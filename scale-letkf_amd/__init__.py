@@ -67,6 +67,18 @@ class EfsoArgs(C.Structure):
                 ("pair_bytes", C.c_int64)]
 
 
+class DasObsArgs(C.Structure):
+    """letkf_das_obs_args (include/letkf_amd.h section 11)"""
+    _fields_ = [("k", C.c_int32), ("det_run", C.c_int32), ("tvar", C.c_int32), ("relax_to_inflated_prior", C.c_int32),
+                ("iv_q_first", C.c_int32), ("iv_q_last", C.c_int32), ("relax_alpha", C.c_double),
+                ("relax_alpha_spread", C.c_double), ("q_update_top", C.c_double), ("q_sprd_max", C.c_double),
+                ("ntgt", C.c_int64), ("tgt_row", C.c_void_p), ("ensval", C.c_void_p), ("kld", C.c_int64),
+                ("dep", C.c_void_p), ("nobs", C.c_int64), ("rlev_tgt", C.c_void_p), ("rz_tgt", C.c_void_p),
+                ("beta", C.c_void_p), ("infl", C.c_void_p), ("infl_mul", C.c_double), ("ya", C.c_void_p),
+                ("lda", C.c_int64), ("ya_mean", C.c_void_p), ("ya_table", C.c_void_p), ("dep_a", C.c_void_p),
+                ("nobs_out", C.c_void_p), ("status", C.c_void_p), ("list_bytes", C.c_int64)]
+
+
 class SearchTables(C.Structure):
     """letkf_search_tables (include/letkf_amd.h section 3)"""
     _fields_ = [("nctype", C.c_int32), ("ngroup", C.c_int32), ("criterion", C.c_int32), ("nlon", C.c_int32),
@@ -204,6 +216,26 @@ class ObsTable:
         out["tot_g"] = arr(i.tot_g, np.int32, 2 * nc).reshape(nc, 2) if i.tot_g else None
         return out
 
+    def target_groups(self):
+        """das_letkf_obs's targets of this rank: {tvar: rows} (int32 numpy, ascending) of the rows that lie in the INTERIOR
+        cells of each ctype's sorting mesh (not the ngrdsch halo), grouped by letkf_obs_target_var(elm of the ctype) -- so
+        that a sum over the ranks covers every observation once."""
+        import numpy as np
+        h = self.host()
+        ac = self.download()["ac_ext"].astype(np.int64)
+        groups = {}
+        for c in range(h["nctype"]):
+            ni, nsi, nxi = int(h["ngrd_i"][c]), int(h["ngrdsch_i"][c]), int(h["ngrdext_i"][c])
+            nj, nsj = int(h["ngrd_j"][c]), int(h["ngrdsch_j"][c])
+            base = int(h["ac_off"][c])
+            tv = obs_target_var(int(h["elm_ctype"][c]))
+            for j in range(nsj + 1, nsj + nj + 1):        # entry (i, j) at ac_off + i + (ngrdext_i + 1) * (j - 1)
+                r0 = ac[base + nsi + (nxi + 1) * (j - 1)]
+                r1 = ac[base + nsi + ni + (nxi + 1) * (j - 1)]
+                if r1 > r0:
+                    groups.setdefault(tv, []).append(np.arange(r0, r1, dtype=np.int32))
+        return {tv: np.sort(np.concatenate(r)).astype(np.int32) for tv, r in sorted(groups.items())}
+
     def search_tables(self):
         t = SearchTables()
         self._ctx._check(self._ctx._l.letkf_obs_table_search(self._h, C.byref(t)))
@@ -276,6 +308,7 @@ EXPORTS = ["letkf_amd_abi_version", "letkf_amd_last_error", "letkf_ctx_create", 
            "letkf_obs_mesh_dims", "letkf_set_obs_local_dev", "letkf_set_obs_finish_dev", "letkf_set_obs_dev",
            "letkf_obs_table_info_get", "letkf_obs_table_search", "letkf_obs_table_set_varloc", "letkf_obs_table_download",
            "letkf_obs_table_destroy", "letkf_efso_points_dev", "letkf_efso_columns_dev", "letkf_efso_obsense_dev",
+           "letkf_das_obs_dev", "letkf_obs_target_var",
            "letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path", "letkf_sched_plan_check", "letkf_sched_plan_check_units"]
 
 _lib = None
@@ -501,6 +534,26 @@ class Context:
         self._check(self._l.letkf_efso_obsense_dev(self._c, C.c_int32(nterm), C.c_int64(dep.numel()), _ptr(djdy), _ptr(dep),
                                                    _ptr(obsense)))
 
+    # ---- (11) das_letkf_obs: the analysis ensemble in observation space
+    def das_obs(self, k, tvar, tables, ensval, kld, dep, nobs, ya, lda=None, tgt_row=None, ntgt=None, ya_mean=None,
+                ya_table=None, dep_a=None, nobs_out=None, status=None, rlev_tgt=None, rz_tgt=None, beta=None, infl=None,
+                infl_mul=1.0, det_run=False, relax_to_inflated_prior=False, relax_alpha=0.0, relax_alpha_spread=0.0,
+                q_update_top=0.0, q_sprd_max=0.0, iv_q_first=5, iv_q_last=10, list_bytes=0):
+        """letkf_das_obs_dev: the LETKF at every target row's own location (tgt_row None: rows 0..ntgt-1, ntgt = nobs by
+        default); ya [ntgt][lda] the analysis members, the other outputs optional."""
+        a = DasObsArgs()
+        a.k, a.det_run, a.tvar = k, int(bool(det_run)), int(tvar)
+        a.relax_to_inflated_prior = int(bool(relax_to_inflated_prior))
+        a.iv_q_first, a.iv_q_last = iv_q_first, iv_q_last
+        a.relax_alpha, a.relax_alpha_spread, a.q_update_top, a.q_sprd_max = relax_alpha, relax_alpha_spread, q_update_top, q_sprd_max
+        a.ntgt = tgt_row.numel() if tgt_row is not None else (nobs if ntgt is None else ntgt)
+        a.tgt_row, a.ensval, a.kld, a.dep, a.nobs = _ptr(tgt_row), _ptr(ensval), kld, _ptr(dep), nobs
+        a.rlev_tgt, a.rz_tgt, a.beta, a.infl, a.infl_mul = _ptr(rlev_tgt), _ptr(rz_tgt), _ptr(beta), _ptr(infl), infl_mul
+        a.ya, a.lda = _ptr(ya), (k + (1 if det_run else 0)) if lda is None else lda
+        a.ya_mean, a.ya_table, a.dep_a = _ptr(ya_mean), _ptr(ya_table), _ptr(dep_a)
+        a.nobs_out, a.status, a.list_bytes = _ptr(nobs_out), _ptr(status), int(list_bytes)
+        self._check(self._l.letkf_das_obs_dev(self._c, C.byref(a), C.byref(tables)))
+
     # ---- (5) set_letkf_obs on the device
     def obs_departure(self, params, elm, dat, err, ensval, kld, val, qc):
         self._check(self._l.letkf_obs_departure_dev(self._c, C.byref(params), C.c_int64(elm.numel()), _ptr(elm),
@@ -708,6 +761,11 @@ def ctype_merge_groups(elm_u_ctype, typ_ctype, ctype_merge):
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_ctype_merge_groups: {rc}")
     return gs[:ng.value + 1].copy(), gm[:nct].copy()
+
+
+def obs_target_var(elm):
+    """letkf_obs_target_var (host only): the 0-based grid variable das_letkf_obs regards an observation element as, -1 none."""
+    return int(lib().letkf_obs_target_var(C.c_int32(int(elm))))
 
 
 def radar_only(typ_ctype, typ_radar=22):

@@ -86,6 +86,8 @@ struct letkf_ctx {
   int limited_rings = 2;      // LETKF_OPT_LIMITED_RINGS: 0 never, 1 wherever eligible, 2 where a group's survivors overflow the column kernel's buffer
   char* efso_ws = nullptr;    // EFSO: the pair contributions of a slab, their sort by observation row and the row offsets
   size_t efso_ws_bytes = 0;
+  char* obsanal_ws = nullptr; // das_letkf_obs: the targets' coordinates, pseudo-state, inflation and flag word
+  size_t obsanal_ws_bytes = 0;
   char* staged_ws = nullptr;  // staged path: per-point slabs of a batch + meta / info words
   size_t staged_ws_bytes = 0;
   std::string last_path;      // kernels the last loop-body / letkf_core launch went through (bench.py reports it)
@@ -538,6 +540,7 @@ int letkf_ctx_destroy(letkf_ctx* c) {
     if (c->ring_ws) (void)hipFree(c->ring_ws);
     if (c->ring_aux) (void)hipFree(c->ring_aux);
     if (c->efso_ws) (void)hipFree(c->efso_ws);
+    if (c->obsanal_ws) (void)hipFree(c->obsanal_ws);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   }
   delete c;
@@ -1029,6 +1032,164 @@ int letkf_efso_obsense_dev(letkf_ctx* c, int32_t nterm, int64_t nobs, const doub
   if (nobs > 0 && (!djdy || !dep || !obsense)) return fail(LETKF_E_INVALID, "a required pointer is NULL (djdy, dep, obsense)");
   HIP_TRY(letkf::launch_efso_obsense(nterm, nobs, djdy, dep, obsense, c->stream));
   return LETKF_OK;
+}
+
+// (11) das_letkf_obs (scale/letkf/letkf_tools.f90:933-1156): the loop body at every target observation's own location, on
+// the two-variable pseudo-state of letkf_obsanal.hip (variable 0 the target, variable 1 its pressure for Q_UPDATE_TOP), in
+// chunks of targets whose lists fit list_bytes
+int letkf_das_obs_dev(letkf_ctx* c, const letkf_das_obs_args* g, const letkf_search_tables* t) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!g || !t) return fail(LETKF_E_INVALID, "args / tables is NULL");
+  const int det = g->det_run ? 1 : 0;
+  if (g->k < 2) return fail(LETKF_E_INVALID, "ensemble size must be >= 2");
+  if (g->ntgt < 0) return fail(LETKF_E_INVALID, "negative ntgt");
+  if (g->lda < g->k + det) return fail(LETKF_E_INVALID, "lda too small for k (+1 with det_run)");
+  if (g->kld < g->k + det) return fail(LETKF_E_INVALID, "kld too small for k (+1 with det_run)");
+  if (!g->ensval || !g->dep || !g->ya) return fail(LETKF_E_INVALID, "a required pointer is NULL (ensval, dep, ya)");
+  if (g->ntgt == 0) return LETKF_OK;
+  if (g->nobs < 1) return fail(LETKF_E_INVALID, "targets in a table without rows");
+  if (g->nobs > 0x7fffffff) return fail(LETKF_E_INVALID, "more than 2^31 observation rows");
+  if (t->nctype < 1 || t->ngroup < 1) return fail(LETKF_E_INVALID, "bad nctype / ngroup");
+  const int64_t n = g->ntgt;
+  const int k = g->k;
+  const bool qvar = g->tvar >= 0 && g->tvar >= g->iv_q_first && g->tvar <= g->iv_q_last;
+  const bool qtop = qvar && g->q_update_top > 0.0;
+  const bool qsprd = g->tvar >= 0 && g->tvar == g->iv_q_first && g->q_sprd_max > 0.0;
+  // the tables with what the host now knows of the limits: the fill passes of the chunks read nothing back
+  letkf_search_tables tab = *t;
+  if (tab.limit_hint != 1 && tab.limit_hint != 2) {
+    bool limited = false;
+    if (int rc = tables_limited(c, t, &limited)) return rc;
+    tab.limit_hint = limited ? 2 : 1;
+  }
+  // workspace: ri | rj | rlev | rz [n] | infl [2 n] | gues [2 (k + 2) n] | anal [2 (k + 2) n] | flag word
+  const size_t nd = (size_t)n, ps = 2 * (size_t)(k + 2) * nd;
+  const size_t o_flag = (((6 * nd + 2 * ps) * 8) + 255) & ~(size_t)255;
+  if (int rc = grow(c, &c->obsanal_ws, &c->obsanal_ws_bytes, o_flag + 256)) return rc;
+  double* w = reinterpret_cast<double*>(c->obsanal_ws);
+  letkf::ObsAnalArgs o;
+  std::memset(&o, 0, sizeof(o));
+  o.tab = tab;
+  o.k = k;
+  o.det_run = det;
+  o.q_top = qtop ? 1 : 0;
+  o.ntgt = n;
+  o.nobs = g->nobs;
+  o.kld = g->kld;
+  o.lda = g->lda;
+  o.tgt_row = g->tgt_row;
+  o.ensval = g->ensval;
+  o.dep = g->dep;
+  o.rlev_tgt = g->rlev_tgt;
+  o.rz_tgt = g->rz_tgt;
+  o.infl = g->infl;
+  o.infl_mul = g->infl_mul;
+  o.ri = w;
+  o.rj = w + nd;
+  o.rlev = w + 2 * nd;
+  o.rz = w + 3 * nd;
+  o.infl_ws = w + 4 * nd;
+  o.gues = w + 6 * nd;
+  o.anal = w + 6 * nd + ps;
+  o.flags = reinterpret_cast<unsigned*>(c->obsanal_ws + o_flag);
+  o.ya = g->ya;
+  o.ya_mean = g->ya_mean;
+  o.ya_table = g->ya_table;
+  o.dep_a = g->dep_a;
+  // workspace: counts [n + 1] int32 | obs_off [n + 1] int64 | scan scratch
+  size_t scan_bytes = 0;
+  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, nd + 1, c->stream));
+  const size_t off_off = ((nd + 1) * 4 + 255) & ~(size_t)255;
+  const size_t off_scan = off_off + (((nd + 1) * 8 + 255) & ~(size_t)255);
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
+  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch);
+  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
+  // ---- targets, count pass, prefix sum; the offsets and the argument flags back to the host (the one synchronisation)
+  HIP_TRY(hipMemsetAsync(o.flags, 0, 4, c->stream));
+  HIP_TRY(letkf::launch_obsanal_targets(o, c->stream));
+  HIP_TRY(hipMemsetAsync(counts + n, 0, 4, c->stream));
+  if (int rc = letkf_obs_search_dev(c, &tab, n, o.ri, o.rj, o.rlev, o.rz, 0, counts, nullptr, nullptr, nullptr, nullptr)) return rc;
+  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, nd + 1, c->stream));
+  std::vector<int64_t> hoff(nd + 1);
+  unsigned flags = 0;
+  HIP_TRY(hipMemcpyAsync(hoff.data(), off, (nd + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&flags, o.flags, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (flags & letkf::kObsAnalBadRow) return fail(LETKF_E_INVALID, "a tgt_row entry outside [0, nobs)");
+  if (flags & letkf::kObsAnalNoCtype) return fail(LETKF_E_INVALID, "a target row lies in no ctype block of the tables");
+  if (flags & letkf::kObsAnalNoCoord)
+    return fail(LETKF_E_INVALID, "the tables need a vertical coordinate of the targets that rlev_tgt / rz_tgt does not give");
+  if (g->nobs_out) {
+    HIP_TRY(hipMemcpyAsync(g->nobs_out, counts, nd * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (g->beta) {   // (as letkf_das_columns_dev reports them: no obs_local where beta = 0)
+      hipLaunchKernelGGL(zero_where_beta_is_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, g->beta, g->nobs_out);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  // ---- chunks of targets whose lists fit the workspace (20 B per entry), at least one target each: fill pass, loop body
+  const int64_t list_bytes = g->list_bytes > 0 ? g->list_bytes : ((int64_t)8 << 30);
+  letkf_das_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.k = k;
+  a.nv = 2;
+  a.det_run = det;
+  a.relax_to_inflated_prior = g->relax_to_inflated_prior;
+  a.iv_p = 1;
+  a.iv_q_first = qvar ? 0 : 2;   // (an empty range beyond the two variables where tvar is no moisture variable)
+  a.iv_q_last = qvar ? 0 : 1;
+  a.relax_alpha = g->relax_alpha;
+  a.relax_alpha_spread = g->relax_alpha_spread;
+  a.q_update_top = qtop ? g->q_update_top : 0.0;
+  a.q_sprd_max = qsprd ? g->q_sprd_max : 0.0;
+  a.ensval = g->ensval;
+  a.kld = g->kld;
+  a.dep = g->dep;
+  a.sp = 1;
+  a.sm = n;
+  a.sv = n * (int64_t)(k + 2);
+  a.warm_run = 1;
+  a.var_mask = 1u;
+  a.infl_sv = n;
+  std::string path;
+  for (int64_t p0 = 0; p0 < n;) {
+    int64_t p1 = p0 + 1;
+    while (p1 < n && (hoff[p1 + 1] - hoff[p0]) * 20 <= list_bytes) ++p1;
+    const size_t n1 = (size_t)std::max<int64_t>(hoff[p1] - hoff[p0], 1);
+    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
+    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, o_rl + n1 * 8 + 256)) return rc;
+    // list entry e of the chunk's target p at base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
+    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - hoff[p0];
+    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - hoff[p0];
+    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - hoff[p0];
+    if (int rc = letkf_obs_search_dev(c, &tab, p1 - p0, o.ri + p0, o.rj + p0, o.rlev + p0, o.rz + p0, 1, nullptr, off + p0, idx, rd, rl))
+      return rc;
+    a.npts = p1 - p0;
+    a.obs_off = off + p0;
+    a.obs_idx = idx;
+    a.rdiag_l = rd;
+    a.rloc_l = rl;
+    a.beta = g->beta ? g->beta + p0 : nullptr;
+    a.infl = o.infl_ws + p0;
+    a.gues = o.gues + p0;
+    a.anal = o.anal + p0;
+    a.status = g->status ? g->status + p0 : nullptr;
+    if (int rc = das_points_impl(c, &a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    path = c->last_path;
+    p0 = p1;
+  }
+  HIP_TRY(letkf::launch_obsanal_finish(o, c->stream));
+  c->last_path = "obs_search + " + path + " + obsanal_finish_kernel";
+  return LETKF_OK;
+}
+
+int letkf_obs_target_var(int32_t elm) {
+  switch (elm) {
+    case 2819: return 0;              // id_u_obs -> iv3d_u
+    case 2820: return 1;              // id_v_obs -> iv3d_v
+    case 3073: case 3074: return 3;   // id_t_obs, id_tv_obs -> iv3d_t
+    case 3330: case 3331: return 5;   // id_q_obs, id_rh_obs -> iv3d_q
+    default: return -1;               // ps (nv2d = 0), rain, radar, H08, TC: n = 0
+  }
 }
 
 int letkf_ens_to_perturbations_dev(letkf_ctx* c, int32_t k, int32_t nv, int64_t npts, double* x, int64_t sp,

@@ -324,4 +324,32 @@ hipError_t efso_slab(const EfsoArgs& a, long npts, long e_base, long e_end, char
 hipError_t launch_efso_obsense(int nterm, long nobs, const double* djdy, const double* dep, double* obsense, hipStream_t st);
 const char* efso_path_name(int nterm);
 
+// das_letkf_obs (letkf_obsanal.hip): the targets kernel builds the pseudo-state of one point per target, the finish kernel
+// turns the loop body's analysis of it into the obs-space outputs.  Flag bits the targets kernel ORs into *flags:
+constexpr unsigned kObsAnalBadRow = 1u, kObsAnalNoCtype = 2u, kObsAnalNoCoord = 4u;
+struct ObsAnalArgs {
+  letkf_search_tables tab;     // the search tables (vmode, ac_off, ac_ext, ngrdext_*, ob_*, rain_base are read)
+  int k, det_run, q_top;       // q_top: Q_UPDATE_TOP applies to the call's variable (the tables then need rlev everywhere)
+  long ntgt, nobs, kld, lda;
+  const int* tgt_row;          // [ntgt] or null (target t = row t)
+  const double* ensval;        // [nobs][kld]
+  const double* dep;           // [nobs]
+  const double *rlev_tgt, *rz_tgt;   // [ntgt] or null
+  const double* infl;          // [ntgt] or null (infl_mul everywhere)
+  double infl_mul;
+  // workspace: coordinates [ntgt] each, pseudo-state gues / anal [2][k + 2][ntgt], inflation [2][ntgt], the flag word
+  double *ri, *rj, *rlev, *rz;
+  double* gues;
+  double* anal;
+  double* infl_ws;
+  unsigned* flags;
+  // outputs (ya required, the rest may be null)
+  double* ya;                  // [ntgt][lda]
+  double* ya_mean;             // [ntgt]
+  double* ya_table;            // [nobs][kld], rows tgt_row[t] only
+  double* dep_a;               // [ntgt]
+};
+hipError_t launch_obsanal_targets(const ObsAnalArgs& a, hipStream_t st);
+hipError_t launch_obsanal_finish(const ObsAnalArgs& a, hipStream_t st);
+
 }  // namespace letkf

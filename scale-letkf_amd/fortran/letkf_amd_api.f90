@@ -42,6 +42,24 @@ MODULE letkf_amd_api
     INTEGER(c_int64_t) :: pair_bytes
   END TYPE letkf_efso_args
 
+  ! include/letkf_amd.h section 11: the analysis ensemble in observation space (das_letkf_obs, letkf_tools.f90:933-1156)
+  TYPE, BIND(C) :: letkf_das_obs_args
+    INTEGER(c_int32_t) :: k, det_run, tvar, relax_to_inflated_prior
+    INTEGER(c_int32_t) :: iv_q_first, iv_q_last
+    REAL(c_double)     :: relax_alpha, relax_alpha_spread, q_update_top, q_sprd_max
+    INTEGER(c_int64_t) :: ntgt
+    TYPE(c_ptr)        :: tgt_row, ensval
+    INTEGER(c_int64_t) :: kld
+    TYPE(c_ptr)        :: dep
+    INTEGER(c_int64_t) :: nobs
+    TYPE(c_ptr)        :: rlev_tgt, rz_tgt, beta, infl
+    REAL(c_double)     :: infl_mul
+    TYPE(c_ptr)        :: ya
+    INTEGER(c_int64_t) :: lda
+    TYPE(c_ptr)        :: ya_mean, ya_table, dep_a, nobs_out, status
+    INTEGER(c_int64_t) :: list_bytes
+  END TYPE letkf_das_obs_args
+
   ! include/letkf_amd.h section 7
   TYPE, BIND(C) :: letkf_beta_params
     INTEGER(c_int32_t) :: radar_only, ihalo, jhalo, nlong, nlatg, reserved0
@@ -335,6 +353,19 @@ MODULE letkf_amd_api
       INTEGER(c_int32_t), VALUE :: nterm
       INTEGER(c_int64_t), VALUE :: nobs
       INTEGER(c_int) :: rc
+    END FUNCTION
+    ! ---- section 11: das_letkf_obs on the device, and the reference's element -> grid variable map (0-based, -1 none)
+    FUNCTION letkf_das_obs_dev(ctx, args, tables) BIND(C, name='letkf_das_obs_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, letkf_das_obs_args, letkf_search_tables
+      TYPE(c_ptr), VALUE :: ctx
+      TYPE(letkf_das_obs_args), INTENT(IN) :: args
+      TYPE(letkf_search_tables), INTENT(IN) :: tables
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_obs_target_var(elm) BIND(C, name='letkf_obs_target_var') RESULT(tv)
+      IMPORT :: c_int, c_int32_t
+      INTEGER(c_int32_t), VALUE :: elm
+      INTEGER(c_int) :: tv
     END FUNCTION
     ! ---- section 4: the steps either side of the loop (row f3)
     FUNCTION letkf_state_trans_dev(ctx, c, nlev, nlon, nlat, nv3d, v3dg, inverse) &

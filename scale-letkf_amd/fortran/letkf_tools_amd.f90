@@ -26,7 +26,7 @@ MODULE letkf_tools_amd
   USE letkf_amd_api
   IMPLICIT NONE
   PRIVATE
-  PUBLIC :: das_letkf_amd, das_efso_amd, letkf_das_nml, letkf_obs_tables, letkf_obs_tables_dev, letkf_vmode, letkf_obs_tables_dev_free
+  PUBLIC :: das_letkf_amd, das_efso_amd, das_letkf_obs_amd, letkf_das_nml, letkf_obs_tables, letkf_obs_tables_dev, letkf_vmode, letkf_obs_tables_dev_free
 
   INTEGER, PARAMETER :: r_size = c_double
   INTEGER, PARAMETER :: nlt = 9               ! columns of var_local: VAR_LOCAL_UV .. VAR_LOCAL_H08 (letkf_tools.f90:130-138)
@@ -415,6 +415,129 @@ CONTAINS
     END IF
     CALL free_all([d_rig, d_rjg, d_rlev, d_rz, d_fcst, d_fcer, d_ya, d_dep, d_djdy, d_obsense])
   END SUBROUTINE das_efso_amd
+
+  ! das_letkf_obs (scale/letkf/letkf_tools.f90:933-1156) on the device: the analysis ensemble at every target observation, one
+  ! letkf_das_obs_dev call per target variable tvar = letkf_obs_target_var(elm) (include/letkf_amd.h section 11).  Per tvar the
+  ! tables' varloc (a device array [nctype]) is set to var_local(tvar, uid_obs_varlocal(elm of the ctype)), all ones for
+  ! tvar = -1 (the reference's nvar = 0), and restored after the last call.
+  !   tables              device search tables (what set_letkf_obs_amd leaves, letkf_obs_table_search)
+  !   uid_varlocal_ctype  column of nml%var_local per combined type, 1..9
+  !   ensval, dep         obsda_sort%ensval(1:kld, :) and %val
+  !   tgt_row, tgt_elm    1-based obsda_sort rows of the targets (e.g. this rank's interior rows) and their obs element
+  !   ya                  (member (+1 with det_run), ntgt): obsanalNNN (and the deterministic member); ya_mean, dep_a (ntgt)
+  !   ya_table            (kld, nobs) INOUT: the target rows get ya - ya_mean (set_efso_obs's obshdxf), other rows untouched
+  !   rlev_tgt / rz_tgt   the other vertical coordinate of the targets where the tables need it; infl: rho per target
+  !                       (default nml%infl_mul)
+  SUBROUTINE das_letkf_obs_amd(ctx, nml, tables, nctype, uid_varlocal_ctype, kld, nobs, ensval, dep, ntgt, tgt_row, tgt_elm, &
+                               ya, ya_mean, dep_a, ya_table, rlev_tgt, rz_tgt, infl)
+    TYPE(c_ptr), INTENT(IN) :: ctx
+    TYPE(letkf_das_nml), INTENT(IN) :: nml
+    TYPE(letkf_search_tables), INTENT(IN) :: tables
+    INTEGER, INTENT(IN) :: nctype, kld, nobs, ntgt
+    INTEGER, INTENT(IN) :: uid_varlocal_ctype(nctype), tgt_row(ntgt), tgt_elm(ntgt)
+    REAL(r_size), INTENT(IN), TARGET :: ensval(kld, nobs), dep(nobs)
+    REAL(r_size), INTENT(OUT) :: ya(:, :), ya_mean(ntgt), dep_a(ntgt)
+    REAL(r_size), INTENT(INOUT), TARGET :: ya_table(kld, nobs)
+    REAL(r_size), INTENT(IN), OPTIONAL :: rlev_tgt(ntgt), rz_tgt(ntgt), infl(ntgt)
+    TYPE(letkf_das_obs_args) :: a
+    TYPE(c_ptr) :: d_ens, d_dep, d_tab, d_row, d_rlev, d_rz, d_infl, d_ya, d_ym, d_da
+    REAL(r_size), TARGET :: vl0(MAX(nctype, 1)), vl(MAX(nctype, 1))
+    INTEGER :: tv(ntgt), sel(ntgt), lda, tvar, n, i, ic
+    INTEGER(c_int32_t), ALLOCATABLE, TARGET :: rows0(:)
+    REAL(r_size), ALLOCATABLE, TARGET :: buf(:), hya(:, :), hym(:), hda(:)
+
+    lda = nml%member + MERGE(1, 0, nml%det_run)
+    IF (SIZE(ya, 1) < lda .OR. SIZE(ya, 2) < ntgt) CALL fail('das_letkf_obs_amd: ya too small')
+    IF (ntgt == 0) RETURN
+    DO i = 1, ntgt
+      tv(i) = letkf_obs_target_var(INT(tgt_elm(i), c_int32_t))
+    END DO
+    d_ens = up(c_loc(ensval), 8_c_size_t*kld*nobs)
+    d_dep = up(c_loc(dep), 8_c_size_t*nobs)
+    d_tab = up(c_loc(ya_table), 8_c_size_t*kld*nobs)
+    CALL chk(hipMemcpy(c_loc(vl0), tables%varloc, 8_c_size_t*nctype, hipMemcpyDeviceToHost), 'download varloc')
+    DO tvar = -1, SIZE(nml%var_local, 1) - 1           ! ascending target variable: the calls' order
+      n = 0
+      DO i = 1, ntgt
+        IF (tv(i) == tvar) THEN
+          n = n + 1
+          sel(n) = i
+        END IF
+      END DO
+      IF (n == 0) CYCLE
+      DO ic = 1, nctype
+        vl(ic) = 1.0d0
+        IF (tvar >= 0) vl(ic) = nml%var_local(tvar + 1, uid_varlocal_ctype(ic))
+      END DO
+      CALL chk(hipMemcpy(tables%varloc, c_loc(vl), 8_c_size_t*nctype, hipMemcpyHostToDevice), 'upload varloc')
+      ALLOCATE (rows0(n), buf(n), hya(lda, n), hym(n), hda(n))
+      rows0 = INT(tgt_row(sel(1:n)) - 1, c_int32_t)
+      d_row = up(c_loc(rows0), 4_c_size_t*n)
+      d_rlev = c_null_ptr
+      d_rz = c_null_ptr
+      d_infl = c_null_ptr
+      IF (PRESENT(rlev_tgt)) THEN
+        buf = rlev_tgt(sel(1:n))
+        d_rlev = up(c_loc(buf), 8_c_size_t*n)
+      END IF
+      IF (PRESENT(rz_tgt)) THEN
+        buf = rz_tgt(sel(1:n))
+        d_rz = up(c_loc(buf), 8_c_size_t*n)
+      END IF
+      IF (PRESENT(infl)) THEN
+        buf = infl(sel(1:n))
+        d_infl = up(c_loc(buf), 8_c_size_t*n)
+      END IF
+      CALL chk(hipMalloc(d_ya, 8_c_size_t*lda*n), 'hipMalloc ya')
+      CALL chk(hipMalloc(d_ym, 8_c_size_t*n), 'hipMalloc ya_mean')
+      CALL chk(hipMalloc(d_da, 8_c_size_t*n), 'hipMalloc dep_a')
+      a%k = nml%member
+      a%det_run = MERGE(1, 0, nml%det_run)
+      a%tvar = tvar
+      a%relax_to_inflated_prior = MERGE(1, 0, nml%relax_to_inflated_prior)
+      a%iv_q_first = nml%iv3d_q - 1
+      a%iv_q_last = nml%iv3d_qlast - 1
+      a%relax_alpha = nml%relax_alpha
+      a%relax_alpha_spread = nml%relax_alpha_spread
+      a%q_update_top = nml%q_update_top
+      a%q_sprd_max = nml%q_sprd_max
+      a%ntgt = n
+      a%tgt_row = d_row
+      a%ensval = d_ens
+      a%kld = kld
+      a%dep = d_dep
+      a%nobs = nobs
+      a%rlev_tgt = d_rlev
+      a%rz_tgt = d_rz
+      a%beta = c_null_ptr
+      a%infl = d_infl
+      a%infl_mul = nml%infl_mul
+      a%ya = d_ya
+      a%lda = lda
+      a%ya_mean = d_ym
+      a%ya_table = d_tab
+      a%dep_a = d_da
+      a%nobs_out = c_null_ptr
+      a%status = c_null_ptr
+      a%list_bytes = nml%list_bytes
+      CALL chk(letkf_das_obs_dev(ctx, a, tables), 'letkf_das_obs_dev')
+      CALL chk(letkf_ctx_synchronize(ctx), 'letkf_ctx_synchronize')
+      CALL chk(hipMemcpy(c_loc(hya), d_ya, 8_c_size_t*lda*n, hipMemcpyDeviceToHost), 'download ya')
+      CALL chk(hipMemcpy(c_loc(hym), d_ym, 8_c_size_t*n, hipMemcpyDeviceToHost), 'download ya_mean')
+      CALL chk(hipMemcpy(c_loc(hda), d_da, 8_c_size_t*n, hipMemcpyDeviceToHost), 'download dep_a')
+      ya(1:lda, sel(1:n)) = hya
+      ya_mean(sel(1:n)) = hym
+      dep_a(sel(1:n)) = hda
+      CALL free_all([d_row, d_ya, d_ym, d_da])
+      IF (c_associated(d_rlev)) CALL free_all([d_rlev])
+      IF (c_associated(d_rz)) CALL free_all([d_rz])
+      IF (c_associated(d_infl)) CALL free_all([d_infl])
+      DEALLOCATE (rows0, buf, hya, hym, hda)
+    END DO
+    CALL chk(hipMemcpy(tables%varloc, c_loc(vl0), 8_c_size_t*nctype, hipMemcpyHostToDevice), 'restore varloc')
+    CALL chk(hipMemcpy(c_loc(ya_table), d_tab, 8_c_size_t*kld*nobs, hipMemcpyDeviceToHost), 'download ya_table')
+    CALL free_all([d_ens, d_dep, d_tab])
+  END SUBROUTINE das_letkf_obs_amd
 
   ! device pointer + an offset in doubles
   FUNCTION off_ptr(base, ndbl) RESULT(p)
