@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LETKF_AMD_ABI_VERSION 10
+#define LETKF_AMD_ABI_VERSION 11
 
 /* host-side errors (function return values) */
 #define LETKF_OK 0
@@ -778,8 +778,9 @@ typedef struct {
 int letkf_efso_points_dev(letkf_ctx *ctx, const letkf_efso_args *args);
 /* For the points p = ij + nij1*lev of a subdomain (npts = nij1*nlev): the column search (3a) and the EFSO passes by slabs
  * of levels whose lists and pair workspace fit list_bytes (0 = 8 GiB; 20 + 8 nterm + 20 B per list entry; a single level
- * that exceeds it still runs), as the list route of letkf_das_columns_dev.  With localisation advection the host passes the
- * advected rig / rjg.  Synchronises the stream once besides the search's own. */
+ * that exceeds it still runs), as the list route of letkf_das_columns_dev.  The search position is the column's own, shared
+ * by its levels: with localisation advection, whose position differs by level, use letkf_efso_locadv_dev and
+ * letkf_efso_search_dev (section 12).  Synchronises the stream once besides the search's own. */
 int letkf_efso_columns_dev(letkf_ctx *ctx, const letkf_efso_args *args, const letkf_search_tables *tables, int64_t nij1,
                            int32_t nlev, const double *rig, const double *rjg, const double *rlev, const double *rz,
                            int64_t list_bytes);
@@ -866,6 +867,50 @@ int letkf_das_obs_dev(letkf_ctx *ctx, const letkf_das_obs_args *args, const letk
  * u -> 0 (U), v -> 1 (V), t and tv -> 3 (T), q and rh -> 5 (QV), every other element (ps, radar, H08, TC, ...) -> -1.
  * (SCALE has nv2d = 0: ps has no 2-D variable to map to.)  Host only. */
 int letkf_obs_target_var(int32_t elm);
+
+/*---------------------------------------------------------------------------
+ * (12, ABI 11) EFSO with localisation advection: the other branch of das_efso (scale/letkf/letkf_tools.f90:1225-1229),
+ *     where obs_local runs at each point's advected position rather than at its column's.
+ *
+ *     letkf_efso_locadv_dev -- loc_advection (scale/letkf/efso_tools.f90:158-195) in SCALE's grid frame.  For every point
+ *     p = ij + nij1*lev (npts = nij1*nlev):
+ *       c_i = locadv_rate * eft * 3600 / dx,   c_j = locadv_rate * eft * 3600 / dy       (host, once, in this order)
+ *       ri[p] = rig[ij] - (0.5 * (u0[p] + u1[p])) * c_i
+ *       rj[p] = rjg[ij] - (0.5 * (v0[p] + v1[p])) * c_j
+ *     Positions are fractional global grid indices as rig / rjg (obs_local_cal turns them into metres with dx / dy), so
+ *     the reference's 1/cos(lat), pole reflection and longitude wrap of its lon/lat grid have no counterpart on SCALE's
+ *     Cartesian grid and are not applied.  u0 / v0 are the analysis-mean winds at the initial time, u1 / v1 the winds
+ *     at the evaluation time (the reference's uadf / vadf), in m/s; eft in hours; dx / dy in metres.  rig / rjg: dev
+ *     [nij1]; u0, v0, u1, v1, ri, rj: dev [npts] (a variable slot of the mean in the layout of section 2 is such an
+ *     array).  No multiply-add fusion: the bits are those of the formula evaluated operation by operation in IEEE
+ *     double.  Points whose result is not finite or that move by more than 2^20 cells in either direction (the column
+ *     positions lie in the subdomain, so every accepted position lies within 2^20 cells of it -- the search's grid
+ *     cell stays inside int) are counted on the device and read back once: any such point gives LETKF_E_INVALID
+ *     (ri / rj are written all the same).  LETKF_E_INVALID also for nij1 < 1, nlev < 1, a NULL pointer, dx or dy not
+ *     finite and > 0, or locadv_rate / eft not finite.  Synchronises the stream once.
+ *
+ *     letkf_efso_search_dev -- section 10's EFSO for npts points at per-point positions (ri, rj) with their own rlev /
+ *     rz (the reference passes pfull(ij, ilev): the vertical coordinates are not advected): one count pass of the
+ *     point search (3) over all points, the device scan, one read-back of the list offsets; then for each run of
+ *     consecutive points whose lists and pair workspace fit list_bytes (0 = 8 GiB; 20 + 8 nterm + 20 B per list entry;
+ *     one point always runs) the fill pass and the EFSO passes.  The runs are taken in ascending order, so every row's
+ *     sum goes on in ascending point order and the bits do not depend on list_bytes: they are those of
+ *     letkf_obs_search_dev + letkf_efso_points_dev on the same positions, and with every point at its column's position
+ *     and no MAX_NOBS_PER_GRID limit those of letkf_efso_columns_dev.  Limited tables go through the point search's
+ *     own selection.  Points whose position lies outside the extended subdomain find no observation.  args->npts must
+ *     equal npts; args->obs_off / obs_idx / rdiag_l / rloc_l / pair_bytes are ignored.  LETKF_E_INVALID: section 10's
+ *     conditions, tables / a coordinate array NULL, npts mismatch, bad nctype / ngroup / criterion.
+ *     Synchronisations: one read-back of the list offsets, besides the search's own (none when tables->limit_hint is
+ *     set); none per run.
+ *
+ *     Out of scope: a column-cooperative search for advected positions (levels move by different amounts, so a column's
+ *     union of search windows is no longer one horizontal pass), and the energy norm (the host's, as section 10).
+ *-------------------------------------------------------------------------*/
+int letkf_efso_locadv_dev(letkf_ctx *ctx, int64_t nij1, int32_t nlev, const double *rig, const double *rjg, const double *u0,
+                          const double *v0, const double *u1, const double *v1, double locadv_rate, double eft, double dx,
+                          double dy, double *ri, double *rj);
+int letkf_efso_search_dev(letkf_ctx *ctx, const letkf_efso_args *args, const letkf_search_tables *tables, int64_t npts,
+                          const double *ri, const double *rj, const double *rlev, const double *rz, int64_t list_bytes);
 
 /* Name(s) of the kernel(s) the context's last letkf_das_points*_dev / letkf_core_batch_dev / letkf_efso_*_dev call went
  * through, as a NUL-terminated string (truncated to len): what bench.py reports as roofline.kernel. */

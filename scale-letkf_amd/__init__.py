@@ -308,8 +308,15 @@ EXPORTS = ["letkf_amd_abi_version", "letkf_amd_last_error", "letkf_ctx_create", 
            "letkf_obs_mesh_dims", "letkf_set_obs_local_dev", "letkf_set_obs_finish_dev", "letkf_set_obs_dev",
            "letkf_obs_table_info_get", "letkf_obs_table_search", "letkf_obs_table_set_varloc", "letkf_obs_table_download",
            "letkf_obs_table_destroy", "letkf_efso_points_dev", "letkf_efso_columns_dev", "letkf_efso_obsense_dev",
-           "letkf_das_obs_dev", "letkf_obs_target_var",
+           "letkf_das_obs_dev", "letkf_obs_target_var", "letkf_efso_locadv_dev", "letkf_efso_search_dev",
            "letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path", "letkf_sched_plan_check", "letkf_sched_plan_check_units"]
+
+# ctypes signatures of the entries that are called with them (include/letkf_amd.h; pointers as void *)
+_VP, _I32, _I64, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+ARGTYPES = {
+    "letkf_efso_locadv_dev": [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _F64, _F64, _F64, _F64, _VP, _VP],
+    "letkf_efso_search_dev": [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64],
+}
 
 _lib = None
 
@@ -329,6 +336,9 @@ def lib():
         _lib.letkf_amd_last_error.restype = C.c_char_p
         for name in EXPORTS:
             getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
+        for name, at in ARGTYPES.items():
+            f = getattr(_lib, name)
+            f.argtypes, f.restype = at, C.c_int
     return _lib
 
 
@@ -533,6 +543,31 @@ class Context:
         """letkf_efso_obsense_dev: obsense[j*nterm + t] = djdy[j*nterm + t] * dep[j]."""
         self._check(self._l.letkf_efso_obsense_dev(self._c, C.c_int32(nterm), C.c_int64(dep.numel()), _ptr(djdy), _ptr(dep),
                                                    _ptr(obsense)))
+
+    # ---- (12) EFSO with localisation advection
+    def efso_locadv(self, rig, rjg, nlev, u0, v0, u1, v1, locadv_rate, eft, dx, dy, ri=None, rj=None):
+        """letkf_efso_locadv_dev: the advected search positions (ri, rj) [nij1*nlev] of the points p = ij + nij1*lev,
+        ri = rig[ij] - (0.5 (u0 + u1)) * locadv_rate*eft*3600/dx (rj likewise with v, dy); allocated when not given."""
+        import torch
+        nij1 = rig.numel()
+        if ri is None:
+            ri = torch.empty(nij1 * nlev, dtype=torch.float64, device=rig.device)
+        if rj is None:
+            rj = torch.empty(nij1 * nlev, dtype=torch.float64, device=rig.device)
+        self._check(self._l.letkf_efso_locadv_dev(self._c, nij1, nlev, _ptr(rig), _ptr(rjg), _ptr(u0), _ptr(v0), _ptr(u1),
+                                                  _ptr(v1), float(locadv_rate), float(eft), float(dx), float(dy), _ptr(ri),
+                                                  _ptr(rj)))
+        return ri, rj
+
+    def efso_search(self, k, nv, term_of_var, nterm, tables, ri, rj, rlev, rz, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp,
+                    fsv, djdy, var_mask=0, list_bytes=0, npts=None):
+        """letkf_efso_search_dev: the point search and EFSO at per-point positions, in runs of points that fit list_bytes
+        (npts: the count passed beside args->npts = ri.numel(), for argument checks)."""
+        n = ri.numel() if ri is not None else int(npts)
+        a, keep = self._efso_args(k, nv, term_of_var, nterm, n, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp, fsv, djdy,
+                                  var_mask)
+        self._check(self._l.letkf_efso_search_dev(self._c, C.byref(a), C.byref(tables), n if npts is None else npts, _ptr(ri),
+                                                  _ptr(rj), _ptr(rlev), _ptr(rz), int(list_bytes)))
 
     # ---- (11) das_letkf_obs: the analysis ensemble in observation space
     def das_obs(self, k, tvar, tables, ensval, kld, dep, nobs, ya, lda=None, tgt_row=None, ntgt=None, ya_mean=None,

@@ -11,6 +11,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1031,6 +1032,102 @@ int letkf_efso_obsense_dev(letkf_ctx* c, int32_t nterm, int64_t nobs, const doub
   if (nobs < 0) return fail(LETKF_E_INVALID, "negative nobs");
   if (nobs > 0 && (!djdy || !dep || !obsense)) return fail(LETKF_E_INVALID, "a required pointer is NULL (djdy, dep, obsense)");
   HIP_TRY(letkf::launch_efso_obsense(nterm, nobs, djdy, dep, obsense, c->stream));
+  return LETKF_OK;
+}
+
+// (12) das_efso's advection branch (letkf_tools.f90:1225-1229): loc_advection (efso_tools.f90:158-195) on SCALE's grid
+int letkf_efso_locadv_dev(letkf_ctx* c, int64_t nij1, int32_t nlev, const double* rig, const double* rjg, const double* u0,
+                          const double* v0, const double* u1, const double* v1, double locadv_rate, double eft, double dx,
+                          double dy, double* ri, double* rj) {
+  if (int rc = check_ctx(c)) return rc;
+  if (nij1 < 1 || nlev < 1) return fail(LETKF_E_INVALID, "nij1 and nlev must be >= 1");
+  if (!rig || !rjg || !u0 || !v0 || !u1 || !v1 || !ri || !rj)
+    return fail(LETKF_E_INVALID, "a required pointer is NULL (rig, rjg, u0, v0, u1, v1, ri, rj)");
+  if (!(std::isfinite(dx) && dx > 0.0) || !(std::isfinite(dy) && dy > 0.0)) return fail(LETKF_E_INVALID, "dx and dy must be finite and > 0");
+  if (!std::isfinite(locadv_rate) || !std::isfinite(eft)) return fail(LETKF_E_INVALID, "locadv_rate and eft must be finite");
+  // the reference's rad2deg = locadv_rate*eft*3600*180/(pi*re), with the grid spacing in place of the arc per degree
+  const double ci = locadv_rate * eft * 3600.0 / dx;
+  const double cj = locadv_rate * eft * 3600.0 / dy;
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, 256)) return rc;
+  unsigned* bad = reinterpret_cast<unsigned*>(c->scratch);
+  HIP_TRY(hipMemsetAsync(bad, 0, 4, c->stream));
+  HIP_TRY(letkf::launch_efso_locadv(nij1, nij1 * (int64_t)nlev, rig, rjg, u0, v0, u1, v1, ci, cj, ri, rj, bad, c->num_cu,
+                                    c->stream));
+  unsigned nbad = 0;
+  HIP_TRY(hipMemcpyAsync(&nbad, bad, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->last_path = "efso_locadv_kernel";
+  if (nbad)
+    return fail(LETKF_E_INVALID, std::to_string(nbad) + " point(s) advected to a non-finite position or by more than 2^20 cells");
+  return LETKF_OK;
+}
+
+// (12) EFSO at per-point positions: the point search (3) and the EFSO passes in runs of consecutive points whose lists and
+// pair workspace fit list_bytes -- the chunking of letkf_das_obs_dev
+int letkf_efso_search_dev(letkf_ctx* c, const letkf_efso_args* g, const letkf_search_tables* t, int64_t npts, const double* ri,
+                          const double* rj, const double* rlev, const double* rz, int64_t list_bytes) {
+  letkf::EfsoArgs a;
+  if (int rc = efso_check(c, g, false, &a)) return rc;
+  if (!t) return fail(LETKF_E_INVALID, "tables is NULL");
+  if (npts != g->npts) return fail(LETKF_E_INVALID, "npts must equal args->npts");
+  if (!ri || !rj || !rlev || !rz) return fail(LETKF_E_INVALID, "a point coordinate array is NULL");
+  if (t->nctype < 1 || t->ngroup < 1 || t->criterion < 1 || t->criterion > 3)
+    return fail(LETKF_E_INVALID, "bad nctype / ngroup / criterion");
+  // the tables with what the host now knows of the limits: the fill passes of the runs read nothing back
+  letkf_search_tables tab = *t;
+  if (tab.limit_hint != 1 && tab.limit_hint != 2) {
+    bool limited = false;
+    if (int rc = tables_limited(c, t, &limited)) return rc;
+    tab.limit_hint = limited ? 2 : 1;
+  }
+  c->last_path = std::string(tab.limit_hint == 2 ? "search_kernel (radix select) + " : "search_kernel + ") +
+                 letkf::efso_path_name(g->nterm);
+  if (npts == 0 || g->nobs == 0) return LETKF_OK;
+  if (list_bytes <= 0) list_bytes = (int64_t)8 << 30;
+  const int64_t per_entry = 20 + efso_entry_bytes(g->nterm);
+  const size_t nd = (size_t)npts;
+  // workspace: counts [npts + 1] int32 | obs_off [npts + 1] int64 | scan scratch
+  size_t scan_bytes = 0;
+  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, nd + 1, c->stream));
+  const size_t off_off = ((nd + 1) * 4 + 255) & ~(size_t)255;
+  const size_t off_scan = off_off + (((nd + 1) * 8 + 255) & ~(size_t)255);
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
+  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch);
+  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
+  // ---- count pass over all points, prefix sum, the offsets back to the host (the one synchronisation)
+  HIP_TRY(hipMemsetAsync(counts + npts, 0, 4, c->stream));
+  if (int rc = letkf_obs_search_dev(c, &tab, npts, ri, rj, rlev, rz, 0, counts, nullptr, nullptr, nullptr, nullptr)) return rc;
+  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, nd + 1, c->stream));
+  std::vector<int64_t> hoff(nd + 1);
+  HIP_TRY(hipMemcpyAsync(hoff.data(), off, (nd + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // ---- runs of consecutive points in ascending order, at least one point each: fill pass, EFSO passes
+  for (int64_t p0 = 0; p0 < npts;) {
+    int64_t p1 = p0 + 1;
+    while (p1 < npts && (hoff[p1 + 1] - hoff[p0]) * per_entry <= list_bytes && hoff[p1 + 1] - hoff[p0] <= kEfsoMaxSlab) ++p1;
+    const int64_t nnz = hoff[p1] - hoff[p0];
+    if (nnz > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a point with more than 2^31 local observations");
+    const size_t n1 = (size_t)std::max<int64_t>(nnz, 1);
+    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
+    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, o_rl + n1 * 8 + 256)) return rc;
+    // list entry e of the run's point p at base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
+    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - hoff[p0];
+    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - hoff[p0];
+    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - hoff[p0];
+    if (nnz > 0) {
+      if (int rc = letkf_obs_search_dev(c, &tab, p1 - p0, ri + p0, rj + p0, rlev + p0, rz + p0, 1, nullptr, off + p0, idx, rd, rl))
+        return rc;
+      letkf::EfsoArgs s = a;
+      s.obs_off = reinterpret_cast<const long*>(off + p0);
+      s.obs_idx = idx;
+      s.rdiag_l = rd;
+      s.rloc_l = rl;
+      s.fcst = a.fcst + p0 * a.sp;
+      s.fcer = a.fcer + p0 * a.fsp;
+      if (int rc = efso_run_slab(c, s, p1 - p0, hoff[p0], hoff[p1])) return rc;
+    }
+    p0 = p1;
+  }
   return LETKF_OK;
 }
 

@@ -323,6 +323,12 @@ hipError_t efso_slab(const EfsoArgs& a, long npts, long e_base, long e_end, char
                      hipStream_t st);
 hipError_t launch_efso_obsense(int nterm, long nobs, const double* djdy, const double* dep, double* obsense, hipStream_t st);
 const char* efso_path_name(int nterm);
+// EFSO's localisation advection (letkf_locadv.hip): per-point search positions; *bad += points whose position is not
+// finite or moved by more than kLocAdvMaxCells cells in i or j
+constexpr double kLocAdvMaxCells = 1048576.0;   // 2^20
+hipError_t launch_efso_locadv(long nij1, long npts, const double* rig, const double* rjg, const double* u0, const double* v0,
+                              const double* u1, const double* v1, double ci, double cj, double* ri, double* rj,
+                              unsigned* bad, int num_cu, hipStream_t st);
 
 // das_letkf_obs (letkf_obsanal.hip): the targets kernel builds the pseudo-state of one point per target, the finish kernel
 // turns the loop body's analysis of it into the obs-space outputs.  Flag bits the targets kernel ORs into *flags:

@@ -354,6 +354,25 @@ MODULE letkf_amd_api
       INTEGER(c_int64_t), VALUE :: nobs
       INTEGER(c_int) :: rc
     END FUNCTION
+    ! ---- section 12: EFSO with localisation advection: the advected positions, then EFSO at per-point positions
+    FUNCTION letkf_efso_locadv_dev(ctx, nij1, nlev, rig, rjg, u0, v0, u1, v1, locadv_rate, eft, dx, dy, ri, rj) &
+        BIND(C, name='letkf_efso_locadv_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+      TYPE(c_ptr), VALUE :: ctx, rig, rjg, u0, v0, u1, v1, ri, rj
+      INTEGER(c_int64_t), VALUE :: nij1
+      INTEGER(c_int32_t), VALUE :: nlev
+      REAL(c_double), VALUE :: locadv_rate, eft, dx, dy
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_efso_search_dev(ctx, args, tables, npts, ri, rj, rlev, rz, list_bytes) &
+        BIND(C, name='letkf_efso_search_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int64_t, letkf_efso_args, letkf_search_tables
+      TYPE(c_ptr), VALUE :: ctx, ri, rj, rlev, rz
+      TYPE(letkf_efso_args), INTENT(IN) :: args
+      TYPE(letkf_search_tables), INTENT(IN) :: tables
+      INTEGER(c_int64_t), VALUE :: npts, list_bytes
+      INTEGER(c_int) :: rc
+    END FUNCTION
     ! ---- section 11: das_letkf_obs on the device, and the reference's element -> grid variable map (0-based, -1 none)
     FUNCTION letkf_das_obs_dev(ctx, args, tables) BIND(C, name='letkf_das_obs_dev') RESULT(rc)
       IMPORT :: c_int, c_ptr, letkf_das_obs_args, letkf_search_tables

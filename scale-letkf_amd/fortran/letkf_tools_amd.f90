@@ -15,7 +15,9 @@
 !                                                      letkf_das_columns_dev (column search + loop body by slabs of levels)
 !   letkf.f90:207  ensmean_grd on the analysis          letkf_ens_mean_dev
 ! das_efso_amd is the same for das_efso (:1158-1302, commented out in the reference): obs_local and the EFSO contraction
-! for every point (letkf_efso_columns_dev), then obsense = djdy * dep (letkf_efso_obsense_dev).
+! for every point (letkf_efso_columns_dev), then obsense = djdy * dep (letkf_efso_obsense_dev).  With localisation
+! advection (:1225-1229) obs_local runs at every point's advected position instead (letkf_efso_locadv_dev, then
+! letkf_efso_search_dev).
 ! gues3d / anal3d keep the reference's shape and meaning: gues3d(nij1,nlev,nens,nv3d) INOUT (members 1..MEMBER come back
 ! as perturbations, slot mmean = MEMBER+1 holds the mean, mmdet = MEMBER+2 the deterministic member), anal3d OUT.
 ! 2-D variables: the reference is built with nv2d = 0 (common_scale.f90:53); they are not arguments here (INTEGRATION.md
@@ -350,8 +352,12 @@ CONTAINS
   ! term_of_var(v) = energy term 1..nterm of variable v, 0 = none (das_efso's iterm); ya(kld, nobs) = H X^a (member
   ! perturbations in observation space, obsda_sort order), dep(nobs) = y - H(xmean^b).  djdy(nterm, nobs) INOUT
   ! accumulates over the calls of several classes (var_mask: bit v-1 for variable v, 0 = all); obsense = djdy * dep.
+  ! Localisation advection (efso.f90:136-156, loc_advection in efso_tools.f90:158-195): with u0, v0 (the analysis-mean
+  ! winds at the initial time), u1, v1 (at the evaluation time, the reference's uadf / vadf), locadv_rate, eft (hours),
+  ! dx, dy (m) all present and ABS(locadv_rate) > TINY, obs_local runs at each point's advected position
+  ! (letkf_efso_locadv_dev + letkf_efso_search_dev); otherwise at the column's (letkf_efso_columns_dev).
   SUBROUTINE das_efso_amd(ctx, tables, nij1, nlev, member, nv3d, rig1, rjg1, rlev, hgt1, fcst3d, fcer3d, nterm, term_of_var, &
-                          kld, nobs, ya, dep, djdy, obsense, var_mask)
+                          kld, nobs, ya, dep, djdy, obsense, var_mask, u0, v0, u1, v1, locadv_rate, eft, dx, dy)
     TYPE(c_ptr), INTENT(IN) :: ctx
     TYPE(letkf_search_tables), INTENT(IN) :: tables
     INTEGER, INTENT(IN) :: nij1, nlev, member, nv3d, nterm, kld, nobs
@@ -362,11 +368,14 @@ CONTAINS
     REAL(r_size), INTENT(INOUT), TARGET :: djdy(nterm, nobs)
     REAL(r_size), INTENT(OUT), TARGET :: obsense(nterm, nobs)
     INTEGER, INTENT(IN), OPTIONAL :: var_mask
+    REAL(r_size), INTENT(IN), TARGET, OPTIONAL :: u0(nij1, nlev), v0(nij1, nlev), u1(nij1, nlev), v1(nij1, nlev)
+    REAL(r_size), INTENT(IN), OPTIONAL :: locadv_rate, eft, dx, dy
     INTEGER(c_int32_t), TARGET :: tv(nv3d)
     TYPE(letkf_efso_args) :: a
-    TYPE(c_ptr) :: d_rig, d_rjg, d_rlev, d_rz, d_fcst, d_fcer, d_ya, d_dep, d_djdy, d_obsense
+    TYPE(c_ptr) :: d_rig, d_rjg, d_rlev, d_rz, d_fcst, d_fcer, d_ya, d_dep, d_djdy, d_obsense, d_u0, d_v0, d_u1, d_v1, d_ri, d_rj
     INTEGER(c_int64_t) :: npts
     INTEGER(c_size_t) :: nb_dj
+    LOGICAL :: advect
 
     npts = INT(nij1, c_int64_t)*nlev
     nb_dj = 8_c_size_t*nterm*nobs
@@ -404,8 +413,23 @@ CONTAINS
     a%fsv = npts
     a%djdy = d_djdy
     a%pair_bytes = 0
-    CALL chk(letkf_efso_columns_dev(ctx, a, tables, INT(nij1, c_int64_t), INT(nlev, c_int32_t), d_rig, d_rjg, d_rlev, d_rz, &
-                                    0_c_int64_t), 'letkf_efso_columns_dev')
+    advect = PRESENT(u0) .AND. PRESENT(v0) .AND. PRESENT(u1) .AND. PRESENT(v1) .AND. PRESENT(locadv_rate) .AND. &
+             PRESENT(eft) .AND. PRESENT(dx) .AND. PRESENT(dy)
+    IF (advect) advect = ABS(locadv_rate) > TINY(locadv_rate)
+    IF (advect) THEN                       ! letkf_tools.f90:1225-1227: obs_local at (lon2(ij,ilev), lat2(ij,ilev))
+      d_u0 = up(c_loc(u0), 8_c_size_t*npts)
+      d_v0 = up(c_loc(v0), 8_c_size_t*npts)
+      d_u1 = up(c_loc(u1), 8_c_size_t*npts)
+      d_v1 = up(c_loc(v1), 8_c_size_t*npts)
+      CALL chk(hipMalloc(d_ri, MAX(8_c_size_t*npts, 8_c_size_t)), 'hipMalloc ri')
+      CALL chk(hipMalloc(d_rj, MAX(8_c_size_t*npts, 8_c_size_t)), 'hipMalloc rj')
+      CALL chk(letkf_efso_locadv_dev(ctx, INT(nij1, c_int64_t), INT(nlev, c_int32_t), d_rig, d_rjg, d_u0, d_v0, d_u1, d_v1, &
+                                     locadv_rate, eft, dx, dy, d_ri, d_rj), 'letkf_efso_locadv_dev')
+      CALL chk(letkf_efso_search_dev(ctx, a, tables, npts, d_ri, d_rj, d_rlev, d_rz, 0_c_int64_t), 'letkf_efso_search_dev')
+    ELSE                                   ! :1228-1229: obs_local at the column's (lon1(ij), lat1(ij))
+      CALL chk(letkf_efso_columns_dev(ctx, a, tables, INT(nij1, c_int64_t), INT(nlev, c_int32_t), d_rig, d_rjg, d_rlev, d_rz, &
+                                      0_c_int64_t), 'letkf_efso_columns_dev')
+    END IF
     CALL chk(letkf_efso_obsense_dev(ctx, INT(nterm, c_int32_t), INT(nobs, c_int64_t), d_djdy, d_dep, d_obsense), &
              'letkf_efso_obsense_dev')
     CALL chk(letkf_ctx_synchronize(ctx), 'letkf_ctx_synchronize')
@@ -414,6 +438,7 @@ CONTAINS
       CALL chk(hipMemcpy(c_loc(obsense), d_obsense, nb_dj, hipMemcpyDeviceToHost), 'download obsense')
     END IF
     CALL free_all([d_rig, d_rjg, d_rlev, d_rz, d_fcst, d_fcer, d_ya, d_dep, d_djdy, d_obsense])
+    IF (advect) CALL free_all([d_u0, d_v0, d_u1, d_v1, d_ri, d_rj])
   END SUBROUTINE das_efso_amd
 
   ! das_letkf_obs (scale/letkf/letkf_tools.f90:933-1156) on the device: the analysis ensemble at every target observation, one
