@@ -9,7 +9,14 @@ Not the contract bench (bench.py).
 --locadv: EFSO with localisation advection instead (include/letkf_amd.h section 12): a fixed wind profile u = 10 + 20 lev /
 (nlev - 1) m/s, v = 5 m/s at both times, eft = 1 h, locadv_rate = 0.5 (18 .. 36 cells of displacement at dx = 1 km), then
 letkf_efso_locadv_dev + letkf_efso_search_dev (the point search over every point) against letkf_efso_columns_dev from the
-same process.  Prints one JSON line: ms per call of each route, pairs and pairs per second of the advected route."""
+same process.  Prints one JSON line: ms per call of each route, pairs and pairs per second of the advected route.
+
+--norm: EFSO's two ends (include/letkf_amd.h section 13) at the same size: letkf_efso_norm_dev on a forecast ensemble of
+k members x nv variables (total fields, a pressure profile in slot 4) with the fcer assembly from three means, dp/ps from
+the mean pressure (the two small passes and the one read-back included) and, separately, with dp/ps given; then
+letkf_efso_summary_dev on nterm = 3 impacts of every observation row.  Each norm call gets the pressure slot back first
+(outside the timed interval: the norm works in place).  Prints one JSON line: ms per call, algorithmic bytes (inputs read
+once where the norm needs them, every output written once) as GB/s and as a fraction of 8 TB/s."""
 import json
 import os
 import sys
@@ -38,6 +45,8 @@ def timed(fn, reps):
 
 
 def main():
+    if "--norm" in sys.argv:
+        return main_norm([a for a in sys.argv[1:] if a != "--norm"])
     argv = [a for a in sys.argv[1:] if a != "--locadv"]
     if len(argv) != len(sys.argv) - 1:
         return main_locadv(argv)
@@ -159,6 +168,75 @@ def main_locadv(argv):
         "efso_locadv_search_ms": adv_ms, "efso_locadv_only_ms": locadv_ms, "efso_columns_ms": col_ms,
         "advected_over_columns": adv_ms / col_ms, "pairs": npairs, "pairs_per_s": npairs / (adv_ms * 1e-3),
         "bitwise_repeatable": deterministic, "kernel": "efso_locadv_kernel + " + path}))
+
+
+def main_norm(argv):
+    reps = int(argv[1]) if len(argv) > 1 else 5
+    name = argv[0] if argv else "C2"
+    pkg = load_package()
+    pkg.build()
+    dev = torch.device("cuda:0")
+    ctx = pkg.Context(0, torch.cuda.current_stream().cuda_stream)
+    cfg = bw.CONFIGS[name]
+    k, nv, nobs = cfg["k"], 11, 1 << 20          # (the summary: a million observation rows)
+    nij, nlev = cfg["nx"] * cfg["ny"], cfg["nz"]
+    npts = nij * nlev
+    g = torch.Generator(device=dev)
+    g.manual_seed(3)
+    # the forecast ensemble, gues3d's order (p fastest): total fields, a pressure profile in slot 4 (SCALE's iv3d_p - 1)
+    fcst = torch.randn(nv * k * npts, dtype=torch.float64, device=dev, generator=g).view(nv, k, npts)
+    lev = torch.arange(nlev, dtype=torch.float64, device=dev).repeat_interleave(nij)
+    p_prof = 1.0e5 * torch.exp(-2.5 * lev / max(nlev - 1, 1))
+    fcst[4] = fcst[4] * 50.0 + p_prof
+    p_slot = fcst[4].clone()
+    fcer = torch.zeros(nv * npts, dtype=torch.float64, device=dev)
+    xs = [torch.randn(nv * npts, dtype=torch.float64, device=dev, generator=g) for _ in range(3)]
+    wlev = torch.full((npts,), 1.0 / nlev, dtype=torch.float64, device=dev)
+    prm = pkg.EfsoNormParams()
+    prm.k, prm.nv, prm.iv_u, prm.iv_v, prm.iv_t, prm.iv_q, prm.iv_p = k, nv, 0, 1, 3, 5, 4
+    prm.tar_minlev, prm.tar_maxlev = 1, nlev
+    prm.cp, prm.tref, prm.hvap, prm.wmoist = 1004.64, 280.0, 2.501e6, 1.0
+    prm.tar_minlon, prm.tar_maxlon, prm.tar_minlat, prm.tar_maxlat = 0.0, 360.0, -90.0, 90.0
+    flat = fcst.view(-1)
+
+    def norm_ms(with_wlev):
+        ts = []
+        for _ in range(reps + 1):
+            fcst[4].copy_(p_slot)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ctx.efso_norm(prm, nij, nlev, flat, 1, npts, npts * k, fcer, 1, npts, xf=xs[0], xg=xs[1], xa=xs[2],
+                          wlev=wlev if with_wlev else None)
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return sum(ts[1:]) / reps, ctx.last_path()
+    ms_computed, path = norm_ms(False)
+    ms_given, path_given = norm_ms(True)
+    # algorithmic bytes (fmean not requested): the four variables with a factor read once (k members), the three fcer
+    # means of those four, dp/ps; every output written once; the dp/ps passes read the pressure slot and write / read
+    # the mean pressure and dp/ps
+    nlive = 4
+    main_bytes = 8 * npts * (nlive * k + 3 * nlive + 1 + nv * k + nv)
+    pre_bytes = 8 * npts * (k + 3)
+    # the summary: nterm = 3 impacts of every row
+    nterm, nobtype = 3, 21
+    uid = [2819, 2820, 3073, 3330, 3331, 14593, 4001, 4002]
+    nrow = max(nobs, 1)
+    obsense = torch.randn(nrow * nterm, dtype=torch.float64, device=dev, generator=g)
+    elm = torch.tensor(uid, dtype=torch.int32, device=dev)[torch.randint(0, len(uid), (nrow,), device=dev, generator=g)]
+    typ = torch.randint(1, nobtype + 2, (nrow,), device=dev, generator=g, dtype=torch.int32)
+    olat = torch.rand(nrow, dtype=torch.float64, device=dev, generator=g) * 180.0 - 90.0
+    outs = ctx.efso_summary(nterm, obsense, elm, typ, olat, uid, nobtype)
+    sum_ms = timed(lambda: ctx.efso_summary(nterm, obsense, elm, typ, olat, uid, nobtype, outs=outs), reps)
+    print(json.dumps({
+        "workload": f"{name}: {cfg['nx']}x{cfg['ny']}x{cfg['nz']} = {npts} points, k={k}, nv={nv}, fcer assembled from three "
+                    f"means; summary: {nrow} rows, nterm={nterm}, nobtype={nobtype}, nid={len(uid)}",
+        "efso_norm_ms": ms_computed, "efso_norm_wlev_given_ms": ms_given,
+        "algorithmic_bytes": main_bytes + pre_bytes, "algorithmic_GBps": (main_bytes + pre_bytes) / (ms_computed * 1e-3) / 1e9,
+        "fraction_of_8TBps": (main_bytes + pre_bytes) / (ms_computed * 1e-3) / HBM_BPS,
+        "wlev_given_bytes": main_bytes, "wlev_given_GBps": main_bytes / (ms_given * 1e-3) / 1e9,
+        "efso_summary_ms": sum_ms, "kernel": path, "kernel_wlev_given": path_given}))
 
 
 if __name__ == "__main__":

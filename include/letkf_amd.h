@@ -731,7 +731,8 @@ int letkf_obs_table_destroy(letkf_obs_table *tab);
  *       djdy(t, j) += (rloc / rdiag) * sum_m ensval[j*kld + m] * w_p(t, m)                                ("djdy")
  *     and afterwards obsense(t, j) = djdy(t, j) * dep[j] (:1283-1290).  t = 0..nterm-1 counts the energy terms
  *     (das_efso's 1 = U/V, 2 = T, 3 = Q; the map is the caller's), m = 0..k-1 the members.
- *     Inputs the host prepares, as the reference does before das_efso (efso.f90:100-120, lnorm in efso_tools.f90):
+ *     Inputs prepared as the reference does before das_efso (efso.f90:100-120, lnorm in efso_tools.f90; fcst and fcer
+ *     by letkf_efso_norm_dev, section 13):
  *       fcst   C^1/2 X^f_t, the normed forecast perturbations, element (p, m, v) at p*sp + m*sm + v*sv
  *       fcer   C^1/2 (e^f + e^g) / (2 (K-1)), element (p, v) at p*fsp + v*fsv
  *       ensval Y^a = H X^a, the analysis ensemble's perturbations in observation space, row j member-fastest
@@ -904,13 +905,90 @@ int letkf_obs_target_var(int32_t elm);
  *     set); none per run.
  *
  *     Out of scope: a column-cooperative search for advected positions (levels move by different amounts, so a column's
- *     union of search windows is no longer one horizontal pass), and the energy norm (the host's, as section 10).
+ *     union of search windows is no longer one horizontal pass).  The energy norm is letkf_efso_norm_dev (section 13).
  *-------------------------------------------------------------------------*/
 int letkf_efso_locadv_dev(letkf_ctx *ctx, int64_t nij1, int32_t nlev, const double *rig, const double *rjg, const double *u0,
                           const double *v0, const double *u1, const double *v1, double locadv_rate, double eft, double dx,
                           double dy, double *ri, double *rj);
 int letkf_efso_search_dev(letkf_ctx *ctx, const letkf_efso_args *args, const letkf_search_tables *tables, int64_t npts,
                           const double *ri, const double *rj, const double *rlev, const double *rz, int64_t list_bytes);
+
+/*---------------------------------------------------------------------------
+ * (13, joined at ABI 11: additive entries, the version number is unchanged) The two ends of EFSO around section 10:
+ *     the forecast-error norm before das_efso and the impact table after it (scale/letkf/efso.f90).
+ *
+ *     letkf_efso_norm_dev -- the fcer assembly of efso.f90:100-117 and lnorm (scale/letkf/efso_tools.f90:52-156) in
+ *     SCALE's frame.  Points p = ij + nij1*lev (npts = nij1*nlev), levels bottom first as gues3d.
+ *       fcst   dev INOUT, element (p, m, v) at p*sp + m*sm + v*sv (section 2's layout): in, the total fields of the members
+ *              0..k-1; out, C^1/2 X^f, the normed perturbations.
+ *       fmean  dev OUT [npts*nv] (element (p, v) at p + npts*v) or NULL: the forecast mean.  Given, every variable of
+ *              every point is read; NULL, variables and points whose output is zero are written without being read.
+ *       fcer   dev INOUT, element (p, v) at p*fsp + v*fsv: out, C^1/2 times the forecast error.  With xf, xg and xa
+ *              (dev, fcer's strides; all three or none) the error is first assembled as
+ *                fcer = (0.5 * (xf + xg) - xa) / (k - 1)
+ *              from the mean forecasts from the analysis (xf) and from the guess (xg) and the verifying analysis (xa),
+ *              i.e. [(e^f + e^g) / 2] / (K - 1); without them fcer holds that error on entry.
+ *     The steps, each one IEEE operation at a time in this order (lnorm's):
+ *       1. mean(p, v) = (sum over m = 0..k-1, from 0, in order, of fcst(p, m, v)) * (1.0 / k); perturbation x - mean.
+ *       2. layer weight sw(p) = sqrt(dp/ps(p)) * wg1[ij] (wg1 dev [nij1], the per-column area weight -- SCALE's map
+ *          factors --, NULL = 1).  dp/ps = wlev[p] (dev [npts]) when given; else from the mean pressure pb_l of variable
+ *          iv_p in the column, l = 1..L bottom first (L = nlev):
+ *            p_{1/2}   = pb_1 + 0.5 * (pb_1 - pb_2)
+ *            p_{l+1/2} = 0.5 * (pb_l + pb_{l+1}),                  1 <= l < L
+ *            p_{L+1/2} = max(0, pb_L - 0.5 * (pb_{L-1} - pb_L))
+ *            dp_l = p_{l-1/2} - p_{l+1/2},  ps = p_{1/2},  dp/ps = dp_l / ps;   L = 1: dp/ps = 1
+ *          (the reference takes dp from GFS's sigma coordinates, sigio_modprd; SCALE has none).  On this path a column
+ *          with dp <= 0, ps <= 0 or a value that is not finite at any level is counted on the device, the count is
+ *          read back once (the one synchronisation) and any such column gives LETKF_E_INVALID with no output written.
+ *       3. factor: U, V (iv_u, iv_v): sw;  T (iv_t): sqrt(cp/tref) * sw;  QV (iv_q, the first moisture slot, as lnorm
+ *          uses iv3d_q alone): (sqrt(wmoist/(cp*tref)) * hvap) * sw;  every other variable: 0 (checked in this order,
+ *          the constants evaluated once on the host).  fcst = factor * perturbation, fcer = factor * fcer.
+ *       4. target region: levels outside tar_minlev..tar_maxlev (1-based, inclusive) and columns with lon < tar_minlon,
+ *          lon > tar_maxlon, lat < tar_minlat or lat > tar_maxlat (lon, lat dev [nij1], both NULL = no horizontal box)
+ *          are 0 in every member and variable.
+ *       5. no ps term: SCALE's build has nv2d = 0, so lnorm's surface-pressure branch has nothing to act on.
+ *     Zeros are written as +0.0.  The host supplies cp, tref, hvap and wmoist (SCALE's CONST_CPdry, the reference's
+ *     tref = 280 K, CONST_LHV; wmoist = 0 gives the dry norm).  No multiply-add fusion and no floating-point atomics:
+ *     with correctly rounded / and sqrt the outputs are those of the formulas evaluated in numpy, bit for bit, and two
+ *     identical calls give identical bits.  LETKF_E_INVALID also for ctx / prm / fcst / fcer NULL, nij1 < 1, nlev < 1,
+ *     k < 2, nv outside 1..32, iv_u / iv_v / iv_t / iv_q outside 0..nv-1, iv_p outside it when wlev is NULL,
+ *     tar_minlev > tar_maxlev, only some of xf / xg / xa or one of lon / lat given, cp or tref not finite and > 0,
+ *     wmoist not finite and >= 0, or hvap not finite; nothing is written then.
+ *
+ *     letkf_efso_summary_dev -- print_obsense's table (efso_tools.f90:232-253) for every term.  obsense dev [nobs][nterm]
+ *     (section 10's layout); elm, typ (int32, NINT of obs%elm / obs%typ), lat (double) dev [nobs]; qc dev [nobs] or NULL
+ *     (rows with qc != 0 are skipped); elem_uid HOST [nid] (1..32 element ids, as letkf_monit_dep_dev; a row's element
+ *     is its first match).  A row is skipped when its element is not in the table or typ is outside 1..nobtype+1
+ *     (nobtype + 1 = "OTHERS").  Regions: NH (0) if lat > latbound, SH (2) if lat < -latbound, TR (1) otherwise (the
+ *     reference's latbound = 20).  Outputs, dev, every element written:
+ *       count [3][nobtype+1][nid]          int32, rows per bin
+ *       sum   [nterm][3][nobtype+1][nid]   double, the impacts of the bin's rows added from 0 in ascending row order
+ *       nneg  [nterm][3][nobtype+1][nid]   int32, rows of the bin with obsense < 0 (the reference's "rate" numerator)
+ *     i.e. bin (region r, type o = typ - 1, element u) at (r*(nobtype+1) + o)*nid + u, the reference's
+ *     nobs_sense(oid, otype, ireg) in C order; the reference prints term 0 (KE) only.  The sums have the bits of the
+ *     reference's sequential loop (a stable radix sort of the rows by bin, then one sequential sum per bin; no atomics).
+ *     LETKF_E_INVALID: nterm outside 1..4, nobs outside 0..2^31-1, nid outside 1..32, nobtype outside 1..4096, latbound
+ *     not finite, elem_uid / an output NULL, or obsense / elm / typ / lat NULL with nobs > 0.  No synchronisation.
+ *-------------------------------------------------------------------------*/
+typedef struct {
+  int32_t k;                 /* MEMBER (nbv), >= 2 */
+  int32_t nv;                /* variables of fcst / fcer, 1..32 */
+  int32_t iv_u, iv_v, iv_t, iv_q; /* 0-based slots of U, V, T and QV */
+  int32_t iv_p;              /* 0-based slot of the pressure (dp/ps from its mean when wlev is NULL) */
+  int32_t tar_minlev, tar_maxlev; /* target levels, 1-based inclusive (the reference's defaults: 1, 64) */
+  double cp;                 /* specific heat of dry air at constant pressure, J/(kg K) */
+  double tref;               /* reference temperature, K (the reference's 280) */
+  double hvap;               /* latent heat of vaporisation, J/kg */
+  double wmoist;             /* weight of the moist term (0 = dry norm) */
+  double tar_minlon, tar_maxlon, tar_minlat, tar_maxlat; /* horizontal box, in lon / lat's units */
+} letkf_efso_norm_params;
+int letkf_efso_norm_dev(letkf_ctx *ctx, const letkf_efso_norm_params *prm, int64_t nij1, int32_t nlev, double *fcst,
+                        int64_t sp, int64_t sm, int64_t sv, double *fmean, double *fcer, int64_t fsp, int64_t fsv,
+                        const double *xf, const double *xg, const double *xa, const double *wlev, const double *wg1,
+                        const double *lon, const double *lat);
+int letkf_efso_summary_dev(letkf_ctx *ctx, int32_t nterm, int64_t nobs, const double *obsense, const int32_t *elm,
+                           const int32_t *typ, const double *lat, const int32_t *qc, int32_t nid, const int32_t *elem_uid,
+                           int32_t nobtype, double latbound, int32_t *count, double *sum, int32_t *nneg);
 
 /* Name(s) of the kernel(s) the context's last letkf_das_points*_dev / letkf_core_batch_dev / letkf_efso_*_dev call went
  * through, as a NUL-terminated string (truncated to len): what bench.py reports as roofline.kernel. */

@@ -67,6 +67,15 @@ class EfsoArgs(C.Structure):
                 ("pair_bytes", C.c_int64)]
 
 
+class EfsoNormParams(C.Structure):
+    """letkf_efso_norm_params (include/letkf_amd.h section 13)"""
+    _fields_ = [("k", C.c_int32), ("nv", C.c_int32), ("iv_u", C.c_int32), ("iv_v", C.c_int32), ("iv_t", C.c_int32),
+                ("iv_q", C.c_int32), ("iv_p", C.c_int32), ("tar_minlev", C.c_int32), ("tar_maxlev", C.c_int32),
+                ("cp", C.c_double), ("tref", C.c_double), ("hvap", C.c_double), ("wmoist", C.c_double),
+                ("tar_minlon", C.c_double), ("tar_maxlon", C.c_double), ("tar_minlat", C.c_double),
+                ("tar_maxlat", C.c_double)]
+
+
 class DasObsArgs(C.Structure):
     """letkf_das_obs_args (include/letkf_amd.h section 11)"""
     _fields_ = [("k", C.c_int32), ("det_run", C.c_int32), ("tvar", C.c_int32), ("relax_to_inflated_prior", C.c_int32),
@@ -309,6 +318,7 @@ EXPORTS = ["letkf_amd_abi_version", "letkf_amd_last_error", "letkf_ctx_create", 
            "letkf_obs_table_info_get", "letkf_obs_table_search", "letkf_obs_table_set_varloc", "letkf_obs_table_download",
            "letkf_obs_table_destroy", "letkf_efso_points_dev", "letkf_efso_columns_dev", "letkf_efso_obsense_dev",
            "letkf_das_obs_dev", "letkf_obs_target_var", "letkf_efso_locadv_dev", "letkf_efso_search_dev",
+           "letkf_efso_norm_dev", "letkf_efso_summary_dev",
            "letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path", "letkf_sched_plan_check", "letkf_sched_plan_check_units"]
 
 # ctypes signatures of the entries that are called with them (include/letkf_amd.h; pointers as void *)
@@ -316,6 +326,9 @@ _VP, _I32, _I64, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 ARGTYPES = {
     "letkf_efso_locadv_dev": [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _F64, _F64, _F64, _F64, _VP, _VP],
     "letkf_efso_search_dev": [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64],
+    "letkf_efso_norm_dev": [_VP, _VP, _I64, _I32, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP,
+                            _VP],
+    "letkf_efso_summary_dev": [_VP, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _I32, _F64, _VP, _VP, _VP],
 }
 
 _lib = None
@@ -568,6 +581,34 @@ class Context:
                                   var_mask)
         self._check(self._l.letkf_efso_search_dev(self._c, C.byref(a), C.byref(tables), n if npts is None else npts, _ptr(ri),
                                                   _ptr(rj), _ptr(rlev), _ptr(rz), int(list_bytes)))
+
+    # ---- (13) EFSO's forecast-error norm and impact summary
+    def efso_norm(self, prm, nij1, nlev, fcst, sp, sm, sv, fcer, fsp, fsv, fmean=None, xf=None, xg=None, xa=None, wlev=None,
+                  wg1=None, lon=None, lat=None):
+        """letkf_efso_norm_dev: fcst (total fields in, C^1/2 X^f out) and fcer (C^1/2 times the error, assembled from xf, xg,
+        xa when given) in place; prm an EfsoNormParams; fmean [npts*nv] written when given."""
+        self._check(self._l.letkf_efso_norm_dev(self._c, C.byref(prm), nij1, nlev, _ptr(fcst), sp, sm, sv, _ptr(fmean),
+                                                _ptr(fcer), fsp, fsv, _ptr(xf), _ptr(xg), _ptr(xa), _ptr(wlev), _ptr(wg1),
+                                                _ptr(lon), _ptr(lat)))
+
+    def efso_summary(self, nterm, obsense, elm, typ, lat, elem_uid, nobtype, latbound=20.0, qc=None, nobs=None, outs=None):
+        """letkf_efso_summary_dev: print_obsense's table; returns (count int32 [3][nobtype+1][nid], sum [nterm][3][nobtype+1][nid],
+        nneg int32, same shape) device tensors (outs: the three to write instead)."""
+        import numpy as np
+        import torch
+        ids = np.ascontiguousarray(elem_uid, dtype=np.int32)
+        nid = len(ids)
+        n = (obsense.numel() // nterm if obsense is not None else 0) if nobs is None else nobs
+        if outs is None:
+            d = obsense.device if obsense is not None else torch.device("cuda")
+            shape = (3, nobtype + 1, max(nid, 1))
+            outs = (torch.empty(shape, dtype=torch.int32, device=d), torch.empty((nterm,) + shape, dtype=torch.float64, device=d),
+                    torch.empty((nterm,) + shape, dtype=torch.int32, device=d))
+        count, ssum, nneg = outs
+        self._check(self._l.letkf_efso_summary_dev(self._c, nterm, n, _ptr(obsense), _ptr(elm), _ptr(typ), _ptr(lat), _ptr(qc),
+                                                   nid, ids.ctypes.data_as(C.c_void_p) if nid else None, nobtype,
+                                                   float(latbound), _ptr(count), _ptr(ssum), _ptr(nneg)))
+        return count, ssum, nneg
 
     # ---- (11) das_letkf_obs: the analysis ensemble in observation space
     def das_obs(self, k, tvar, tables, ensval, kld, dep, nobs, ya, lda=None, tgt_row=None, ntgt=None, ya_mean=None,

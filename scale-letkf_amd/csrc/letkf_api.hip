@@ -1131,6 +1131,106 @@ int letkf_efso_search_dev(letkf_ctx* c, const letkf_efso_args* g, const letkf_se
   return LETKF_OK;
 }
 
+// (13) EFSO's front end: the fcer assembly (efso.f90:100-117) and lnorm (efso_tools.f90:52-156) in SCALE's frame
+int letkf_efso_norm_dev(letkf_ctx* c, const letkf_efso_norm_params* prm, int64_t nij1, int32_t nlev, double* fcst, int64_t sp,
+                        int64_t sm, int64_t sv, double* fmean, double* fcer, int64_t fsp, int64_t fsv, const double* xf,
+                        const double* xg, const double* xa, const double* wlev, const double* wg1, const double* lon,
+                        const double* lat) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!prm || !fcst || !fcer) return fail(LETKF_E_INVALID, "prm, fcst and fcer must not be NULL");
+  const letkf_efso_norm_params& q = *prm;
+  if (nij1 < 1 || nlev < 1) return fail(LETKF_E_INVALID, "nij1 and nlev must be >= 1");
+  if (q.k < 2) return fail(LETKF_E_INVALID, "k must be >= 2");
+  if (q.nv < 1 || q.nv > 32) return fail(LETKF_E_INVALID, "nv must lie in 1..32");
+  auto slot = [&](int32_t i) { return i >= 0 && i < q.nv; };
+  if (!slot(q.iv_u) || !slot(q.iv_v) || !slot(q.iv_t) || !slot(q.iv_q))
+    return fail(LETKF_E_INVALID, "iv_u, iv_v, iv_t and iv_q must lie in 0..nv-1");
+  if (!wlev && !slot(q.iv_p)) return fail(LETKF_E_INVALID, "iv_p must lie in 0..nv-1 when wlev is NULL");
+  if (q.tar_minlev > q.tar_maxlev) return fail(LETKF_E_INVALID, "tar_minlev > tar_maxlev");
+  if ((xf != nullptr) != (xg != nullptr) || (xf != nullptr) != (xa != nullptr))
+    return fail(LETKF_E_INVALID, "xf, xg and xa: all three or none");
+  if ((lon != nullptr) != (lat != nullptr)) return fail(LETKF_E_INVALID, "lon and lat: both or none");
+  if (!(std::isfinite(q.cp) && q.cp > 0.0) || !(std::isfinite(q.tref) && q.tref > 0.0))
+    return fail(LETKF_E_INVALID, "cp and tref must be finite and > 0");
+  if (!(std::isfinite(q.wmoist) && q.wmoist >= 0.0) || !std::isfinite(q.hvap))
+    return fail(LETKF_E_INVALID, "wmoist must be finite and >= 0, hvap finite");
+  letkf::EfsoNormArgs a{};
+  a.k = q.k;
+  a.nv = q.nv;
+  a.nij1 = nij1;
+  a.npts = nij1 * nlev;
+  a.lev0 = (long)q.tar_minlev - 1;
+  a.lev1 = (long)q.tar_maxlev - 1;
+  for (int v = 0; v < q.nv; ++v)    // lnorm's IF / ELSE IF order
+    a.cls[v] = (v == q.iv_u || v == q.iv_v) ? 1 : v == q.iv_t ? 2 : v == q.iv_q ? 3 : 0;
+  a.rinbv = 1.0 / (double)q.k;
+  a.cptr = std::sqrt(q.cp / q.tref);
+  a.qweight = std::sqrt(q.wmoist / (q.cp * q.tref)) * q.hvap;
+  a.km1 = (double)(q.k - 1);
+  a.minlon = q.tar_minlon;
+  a.maxlon = q.tar_maxlon;
+  a.minlat = q.tar_minlat;
+  a.maxlat = q.tar_maxlat;
+  a.fcst = fcst;
+  a.sp = sp;
+  a.sm = sm;
+  a.sv = sv;
+  a.fmean = fmean;
+  a.fcer = fcer;
+  a.fsp = fsp;
+  a.fsv = fsv;
+  a.xf = xf;
+  a.xg = xg;
+  a.xa = xa;
+  a.wg1 = wg1;
+  a.lon = lon;
+  a.lat = lat;
+  a.wl = wlev;
+  c->last_path = letkf::efso_norm_path_name(q.k);
+  if (!wlev) {
+    // dp/ps from the mean pressure; the bad-column count read back before any output is written
+    const size_t nb = ((size_t)a.npts * 8 + 255) & ~(size_t)255;
+    if (int rc = grow(c, &c->scratch, &c->scratch_bytes, 2 * nb + 256)) return rc;
+    double* pbar = reinterpret_cast<double*>(c->scratch);
+    double* w = reinterpret_cast<double*>(c->scratch + nb);
+    unsigned* bad = reinterpret_cast<unsigned*>(c->scratch + 2 * nb);
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, c->stream));
+    HIP_TRY(letkf::launch_efso_dpw(nij1, nlev, q.k, fcst + q.iv_p * sv, sp, sm, a.rinbv, pbar, w, bad, c->num_cu, c->stream));
+    unsigned nbad = 0;
+    HIP_TRY(hipMemcpyAsync(&nbad, bad, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_path = std::string("efso_pmean_kernel + efso_dpw_kernel + ") + c->last_path;
+    if (nbad)
+      return fail(LETKF_E_INVALID, std::to_string(nbad) + " column(s) with dp <= 0, ps <= 0 or a non-finite mean pressure");
+    a.wl = w;
+  }
+  HIP_TRY(letkf::launch_efso_norm(a, c->num_cu, c->stream));
+  return LETKF_OK;
+}
+
+// (13) EFSO's back end: print_obsense's table (efso_tools.f90:232-253) for every term
+int letkf_efso_summary_dev(letkf_ctx* c, int32_t nterm, int64_t nobs, const double* obsense, const int32_t* elm,
+                           const int32_t* typ, const double* lat, const int32_t* qc, int32_t nid, const int32_t* elem_uid,
+                           int32_t nobtype, double latbound, int32_t* count, double* sum, int32_t* nneg) {
+  if (int rc = check_ctx(c)) return rc;
+  if (nterm < 1 || nterm > 4) return fail(LETKF_E_INVALID, "nterm must lie in 1..4");
+  if (nobs < 0 || nobs > 0x7fffffffLL) return fail(LETKF_E_INVALID, "nobs must lie in 0..2^31-1");
+  if (nid < 1 || nid > 32 || !elem_uid) return fail(LETKF_E_INVALID, "bad element table (nid 1..32, elem_uid)");
+  if (nobtype < 1 || nobtype > 4096) return fail(LETKF_E_INVALID, "nobtype must lie in 1..4096");
+  if (!std::isfinite(latbound)) return fail(LETKF_E_INVALID, "latbound must be finite");
+  if (!count || !sum || !nneg) return fail(LETKF_E_INVALID, "an output (count, sum, nneg) is NULL");
+  if (nobs > 0 && (!obsense || !elm || !typ || !lat)) return fail(LETKF_E_INVALID, "obsense, elm, typ or lat is NULL");
+  const unsigned nbins = 3u * (unsigned)(nobtype + 1) * (unsigned)nid;
+  size_t sort_b = 0, scan_b = 0;
+  const size_t need = letkf::efso_summary_ws(nobs, nbins, c->stream, &sort_b, &scan_b);
+  if (!need) return fail(LETKF_E_HIP, "rocprim workspace query failed");
+  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
+  HIP_TRY(letkf::launch_efso_summary(nterm, nobs, obsense, elm, typ, lat, qc, nid, elem_uid, nobtype, latbound, count, sum,
+                                     nneg, c->scratch, sort_b, scan_b, c->num_cu, c->stream));
+  c->last_path = "efso_bin_kernel + rocprim radix_sort_pairs + efso_binsum_kernel";
+  return LETKF_OK;
+}
+
 // (11) das_letkf_obs (scale/letkf/letkf_tools.f90:933-1156): the loop body at every target observation's own location, on
 // the two-variable pseudo-state of letkf_obsanal.hip (variable 0 the target, variable 1 its pressure for Q_UPDATE_TOP), in
 // chunks of targets whose lists fit list_bytes

@@ -329,6 +329,33 @@ constexpr double kLocAdvMaxCells = 1048576.0;   // 2^20
 hipError_t launch_efso_locadv(long nij1, long npts, const double* rig, const double* rjg, const double* u0, const double* v0,
                               const double* u1, const double* v1, double ci, double cj, double* ri, double* rj,
                               unsigned* bad, int num_cu, hipStream_t st);
+// EFSO's forecast-error norm and impact summary (letkf_efsonorm.hip)
+struct EfsoNormArgs {
+  int k, nv;
+  long nij1, npts, lev0, lev1;        // target levels lev0..lev1, 0-based inclusive
+  unsigned char cls[32];              // per variable: 0 = zero, 1 = U/V, 2 = T, 3 = QV
+  double rinbv, cptr, qweight, km1;   // 1/k, sqrt(cp/tref), sqrt(wmoist/(cp*tref))*hvap, k-1 (host)
+  double minlon, maxlon, minlat, maxlat;
+  double* fcst;
+  long sp, sm, sv;
+  double* fmean;                      // (p, v) at p + npts*v, or NULL
+  double* fcer;
+  long fsp, fsv;
+  const double *xf, *xg, *xa;         // fcer's strides, all NULL or all given
+  const double* wl;                   // dp/ps [npts]
+  const double *wg1, *lon, *lat;      // [nij1] or NULL
+};
+// the mean pressure (fcst_p: variable iv_p's slot) into pbar [npts], then dp/ps into w [npts]; *bad += bad columns
+hipError_t launch_efso_dpw(long nij1, int nlev, int k, const double* fcst_p, long sp, long sm, double rinbv, double* pbar,
+                           double* w, unsigned* bad, int num_cu, hipStream_t st);
+hipError_t launch_efso_norm(const EfsoNormArgs& a, int num_cu, hipStream_t st);
+const char* efso_norm_path_name(int k);
+// print_obsense's table; ws of efso_summary_ws bytes (0: a rocprim size query failed)
+size_t efso_summary_ws(long nobs, unsigned nbins, hipStream_t st, size_t* sort_bytes, size_t* scan_bytes);
+hipError_t launch_efso_summary(int nterm, long nobs, const double* obsense, const int* elm, const int* typ, const double* lat,
+                               const int* qc, int nid, const int* elem_uid, int nobtype, double latbound, int* count,
+                               double* sum, int* nneg, char* ws, size_t sort_bytes, size_t scan_bytes, int num_cu,
+                               hipStream_t st);
 
 // das_letkf_obs (letkf_obsanal.hip): the targets kernel builds the pseudo-state of one point per target, the finish kernel
 // turns the loop body's analysis of it into the obs-space outputs.  Flag bits the targets kernel ORs into *flags:

@@ -42,6 +42,19 @@ MODULE letkf_amd_api
     INTEGER(c_int64_t) :: pair_bytes
   END TYPE letkf_efso_args
 
+  ! include/letkf_amd.h section 13: EFSO's forecast-error norm (lnorm, scale/letkf/efso_tools.f90:52-156)
+  TYPE, BIND(C) :: letkf_efso_norm_params
+    INTEGER(c_int32_t) :: k, nv
+    INTEGER(c_int32_t) :: iv_u, iv_v, iv_t, iv_q
+    INTEGER(c_int32_t) :: iv_p
+    INTEGER(c_int32_t) :: tar_minlev, tar_maxlev
+    REAL(c_double)     :: cp
+    REAL(c_double)     :: tref
+    REAL(c_double)     :: hvap
+    REAL(c_double)     :: wmoist
+    REAL(c_double)     :: tar_minlon, tar_maxlon, tar_minlat, tar_maxlat
+  END TYPE letkf_efso_norm_params
+
   ! include/letkf_amd.h section 11: the analysis ensemble in observation space (das_letkf_obs, letkf_tools.f90:933-1156)
   TYPE, BIND(C) :: letkf_das_obs_args
     INTEGER(c_int32_t) :: k, det_run, tvar, relax_to_inflated_prior
@@ -371,6 +384,25 @@ MODULE letkf_amd_api
       TYPE(letkf_efso_args), INTENT(IN) :: args
       TYPE(letkf_search_tables), INTENT(IN) :: tables
       INTEGER(c_int64_t), VALUE :: npts, list_bytes
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    ! ---- section 13: EFSO's forecast-error norm and impact summary (print_obsense's table)
+    FUNCTION letkf_efso_norm_dev(ctx, prm, nij1, nlev, fcst, sp, sm, sv, fmean, fcer, fsp, fsv, xf, xg, xa, wlev, wg1, lon, lat) &
+        BIND(C, name='letkf_efso_norm_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int32_t, c_int64_t, letkf_efso_norm_params
+      TYPE(c_ptr), VALUE :: ctx, fcst, fmean, fcer, xf, xg, xa, wlev, wg1, lon, lat
+      TYPE(letkf_efso_norm_params), INTENT(IN) :: prm
+      INTEGER(c_int64_t), VALUE :: nij1, sp, sm, sv, fsp, fsv
+      INTEGER(c_int32_t), VALUE :: nlev
+      INTEGER(c_int) :: rc
+    END FUNCTION
+    FUNCTION letkf_efso_summary_dev(ctx, nterm, nobs, obsense, elm, typ, lat, qc, nid, elem_uid, nobtype, latbound, count, &
+                                    sum, nneg) BIND(C, name='letkf_efso_summary_dev') RESULT(rc)
+      IMPORT :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+      TYPE(c_ptr), VALUE :: ctx, obsense, elm, typ, lat, qc, elem_uid, count, sum, nneg
+      INTEGER(c_int32_t), VALUE :: nterm, nid, nobtype
+      INTEGER(c_int64_t), VALUE :: nobs
+      REAL(c_double), VALUE :: latbound
       INTEGER(c_int) :: rc
     END FUNCTION
     ! ---- section 11: das_letkf_obs on the device, and the reference's element -> grid variable map (0-based, -1 none)
