@@ -707,19 +707,25 @@ struct SurvivorView {
   int64_t pt_stride, pt0;
   int64_t cap;               // most survivors of a column of the batch (bounds a point's local list)
 };
+// the loop body's own argument checks (npts > 0); letkf_das_columns_dev runs them before its search writes anything
+int das_args_check(const letkf_das_args* g, bool lists) {
+  if (g->k < 2 || g->nv < 1 || g->npts < 0) return fail(LETKF_E_INVALID, "bad k/nv/npts");
+  if ((lists && !g->obs_off) || !g->gues || !g->anal || !g->infl)
+    return fail(LETKF_E_INVALID, "a required device pointer is NULL");
+  if (g->kld < g->k + (g->det_run ? 1 : 0)) return fail(LETKF_E_INVALID, "kld too small for k (+1 with det_run)");
+  if (g->iv_p < 0 || g->iv_p >= g->nv) {
+    if (g->q_update_top > 0.0) return fail(LETKF_E_INVALID, "iv_p out of range");
+  }
+  return LETKF_OK;
+}
+
 int das_points_impl(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const double* ri,
                     const double* rj, const double* rlev, const double* rz, int32_t* nobs_out,
                     const SurvivorView* sview = nullptr) {
   if (int rc = check_ctx(c)) return rc;
   if (!g) return fail(LETKF_E_INVALID, "args is NULL");
   if (g->npts == 0) return LETKF_OK;
-  if (g->k < 2 || g->nv < 1 || g->npts < 0) return fail(LETKF_E_INVALID, "bad k/nv/npts");
-  if ((!t && !g->obs_off) || !g->gues || !g->anal || !g->infl)
-    return fail(LETKF_E_INVALID, "a required device pointer is NULL");
-  if (g->kld < g->k + (g->det_run ? 1 : 0)) return fail(LETKF_E_INVALID, "kld too small for k (+1 with det_run)");
-  if (g->iv_p < 0 || g->iv_p >= g->nv) {
-    if (g->q_update_top > 0.0) return fail(LETKF_E_INVALID, "iv_p out of range");
-  }
+  if (int rc = das_args_check(g, !t)) return rc;
   letkf::PointArgs a;
   std::memset(&a, 0, sizeof(a));
   a.k = g->k;
@@ -815,6 +821,8 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
   if (nij1 < 1 || nlev < 1 || g->npts != nij1 * (int64_t)nlev) return fail(LETKF_E_INVALID, "npts must be nij1 * nlev");
   if (!rig || !rjg || !rlev || !rz) return fail(LETKF_E_INVALID, "a point coordinate array is NULL");
   if (g->trans_out || g->transm_out || g->pa_out) return fail(LETKF_E_INVALID, "per-point k x k / w-bar outputs: use letkf_das_points_dev");
+  // (the loop body's checks, before the count pass of the list route copies its counts to nobs_out: a refused call writes nothing)
+  if (int rc = das_args_check(g, false)) return rc;
   const int64_t npts = g->npts;
   if (list_bytes <= 0) list_bytes = (int64_t)8 << 30;
   // ---- the list-free route: where the one-wave kernel serves the call and no combined type has a limit, the horizontal half of

@@ -3,7 +3,8 @@
 ! calls das_letkf: fills the two derived types from a case file written by tests/test_fortran_das.py (what the
 ! reference's modules would hold after set_letkf_obs and read_ens_mpi), calls the routine, writes anal3d, the
 ! perturbations gues3d comes back as, the inflation field and the local-observation counts.
-!   file (little endian, stream): int32 hdr(19); real64 r(13); then the arrays in the order read below
+!   file (little endian, stream): int32 hdr(19); real64 r(13); then the arrays in the order read below; optionally one
+!   int64 record at the end: nml%list_bytes (absent: 0, the library's default; files without it read as before)
 !===============================================================================
 PROGRAM das_letkf_driver
   USE, INTRINSIC :: iso_c_binding
@@ -11,6 +12,7 @@ PROGRAM das_letkf_driver
   USE letkf_tools_amd
   IMPLICIT NONE
   INTEGER(c_int32_t) :: hdr(19)
+  INTEGER(c_int64_t) :: list_bytes
   REAL(c_double) :: r(13)
   INTEGER :: member, det, nij1, nlev, nv3d, nctype, nobstotal, nensobs, nens, relax, nid_obs, nobtype, nac, u, ios
   TYPE(letkf_das_nml) :: nml
@@ -66,6 +68,8 @@ PROGRAM das_letkf_driver
             work3d(nij1, nlev, nv3d), nobs_point(nij1, nlev))
   READ (u) rig1, rjg1, hgt1
   READ (u) gues3d
+  READ (u, iostat=ios) list_bytes
+  IF (ios == 0) nml%list_bytes = list_bytes
   CLOSE (u)
 
   IF (letkf_amd_abi_version() < 5) STOP 4

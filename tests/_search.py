@@ -27,10 +27,11 @@ ARRAY_FIELDS = ["group_start", "group_member", "vmode", "hori_loc", "vert_loc", 
 
 
 def build_case(seed, nlon=40, nlat=32, dx=1000.0, nobs_per_ctype=(900, 500, 400, 300), max_nobs=(0, 0, 0, 0),
-               criterion=1, ihalo=2, npts=160):
+               criterion=1, ihalo=2, npts=160, obs_east_of=None):
     """4 combined obs types: 0 radar reflectivity and 1 radar zero-reflectivity (type 22, z localisation, merged into
     one group like letkf_tools.f90:167-192), 2 upper-air T (ln p), 3 surface pressure (ps value as vertical
-    coordinate, larger horizontal scale)."""
+    coordinate, larger horizontal scale).  obs_east_of: the observations lie east of ri = i_org + obs_east_of only (columns
+    west of every cut-off have no horizontal survivors)."""
     rng = np.random.default_rng(seed)
     nctype = 4
     vmode = np.array([1, 1, 0, 2], dtype=np.int32)
@@ -64,7 +65,7 @@ def build_case(seed, nlon=40, nlat=32, dx=1000.0, nobs_per_ctype=(900, 500, 400,
         # obs also live in the halo of the extended subdomain
         ext_i = nsch_i[ic] * nlon / ngrd_i[ic]
         ext_j = nsch_j[ic] * nlat / ngrd_j[ic]
-        ri = i_org + rng.uniform(-0.95 * ext_i, nlon + 0.95 * ext_i, n)
+        ri = i_org + rng.uniform(-0.95 * ext_i if obs_east_of is None else obs_east_of, nlon + 0.95 * ext_i, n)
         rj = j_org + rng.uniform(-0.95 * ext_j, nlat + 0.95 * ext_j, n)
         lev = rng.uniform(0.0, 12000.0, n) if vmode[ic] == 1 else rng.uniform(2.0e4, 1.0e5, n)
         dat = rng.uniform(9.0e4, 1.03e5, n)

@@ -110,6 +110,20 @@ class OrcBeta(C.Structure):
 @pytest.mark.skipif(not HAVE_FC, reason="amdflang not present")
 @pytest.mark.parametrize("k,det,relax,alpha,bw", [(20, 0, 2, 0.9, 0.0), (50, 1, 1, 0.6, 3000.0)])
 def test_das_letkf_amd_from_fortran_matches_the_oracle(k, det, relax, alpha, bw):
+    run_das_letkf_amd(k, det, relax, alpha, bw, (12, 12, 0, 3), 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not HAVE_FC, reason="amdflang not present")
+def test_das_letkf_amd_on_the_list_free_route_matches_the_oracle():
+    """no MAX_NOBS_PER_GRID and a workspace (list_bytes) far smaller than the lists of all levels: every class's
+    letkf_das_columns_dev takes the list-free route (include/letkf_amd.h (3c), LETKF_OPT_COLUMN_SURVIVORS = 2) with its mask"""
+    run_das_letkf_amd(33, 1, 2, 0.9, 3000.0, (0, 0, 0, 0), 4096)
+
+
+def run_das_letkf_amd(k, det, relax, alpha, bw, limits, list_bytes):
+    """limits: MAX_NOBS_PER_GRID per combined type (with them every class's call takes the list route); list_bytes:
+    nml%list_bytes of the driver (0: the library's default)"""
     build_fortran()
     rng = np.random.default_rng(700 + k)
     nlon, nlat, nlev, nv, ihalo, dx = 12, 10, 4, 11, 2, 1000.0
@@ -117,8 +131,8 @@ def test_das_letkf_amd_from_fortran_matches_the_oracle(k, det, relax, alpha, bw)
     npts = nij1 * nlev
     nens = k + 1 + det
     # tables of set_letkf_obs: 4 combined types -- 0 radar reflectivity + 1 zero-reflectivity (type 22, merged, limited to
-    # 12 per grid point), 2 upper-air T, 3 surface pressure (limited to 3)
-    case = build_case(41 + k, nlon=nlon, nlat=nlat, dx=dx, nobs_per_ctype=(500, 300, 250, 120), max_nobs=(12, 12, 0, 3),
+    # 12 per grid point), 2 upper-air T, 3 surface pressure (limited to 3) -- or the same without limits
+    case = build_case(41 + k, nlon=nlon, nlat=nlat, dx=dx, nobs_per_ctype=(500, 300, 250, 120), max_nobs=limits,
                       criterion=1, ihalo=ihalo, npts=1)
     arr, scal = case["arr"], case["scal"]
     nctype, nobs = 4, case["nobs"]
@@ -212,6 +226,8 @@ def test_das_letkf_amd_from_fortran_matches_the_oracle(k, det, relax, alpha, bw)
             for a in (arr["hori_loc"], arr["vert_loc"], arr["ob_ri"], arr["ob_rj"], arr["ob_lev"], arr["ob_dat"], arr["ob_err"],
                       ens, val, rig, rjg, hgt, full_in):
                 w(a, "<f8")
+            if list_bytes:
+                f.write(struct.pack("<q", list_bytes))   # (the optional last record: nml%list_bytes)
         r = subprocess.run([DRIVER, fin, fout], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stdout + r.stderr
         raw = np.fromfile(fout, dtype="<f8", count=2 * nv * nens * npts + npts * nv)
