@@ -118,10 +118,34 @@ __device__ __forceinline__ double dpp_shift0(double v) {     // wave_shl:1 (0x13
   hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
 }
+// The same shift with bound_ctrl = 0: a lane whose source lane does not exist or is switched off KEEPS `old`
+// (tools/ubench_dpp.hip probes both halves of the rule on the device).
+template <int CTRL>
+__device__ __forceinline__ double dpp_shift_keep(double old, double v) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+// (the old value of a dpp_shift_keep that has to survive in its own register: one 64-bit move; left to itself hipcc copies
+// the two halves separately)
+__device__ __forceinline__ double copy64(double v) {
+  double t;
+  asm("v_mov_b64 %0, %1" : "=v"(t) : "v"(v));
+  return t;
+}
 // v[l & 31] + v[32 + (l & 31)] in every lane (both lanes of a slot must be active)
 __device__ __forceinline__ double slot_sum(double v) {
   const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
   const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
+  return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
+}
+
+// the same with the second operand of the swap made by ONE 64-bit move (hipcc copies the two halves separately: 3 instead of 4
+// instructions in front of the add); bit for bit slot_sum's value
+__device__ __forceinline__ double slot_sum_c64(double v) {
+  const double t = copy64(v);
+  const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(t), false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(t), false, false);
   return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
 }
 
@@ -131,7 +155,7 @@ __device__ __forceinline__ double slot_sum(double v) {
 template <int NW>
 __device__ __forceinline__ double slot_sum_nw(double v, double* xs, int& ph) {
   if constexpr (NW == 1) {
-    return slot_sum(v);
+    return slot_sum_c64(v);
   } else {
     const int t = threadIdx.x & 127;
     xs[ph * 128 + t] = v;
@@ -160,6 +184,14 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
   static_assert(KR % 2 == 0, "row halves");
   constexpr int H = KR / 2;
   static_assert(RC % 2 == 0, "RC rows per conversion chunk: RC * 64 NW doubles of LDS");
+  // ENDS: the two ends of the line (slot 0 has no left partner, slot S-1 no right one) keep their norms and scales in the
+  // odd step through DPP moves that leave their destination alone, instead of per-lane selects that every lane executes.
+  // That needs the lanes next to both ends switched off: one wave (unused slots sit out the iteration) and S <= 31, so
+  // that lane 31 -- the source of lane 32, the odd-row half of slot 0, under wave_shr:1 -- belongs to an unused slot.  The
+  // callers keep k <= 62 on one wave (launch_wave_kernel; the block Jacobi of letkf_kernels.hip has k = 32).  Two-wave
+  // points run every lane and keep the selects.
+  constexpr bool ENDS = NW == 1;
+  static_assert(!ENDS || KR <= 64, "one wave: k <= 62, lane 31 stays switched off");
   constexpr int NL = 64 * NW;
   int lane = threadIdx.x & (NL - 1);
   if constexpr (NW == 2) asm volatile("" : "+v"(lane));   // (two-wave points, see letkf_wave_kernel: nothing built from the lane number may be hoisted out of the caller's loop)
@@ -198,6 +230,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
     // branches inside the step pair)
     const unsigned long long hasRm = __builtin_amdgcn_ballot_w64(hasR);
     double alA = 0.0, alB = 0.0, isA = 1.0, isB = 1.0, scA = 1.0, scB = 1.0;
+    const double endR = hasR ? -0.0 : 1.0, endL = hasL ? -0.0 : 1.0;   // (ENDS) addends of the odd step's coefficients
     // `quiet` counts consecutive step pairs in which no visited column pair exceeded the tolerance; S of them in a
     // row are one full cycle of the ordering (every column pair seen once) whatever step it started at, so the
     // iteration stops S step pairs after the last significant rotation, not at the next sweep boundary.
@@ -316,7 +349,12 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
             else p0 = fma(xa[rr], xb[rr], p0);
           }
           }
-          const double alAr = dpp_shift0<0x130>(alA), isAr = dpp_shift0<0x130>(isA), scAr = dpp_shift0<0x130>(scA);
+          // (ENDS: the slot without a right partner reads its own B here.  Its `rot` is false, so tt = 0, c = wc = 1 and
+          // tg = 0 exactly, and the unconditional update below gives alB + 0, isB * 1, scB * 1: the old values bit for bit.
+          // Its h and g2 are both 0 and the tangent's intermediate is NaN, which the select on `rot` discards.)
+          const double alAr = ENDS ? dpp_shift_keep<0x130>(copy64(alB), alA) : dpp_shift0<0x130>(alA),
+                       isAr = ENDS ? dpp_shift_keep<0x130>(copy64(isB), isA) : dpp_shift0<0x130>(isA),
+                       scAr = ENDS ? dpp_shift_keep<0x130>(copy64(scB), scA) : dpp_shift0<0x130>(scA);
           const double ga = slot_sum_nw<NW>(p0 + p1, lds, ph) * (isB * isAr);
           const double a = alB, b = alAr;
           const double g2 = ga * ga, ab = a * b;
@@ -333,19 +371,34 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
           const double c = fast_rsqrt(w);
           const double tg = tt * ga, wc = w * c;
           // what the right slot needs to rotate its A against this slot's (old) B
-          const double q1 = dpp_shift0<0x138>(-tt * scB), q2 = dpp_shift0<0x138>(isB * c),
-                       q3 = dpp_shift0<0x138>(scB * wc), q4 = dpp_shift0<0x138>(a - tg);
-          const double coefR = hasR ? tt * (isB * scAr) : 1.0;   // position 2m+1 takes c (g_Ar + t g_B)
-          const double coefL = hasL ? q1 * isA : 1.0;            // position 2m takes c (g_Bl - t g_A)
-          if (hasR) {
+          const double q1 = dpp_shift0<0x138>(-tt * scB);
+          // position 2m+1 takes c (g_Ar + t g_B), position 2m takes c (g_Bl - t g_A); 1.0 where there is no partner.
+          // (ENDS: there tt and q1 are exactly 0 and the products' other factors finite, so the fused form gives exactly
+          // 1.0; everywhere else the addend -0.0 leaves the product as it is to the last bit, signed zeros included.)
+          const double coefR = ENDS ? fma(tt, isB * scAr, endR) : hasR ? tt * (isB * scAr) : 1.0;
+          const double coefL = ENDS ? fma(q1, isA, endL) : hasL ? q1 * isA : 1.0;
+          if constexpr (ENDS) {
+            // the left slot's values move straight into this slot's A; slot 0 has no source lane and keeps its own
+            const double nisA = dpp_shift_keep<0x138>(isA, isB * c), nscA = dpp_shift_keep<0x138>(scA, scB * wc),
+                         nalA = dpp_shift_keep<0x138>(alA, a - tg);
             alB = b + tg;
             isB = isAr * c;
             scB = scAr * wc;
-          }
-          if (hasL) {
-            alA = q4;
-            isA = q2;
-            scA = q3;
+            alA = nalA;
+            isA = nisA;
+            scA = nscA;
+          } else {
+            const double q2 = dpp_shift0<0x138>(isB * c), q3 = dpp_shift0<0x138>(scB * wc), q4 = dpp_shift0<0x138>(a - tg);
+            if (hasR) {
+              alB = b + tg;
+              isB = isAr * c;
+              scB = scAr * wc;
+            }
+            if (hasL) {
+              alA = q4;
+              isA = q2;
+              scA = q3;
+            }
           }
           // new B into xb[] (on top of the fetched column); then the old B of the LEFT slot is pulled into xa[] --
           // every lane reads its neighbour's xa[rr] and overwrites its own in the same instruction -- and the new A

@@ -531,6 +531,169 @@ __device__ __forceinline__ void warm_start_product_mfma(double (&g)[KR], const d
   wave_lds_sync();
 }
 
+// STRIP form of the product for KR = 50 (LETKF_WARM_STRIP, default on; -DLETKF_WARM_STRIP=0 gives the form above for an A/B).
+// Above, rows and columns are dealt to four interleaved blocks (4c + I) of which every one is 13/16 full: 13 steps x 16 tiles
+// = 208 matrix instructions for a 50 x 50 x 50 product.  Here the blocks are contiguous -- 0-15, 16-31, 32-47 -- and only their
+// nine full tiles go to the matrix cores (117 instructions); rows and columns 48, 49 of G0 are accumulated on the vector ALU
+// from the operands the tiles load anyway (the narrow block of the Gram, r4, applied to the product).  Per step, lane (q, c)
+// with i = 4s + q holds a[I] = A[16 I + c][i], ae[e] = A[48 + e][i], b[J] = Q[i][16 J + c], be[e] = Q[i][48 + e] and adds
+//   rs[e][J] += ae[e] b[J]   -> G0[48 + e][16 J + c]      cs[e][I] += a[I] be[e]   -> G0[16 I + c][48 + e]
+//   cn[e][f] += ae[e] be[f]  -> G0[48 + e][48 + f]
+// 16 FMAs against the 7 x 16 issue slots of the seven matrix instructions they replace; the partial sums over the four
+// residues q are folded once per point.  The operands are single 8-byte reads at fixed offsets from one address per lane (the
+// memory instructions are not what bounds the kernel: DESIGN 4.1); neither the layout of A in LDS nor that of Q in the
+// workspace slot changes.  Accumulator (I, J), register `reg` of lane (q, c) is G0[16 I + 4 reg + q][16 J + c].
+#ifndef LETKF_WARM_STRIP
+#define LETKF_WARM_STRIP 1
+#endif
+template <int KR>
+__device__ __forceinline__ void warm_start_product_strip(double (&g)[KR], const double* __restrict__ qslot, double* cb) {
+  constexpr int NBF = KR / 16;                 // full blocks (3)
+  constexpr int RS = KR - 16 * NBF;            // rows / columns of the narrow block (2)
+  static_assert(KR % 2 == 0 && KR <= 50 && RS == 2 && NBF == 3, "A must fit the LDS slice; the narrow block is a pair (16-byte reads); the pin below");
+  constexpr int KS = (KR + 3) / 4;             // contraction steps of 4
+  constexpr int PD = (KS < 6) ? KS : 6;        // workspace rows in flight
+  const int wlane = threadIdx.x & 63;
+  const int q = wlane >> 4, c = wlane & 15;
+  struct QOp {
+    double b[NBF];
+    double2 be;
+  };
+  struct AOp {
+    double a[NBF];
+    double2 ae;
+  };
+  unsigned long long qaddr = reinterpret_cast<unsigned long long>(qslot + q * 64 + c);
+  asm volatile("" : "+v"(qaddr));
+  const gdouble* qp = (const gdouble*)qaddr;   // integer -> global pointer: see warm_start_product_mfma
+  auto ldq = [&](const int s) {
+    QOp t;
+#pragma unroll
+    for (int J = 0; J < NBF; ++J) t.b[J] = 0.0;
+    t.be = double2{0.0, 0.0};
+    if (4 * s + 3 < KR || 4 * s + q < KR) {    // rows >= KR do not exist in the slot
+      const gdouble* a = qp + (size_t)s * 256;
+#pragma unroll
+      for (int J = 0; J < NBF; ++J) t.b[J] = a[16 * J];
+      const v2d_t e2 = *(const gdouble2*)(a + (16 * NBF - c));
+      t.be = double2{e2.x, e2.y};
+    }
+    return t;
+  };
+  auto lda = [&](const int s) {
+    AOp t;
+#pragma unroll
+    for (int I = 0; I < NBF; ++I) t.a[I] = 0.0;
+    t.ae = double2{0.0, 0.0};
+    if (4 * s + 3 < KR || 4 * s + q < KR) {
+      const double* a = cb + (4 * s + q) * KR;
+#pragma unroll
+      for (int I = 0; I < NBF; ++I) t.a[I] = a[16 * I + c];
+      t.ae = *reinterpret_cast<const double2*>(a + 16 * NBF);
+    }
+    return t;
+  };
+  QOp qr[PD];
+#pragma unroll
+  for (int s = 0; s < PD; ++s) qr[s] = ldq(s);
+  wave_lds_sync();
+  if (wlane < KR) {
+    double* mine = cb + wlane * KR;
+#pragma unroll
+    for (int r = 0; r < KR; r += 2) *reinterpret_cast<double2*>(&mine[r]) = double2{g[r], g[r + 1]};
+  }
+  wave_lds_sync();
+  v4d acc[NBF * NBF];
+#pragma unroll
+  for (int t = 0; t < NBF * NBF; ++t) acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
+  double rs[RS][NBF], cs[RS][NBF], cn[RS][RS];
+#pragma unroll
+  for (int e = 0; e < RS; ++e) {
+#pragma unroll
+    for (int I = 0; I < NBF; ++I) rs[e][I] = cs[e][I] = 0.0;
+#pragma unroll
+    for (int f = 0; f < RS; ++f) cn[e][f] = 0.0;
+  }
+  AOp ar[2];
+  ar[0] = lda(0);
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    if (s + 1 < KS) ar[(s + 1) & 1] = lda(s + 1);
+    const AOp a4 = ar[s & 1];
+    const QOp b4 = qr[s % PD];
+    const double ae[RS] = {a4.ae.x, a4.ae.y}, be[RS] = {b4.be.x, b4.be.y};
+#pragma unroll
+    for (int I = 0; I < NBF; ++I)
+#pragma unroll
+      for (int J = 0; J < NBF; ++J) acc[NBF * I + J] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4.a[I], b4.b[J], acc[NBF * I + J], 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < RS; ++e) {
+#pragma unroll
+      for (int I = 0; I < NBF; ++I) {
+        rs[e][I] = fma(ae[e], b4.b[I], rs[e][I]);
+        cs[e][I] = fma(a4.a[I], be[e], cs[e][I]);
+      }
+#pragma unroll
+      for (int f = 0; f < RS; ++f) cn[e][f] = fma(ae[e], be[f], cn[e][f]);
+    }
+    if (s + PD < KS) qr[s % PD] = ldq(s + PD);
+    // (keeps the strip's FMAs in the step whose operands they use: left alone, hipcc moves all of them behind the last matrix
+    // instruction and carries the operands of thirteen steps there through scratch -- 100 scratch accesses inside the product)
+    asm volatile(""
+                 : "+v"(rs[0][0]), "+v"(rs[0][1]), "+v"(rs[0][2]), "+v"(rs[1][0]), "+v"(rs[1][1]), "+v"(rs[1][2]), "+v"(cs[0][0]),
+                   "+v"(cs[0][1]), "+v"(cs[0][2]), "+v"(cs[1][0]), "+v"(cs[1][1]), "+v"(cs[1][2]), "+v"(cn[0][0]), "+v"(cn[0][1]),
+                   "+v"(cn[1][0]), "+v"(cn[1][1])::"memory");
+  }
+  // fold the four residues q (lanes c, c + 16, c + 32, c + 48): every lane ends with the whole sums
+  auto fold = [](double v) {
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    return v;
+  };
+#pragma unroll
+  for (int e = 0; e < RS; ++e) {
+#pragma unroll
+    for (int I = 0; I < NBF; ++I) {
+      rs[e][I] = fold(rs[e][I]);
+      cs[e][I] = fold(cs[e][I]);
+    }
+#pragma unroll
+    for (int f = 0; f < RS; ++f) cn[e][f] = fold(cn[e][f]);
+  }
+  wave_lds_sync();
+  // back to "column j at cb[j * KR]" (all rows and columns written are < KR)
+#pragma unroll
+  for (int J = 0; J < NBF; ++J) {
+    double* col = cb + (16 * J + c) * KR;
+#pragma unroll
+    for (int I = 0; I < NBF; ++I)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) col[16 * I + 4 * reg + q] = acc[NBF * I + J][reg];
+    if (q == 0) *reinterpret_cast<double2*>(&col[16 * NBF]) = double2{rs[0][J], rs[1][J]};
+  }
+  if (q == 1) {
+#pragma unroll
+    for (int e = 0; e < RS; ++e)
+#pragma unroll
+      for (int I = 0; I < NBF; ++I) cb[(16 * NBF + e) * KR + 16 * I + c] = cs[e][I];
+  }
+  if (wlane == 32) {
+#pragma unroll
+    for (int f = 0; f < RS; ++f) *reinterpret_cast<double2*>(&cb[(16 * NBF + f) * KR + 16 * NBF]) = double2{cn[0][f], cn[1][f]};
+  }
+  wave_lds_sync();
+  {
+    const double* mine = cb + (wlane < KR ? wlane : 0) * KR;
+#pragma unroll
+    for (int r = 0; r < KR; r += 2) {
+      const double2 v2 = *reinterpret_cast<const double2*>(&mine[r]);
+      g[r] = wlane < KR ? v2.x : 0.0;
+      g[r + 1] = wlane < KR ? v2.y : 0.0;
+    }
+  }
+  wave_lds_sync();
+}
+
 }  // namespace
 
 #if !defined(LETKF_WAVE_UNIT2) && !defined(LETKF_WAVE_UNIT3)
@@ -1481,7 +1644,8 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, NW == 1 ? wave_occupancy(
       // ------------------------------------------------------------ eigen-decomposition in registers
       if constexpr (WARM) {
         if (have_u && !(A.warm_dbg & 1)) {
-          if constexpr (NW == 1 && KR <= 50) warm_start_product_mfma<KR>(g, uws - lane, slice);
+          if constexpr (LETKF_WARM_STRIP && NW == 1 && KR == 50) warm_start_product_strip<KR>(g, uws - lane, slice);
+          else if constexpr (NW == 1 && KR <= 50) warm_start_product_mfma<KR>(g, uws - lane, slice);
           else warm_start_product<KR, NW>(g, uws, k, slice);
         }
       }

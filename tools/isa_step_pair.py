@@ -1,8 +1,9 @@
 """Instruction count and mix of the Jacobi step pair (the loop with the 114 DPP moves) in the ISA of the production wave kernel.
-Usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only scale-letkf_amd/csrc/letkf_wave.hip -o /tmp/wave.s; python tools/isa_step_pair.py /tmp/wave.s"""
+Usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -S --cuda-device-only scale-letkf_amd/csrc/letkf_wave.hip -o /tmp/wave.s; python tools/isa_step_pair.py /tmp/wave.s
+(or the assembly the Makefile leaves beside the objects: scale-letkf_amd/lib/obj/letkf_wave-hip-amdgcn-amd-amdhsa-gfx950.s)"""
 import sys
 from collections import Counter
-def steppair(path, kern="_ZN5letkf17letkf_wave_kernelILi50ELi11ELb0ELi1ELb0EEEvNS_9PointArgsE:"):
+def steppair(path, kern="_ZN5letkf17letkf_wave_kernelILi50ELi11ELb0ELi1ELi0EEEvNS_9PointArgsE:"):
     L=open(path).read().split("\n")
     start=[i for i,l in enumerate(L) if l.startswith(kern)][0]
     end=[i for i,l in enumerate(L) if i>start and l.startswith("_ZN5letkf17letkf_wave_kernel")][0]
