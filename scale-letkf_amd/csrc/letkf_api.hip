@@ -50,27 +50,35 @@ int fail(int code, const std::string& msg) {
 
 }  // namespace
 
+// One of the context's device buffers; grow() below sizes it.
+struct DevBuf {
+  char* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void release() {   // (hipFree waits for the work that still reads the buffer)
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
 struct letkf_ctx {
   int device = -1;
   int num_cu = 256;
   size_t lds_max = 160 * 1024;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
-  char* ws = nullptr;         // letkf_point_kernel<BIG>: its per-workgroup matrices
-  size_t ws_bytes = 0;
-  char* warm_ws = nullptr;    // wave kernel: eigenvectors handed from point to point inside a run
+  DevBuf ws;                  // letkf_point_kernel<BIG>: its per-workgroup matrices
+  DevBuf warm_ws;             // wave kernel: eigenvectors handed from point to point inside a run
   unsigned* sched = nullptr;  // wave kernel: the 8 run counters of the dynamic scheduling (512 bytes)
-  size_t warm_ws_bytes = 0;
-  char* scratch = nullptr;    // staging for the host-pointer entry
-  size_t scratch_bytes = 0;
-  char* list_ws = nullptr;    // letkf_das_columns_dev: the local-observation lists of one slab of levels / the survivors of a batch of columns
-  size_t list_ws_bytes = 0;
-  char* slot_ws = nullptr;    // ... its list-free route: one local list per resident wave
-  size_t slot_ws_bytes = 0;
-  char* ring_ws = nullptr;    // limited column search on dense observations: ring-ordered survivors of a batch of columns
-  size_t ring_ws_bytes = 0;
-  char* ring_aux = nullptr;   // ... their counts / offsets / ring starts
-  size_t ring_aux_bytes = 0;
+  DevBuf scratch;             // staging for the host-pointer entry; counts | offsets | scan scratch of the list-driven entries
+  DevBuf list_ws;             // letkf_das_columns_dev: the local-observation lists of one slab of levels / the survivors of a batch of columns
+  DevBuf slot_ws;             // ... its list-free route: one local list per resident wave
+  DevBuf ring_ws;             // limited column search on dense observations: ring-ordered survivors of a batch of columns
+  DevBuf ring_aux;            // ... their counts / offsets / ring starts
   // (the last "not dense" verdict, by the identity of the tables and columns it was given for: the weighing costs a survivor count
   // and two read-backs -- 17 ms on C2's grid.  Pointer identity says nothing about the CONTENT -- a host that frees and reallocates
   // its tables every analysis gets the same addresses with other observations -- so the verdict only serves (a) the fill call that
@@ -81,16 +89,12 @@ struct letkf_ctx {
   int ring_no_crit = 0;
   bool ring_keep = false;     // inside letkf_das_columns_dev: the survivors of the first search call serve the later ones
   bool ring_ready = false;
-  std::vector<int64_t> ring_hoff;
   int ring_batch_mb = 8192;   // LETKF_OPT_RING_BATCH_MB
   bool ring_release = false;  // LETKF_OPT_RING_RELEASE
   int limited_rings = 2;      // LETKF_OPT_LIMITED_RINGS: 0 never, 1 wherever eligible, 2 where a group's survivors overflow the column kernel's buffer
-  char* efso_ws = nullptr;    // EFSO: the pair contributions of a slab, their sort by observation row and the row offsets
-  size_t efso_ws_bytes = 0;
-  char* obsanal_ws = nullptr; // das_letkf_obs: the targets' coordinates, pseudo-state, inflation and flag word
-  size_t obsanal_ws_bytes = 0;
-  char* staged_ws = nullptr;  // staged path: per-point slabs of a batch + meta / info words
-  size_t staged_ws_bytes = 0;
+  DevBuf efso_ws;             // EFSO: the pair contributions of a slab, their sort by observation row and the row offsets
+  DevBuf obsanal_ws;          // das_letkf_obs: the targets' coordinates, pseudo-state, inflation and flag word
+  DevBuf staged_ws;           // staged path: per-point slabs of a batch + meta / info words
   std::string last_path;      // kernels the last loop-body / letkf_core launch went through (bench.py reports it)
   bool timing = false;
   bool staged_poly = true;    // LETKF_OPT_STAGED_POLY
@@ -101,23 +105,115 @@ struct letkf_ctx {
 
 namespace {
 
-// Grows one of the context's device buffers to at least `need` bytes: a quarter more than that (+ 4 KiB), or exactly `need`
-// without slack.  The buffer it replaces may still be read by work on the stream: that work is waited for first.
-int grow(letkf_ctx* c, char** buf, size_t* have, size_t need, bool slack = true) {
-  if (need <= *have) return LETKF_OK;
-  if (*buf) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-  }
-  const size_t cap = slack ? need + need / 4 + 4096 : need;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), cap));
-  *have = cap;
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Frees one of the context's device buffers.  It may still be read by work on the stream: that work is waited for first.
+int drop(letkf_ctx* c, DevBuf* b) {
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (b->p) HIP_TRY(hipFree(b->p));
+  b->p = nullptr;
+  b->cap = 0;
+  return LETKF_OK;
+}
+
+hipError_t alloc(DevBuf* b, size_t cap) {   // (of a buffer that holds nothing)
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->p), cap);
+  if (e == hipSuccess) b->cap = cap;
+  else b->p = nullptr;
+  return e;
+}
+
+// Grows a buffer to at least `need` bytes: a quarter more than that (+ 4 KiB), or exactly `need` without slack.
+int grow(letkf_ctx* c, DevBuf* b, size_t need, bool slack = true) {
+  if (need <= b->cap) return LETKF_OK;
+  if (b->p)
+    if (int rc = drop(c, b)) return rc;
+  HIP_TRY(alloc(b, slack ? need + need / 4 + 4096 : need));
   return LETKF_OK;
 }
 
 using letkf::count_scan;
+
+// ---- The plumbing of the list-driven entries: count pass -> offsets -> chunks that fit a budget -> fill pass per chunk.
+//
+// counts [n + 1] int32 | offsets [n + 1] int64 | rocprim's scan scratch | tail: bytes of the caller's own, where it asks for any
+// (every part 256-byte aligned)
+struct ScanWs {
+  size_t n = 0, temp_bytes = 0;
+  int32_t* counts = nullptr;
+  int64_t* off = nullptr;
+  char *temp = nullptr, *tail = nullptr;
+  std::vector<int64_t> hoff;   // the offsets that offsets_to_host brought back
+};
+// lays it out in buffer b, grown to hold it
+int scan_ws(letkf_ctx* c, DevBuf* b, size_t n, size_t tail_bytes, ScanWs* s) {
+  s->n = n;
+  HIP_TRY(count_scan(nullptr, &s->temp_bytes, nullptr, nullptr, n + 1, c->stream));
+  const size_t o_off = align256((n + 1) * 4), o_scan = o_off + align256((n + 1) * 8);
+  const size_t o_tail = o_scan + align256(s->temp_bytes);
+  if (int rc = grow(c, b, (tail_bytes ? o_tail + tail_bytes : o_scan + s->temp_bytes) + 256)) return rc;
+  s->counts = reinterpret_cast<int32_t*>(b->p);
+  s->off = reinterpret_cast<int64_t*>(b->p + o_off);
+  s->temp = b->p + o_scan;
+  s->tail = b->p + o_tail;
+  return LETKF_OK;
+}
+
+// in front of the count pass, which writes counts [0, n): the scan runs over n + 1 entries, and the last one is the total
+hipError_t zero_total(letkf_ctx* c, const ScanWs& s) { return hipMemsetAsync(s.counts + s.n, 0, 4, c->stream); }
+// behind the count pass: the prefix sum ...
+hipError_t scan_offsets(letkf_ctx* c, const ScanWs& s) {
+  size_t temp_bytes = s.temp_bytes;
+  return count_scan(s.temp, &temp_bytes, s.counts, s.off, s.n + 1, c->stream);
+}
+// ... and offsets 0, stride, 2 stride, .. n back to the host -- with them, behind the same synchronisation (the entry's one),
+// `also_bytes` of the caller's own
+int offsets_to_host(letkf_ctx* c, ScanWs& s, size_t stride = 1, void* also_dst = nullptr, const void* also_src = nullptr,
+                    size_t also_bytes = 0) {
+  s.hoff.resize(s.n / stride + 1);
+  if (stride == 1)
+    HIP_TRY(hipMemcpyAsync(s.hoff.data(), s.off, s.hoff.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  else
+    HIP_TRY(hipMemcpy2DAsync(s.hoff.data(), 8, s.off, stride * 8, 8, s.hoff.size(), hipMemcpyDeviceToHost, c->stream));
+  if (also_bytes) HIP_TRY(hipMemcpyAsync(also_dst, also_src, also_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LETKF_OK;
+}
+
+// The end of the chunk of items that starts at `first`.  Item i has entries off[i * stride] to off[(i + 1) * stride]: at least one
+// item, however long its list (the workspace grows to hold it), then as many more, below `end`, as keep the chunk's entries within
+// `budget` bytes at entry_bytes each and within max_entries.
+int64_t chunk_end(const std::vector<int64_t>& off, int64_t first, int64_t end, int64_t stride, int64_t entry_bytes,
+                  int64_t budget, int64_t max_entries = INT64_MAX) {
+  auto ne = [&](int64_t i) { return off[(size_t)(i * stride)] - off[(size_t)(first * stride)]; };   // entries of items [first, i)
+  int64_t last = first + 1;
+  while (last < end && ne(last + 1) * entry_bytes <= budget && ne(last + 1) <= max_entries) ++last;
+  return last;
+}
+
+// A chunk's entries [e0, e1) in a workspace of their own.  The kernels address entry j of item p as base[off[p] + j] with the
+// GLOBAL offsets: shift the bases.  A chunk without entries still has a base: room for one.
+//
+// ... local-observation lists idx | rdiag | rloc in list_ws (20 B per entry)
+struct ListSlab {
+  int32_t* idx = nullptr;
+  double *rd = nullptr, *rl = nullptr;
+};
+int list_slab(letkf_ctx* c, int64_t e0, int64_t e1, ListSlab* l) {
+  const size_t n1 = (size_t)std::max<int64_t>(e1 - e0, 1);
+  const size_t o_rd = align256(n1 * 4), o_rl = o_rd + align256(n1 * 8);
+  if (int rc = grow(c, &c->list_ws, o_rl + n1 * 8 + 256)) return rc;
+  l->idx = reinterpret_cast<int32_t*>(c->list_ws.p) - e0;
+  l->rd = reinterpret_cast<double*>(c->list_ws.p + o_rd) - e0;
+  l->rl = reinterpret_cast<double*>(c->list_ws.p + o_rl) - e0;
+  return LETKF_OK;
+}
+// ... the horizontal survivors of a batch of columns in buffer b (4 doubles each)
+int survivor_slab(letkf_ctx* c, DevBuf* b, int64_t e0, int64_t e1, double** sv) {
+  if (int rc = grow(c, b, (size_t)std::max<int64_t>(e1 - e0, 1) * 32 + 256)) return rc;
+  *sv = reinterpret_cast<double*>(b->p) - 4 * e0;
+  return LETKF_OK;
+}
 
 // Measurement-only knobs exist in the PROF twin of the library (make PROF=1) and nowhere else: the production build
 // reads no environment variable that could change a result.
@@ -211,16 +307,16 @@ int prepare_wave(letkf_ctx* c, letkf::PointArgs& a, const Route& r, int warm_run
   if (a.npts % a.warm_stride != 0) return fail(LETKF_E_INVALID, "warm_stride does not divide npts");
   letkf::wave_launch_shape(a.k, a.mode, a.npts, c->num_cu, run_req, a.warm_stride, &a.run_len, &a.wave_grid, &wbytes);
   if (r.family == Family::wave) {   // (the trio kernel parks its eigenvectors in LDS)
-    if (int rc = grow(c, &c->warm_ws, &c->warm_ws_bytes, wbytes)) return rc;
-    a.warm_ws = reinterpret_cast<double*>(c->warm_ws);
+    if (int rc = grow(c, &c->warm_ws, wbytes)) return rc;
+    a.warm_ws = reinterpret_cast<double*>(c->warm_ws.p);
   }
   if (a.mode == 3) {   // one local-list slot per wave of the grid (4 waves per workgroup): idx | rdiag | rloc
     const size_t nslot = (size_t)a.wave_grid * 4, cap = 2 * (size_t)(a.sl_cap > 0 ? a.sl_cap : 4);   // (two lists per wave: this level's and the next one's)
-    const size_t o_rd = (nslot * cap * 4 + 255) & ~(size_t)255, o_rl = o_rd + nslot * cap * 8;
-    if (int rc = grow(c, &c->slot_ws, &c->slot_ws_bytes, o_rl + nslot * cap * 8 + 256)) return rc;
-    a.sl_idx = reinterpret_cast<int*>(c->slot_ws);
-    a.sl_rd = reinterpret_cast<double*>(c->slot_ws + o_rd);
-    a.sl_rl = reinterpret_cast<double*>(c->slot_ws + o_rl);
+    const size_t o_rd = align256(nslot * cap * 4), o_rl = o_rd + nslot * cap * 8;
+    if (int rc = grow(c, &c->slot_ws, o_rl + nslot * cap * 8 + 256)) return rc;
+    a.sl_idx = reinterpret_cast<int*>(c->slot_ws.p);
+    a.sl_rd = reinterpret_cast<double*>(c->slot_ws.p + o_rd);
+    a.sl_rl = reinterpret_cast<double*>(c->slot_ws.p + o_rl);
     a.obs_idx = a.sl_idx;
     a.rdiag_l = a.sl_rd;
     a.rloc_l = a.sl_rl;
@@ -269,7 +365,7 @@ int prepare_staged(letkf_ctx* c, const letkf::PointArgs& a, const Route& r, long
     if (up <= cap) nb = up;
   }
   const size_t need = (size_t)nb * (size_t)wpp * sizeof(double) + (size_t)nb * 4 * sizeof(int) + 256;
-  if (int rc = grow(c, &c->staged_ws, &c->staged_ws_bytes, need)) return rc;
+  if (int rc = grow(c, &c->staged_ws, need)) return rc;
   *nb_out = nb;
   *wpp_out = wpp;
   return LETKF_OK;
@@ -281,10 +377,10 @@ int launch_staged(letkf_ctx* c, const letkf::PointArgs& a, const Route& r, long 
   const size_t slab_bytes = (size_t)nb * (size_t)wpp * sizeof(double);
   letkf::StagedArgs s;
   s.A = a;
-  s.A.ws = reinterpret_cast<double*>(c->staged_ws);
+  s.A.ws = reinterpret_cast<double*>(c->staged_ws.p);
   s.A.ws_per_block = wpp;
   s.A.max_sweep = 60;
-  s.meta = reinterpret_cast<int*>(c->staged_ws + slab_bytes);
+  s.meta = reinterpret_cast<int*>(c->staged_ws.p + slab_bytes);
   s.info = s.meta + 2 * nb;
   s.kkout = (a.trans_out || a.pa_out) ? 1 : 0;
   s.wg_max_order = letkf::eig_wg_max_order();
@@ -328,11 +424,11 @@ int launch(letkf_ctx* c, letkf::PointArgs& a, int warm_run = 0, long warm_stride
   } else if (r.family == Family::staged) {
     if (int rc = prepare_staged(c, a, r, &nb, &wpp)) return rc;
   } else {
-    if (int rc = grow(c, &c->ws, &c->ws_bytes, r.plan.ws_bytes(), false)) return rc;
+    if (int rc = grow(c, &c->ws, r.plan.ws_bytes(), false)) return rc;
     a.ldg = r.plan.ldg;
     a.ldy = r.plan.ldy;
     a.tn = r.plan.tn;
-    a.ws = reinterpret_cast<double*>(c->ws);
+    a.ws = reinterpret_cast<double*>(c->ws.p);
     a.ws_per_block = r.plan.ws_per_block;
     a.big_block = (r.plan.big && !LETKF_KNOB("LETKF_AMD_BIG_STREAM")) ? 1 : 0;   // PROF knob: the older streaming Jacobi
   }
@@ -410,11 +506,7 @@ struct RingKeep {
     // stays with the context for the next analysis (allocating and freeing 64 GB per call cost the MEMBER = 100 tile 1.7 s of a
     // 4 s analysis); LETKF_OPT_RING_RELEASE = 1 hands back whatever exceeds the batch budget when the entry returns, for a host
     // model that needs the memory between analyses (hipFree waits for the work that still reads the buffer)
-    if (c->ring_release && c->ring_ws && c->ring_ws_bytes > ((size_t)c->ring_batch_mb << 20) + ((size_t)c->ring_batch_mb << 18) + 8192) {
-      (void)hipFree(c->ring_ws);
-      c->ring_ws = nullptr;
-      c->ring_ws_bytes = 0;
-    }
+    if (c->ring_release && c->ring_ws.cap > ((size_t)c->ring_batch_mb << 20) + ((size_t)c->ring_batch_mb << 18) + 8192) c->ring_ws.release();
   }
 };
 
@@ -477,8 +569,8 @@ int efso_run_slab(letkf_ctx* c, const letkf::EfsoArgs& a, int64_t npts, int64_t 
   if (npts <= 0 || e1 <= e0 || a.nobs == 0) return LETKF_OK;
   letkf::EfsoWs ws;
   HIP_TRY(letkf::efso_ws_layout(e1 - e0, a.nobs, a.nterm, c->stream, &ws));
-  if (int rc = grow(c, &c->efso_ws, &c->efso_ws_bytes, ws.total)) return rc;
-  HIP_TRY(letkf::efso_slab(a, npts, e0, e1, c->efso_ws, ws, c->num_cu, c->stream));
+  if (int rc = grow(c, &c->efso_ws, ws.total)) return rc;
+  HIP_TRY(letkf::efso_slab(a, npts, e0, e1, c->efso_ws.p, ws, c->num_cu, c->stream));
   return LETKF_OK;
 }
 }  // namespace
@@ -531,20 +623,10 @@ int letkf_ctx_destroy(letkf_ctx* c) {
       (void)hipEventDestroy(ev.first);
       (void)hipEventDestroy(ev.second);
     }
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->warm_ws) (void)hipFree(c->warm_ws);
     if (c->sched) (void)hipFree(c->sched);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->staged_ws) (void)hipFree(c->staged_ws);
-    if (c->list_ws) (void)hipFree(c->list_ws);
-    if (c->slot_ws) (void)hipFree(c->slot_ws);
-    if (c->ring_ws) (void)hipFree(c->ring_ws);
-    if (c->ring_aux) (void)hipFree(c->ring_aux);
-    if (c->efso_ws) (void)hipFree(c->efso_ws);
-    if (c->obsanal_ws) (void)hipFree(c->obsanal_ws);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   }
-  delete c;
+  delete c;   // (its device buffers free themselves)
   return LETKF_OK;
 }
 
@@ -698,6 +780,29 @@ int tables_limited(letkf_ctx* c, const letkf_search_tables* t, bool* limited) {
   return LETKF_OK;
 }
 
+// the tables with what the host now knows of the limits: the fill passes of an entry's chunks read nothing back
+int tables_hinted(letkf_ctx* c, const letkf_search_tables* t, letkf_search_tables* tab) {
+  *tab = *t;
+  if (tab->limit_hint != 1 && tab->limit_hint != 2) {
+    bool limited = false;
+    if (int rc = tables_limited(c, t, &limited)) return rc;
+    tab->limit_hint = limited ? 2 : 1;
+  }
+  return LETKF_OK;
+}
+
+// the counts of a count pass to the caller's nobs_out, if it has one: as the list-free route of letkf_das_columns_dev reports
+// them, zero where beta = 0 (the reference does not run obs_local there, letkf_tools.f90:333-359)
+int report_counts(letkf_ctx* c, const int32_t* counts, int64_t n, const double* beta, int32_t* nobs_out) {
+  if (!nobs_out) return LETKF_OK;
+  HIP_TRY(hipMemcpyAsync(nobs_out, counts, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
+  if (beta) {
+    hipLaunchKernelGGL(zero_where_beta_is_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, beta, nobs_out);
+    HIP_TRY(hipGetLastError());
+  }
+  return LETKF_OK;
+}
+
 // shared by the list-driven and the fused-search entry
 // (mode 3, letkf_das_columns_dev's list-free route: the points are pt0 + a * pt_stride + b, b < g->warm_stride columns whose
 // horizontal survivors are sv[4 * sv_off[b] ..]; every per-point array of g is indexed by that GLOBAL point number)
@@ -834,44 +939,33 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     bool limited = false;
     if (int rc = tables_limited(c, t, &limited)) return rc;
     if (!limited) {
-      // workspace: counts [nij1 + 1] int32 | sv_off [nij1 + 1] int64 | scan scratch
-      size_t scan_b = 0;
-      HIP_TRY(count_scan(nullptr, &scan_b, nullptr, nullptr, (size_t)nij1 + 1, c->stream));
-      const size_t o_off = ((size_t)(nij1 + 1) * 4 + 255) & ~(size_t)255;
-      const size_t o_scan = o_off + (((size_t)(nij1 + 1) * 8 + 255) & ~(size_t)255);
-      if (int rc = grow(c, &c->scratch, &c->scratch_bytes, o_scan + scan_b + 256)) return rc;
-      int32_t* cnt = reinterpret_cast<int32_t*>(c->scratch);
-      int64_t* soff = reinterpret_cast<int64_t*>(c->scratch + o_off);
-      HIP_TRY(hipMemsetAsync(cnt + nij1, 0, 4, c->stream));
-      HIP_TRY(letkf::launch_survivors(*t, 0, nij1, rig, rjg, 0, cnt, nullptr, nullptr, c->num_cu, c->stream));
-      HIP_TRY(count_scan(c->scratch + o_scan, &scan_b, cnt, soff, (size_t)nij1 + 1, c->stream));
-      std::vector<int64_t> hoff((size_t)nij1 + 1);
-      HIP_TRY(hipMemcpyAsync(hoff.data(), soff, ((size_t)nij1 + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
+      // ---- survivor count per column, prefix sum, the offsets back to the host
+      ScanWs sw;
+      if (int rc = scan_ws(c, &c->scratch, (size_t)nij1, 0, &sw)) return rc;
+      HIP_TRY(zero_total(c, sw));
+      HIP_TRY(letkf::launch_survivors(*t, 0, nij1, rig, rjg, 0, sw.counts, nullptr, nullptr, c->num_cu, c->stream));
+      HIP_TRY(scan_offsets(c, sw));
+      if (int rc = offsets_to_host(c, sw)) return rc;
       // (2 = automatic: the list-free route where the lists of all levels would not fit the workspace at once -- about half
       // of a column's horizontal survivors pass a level's vertical cut-off, 20 B each.  Where they fit, one fill pass for
       // the whole domain is cheaper than the vertical half inside the register-bound loop body kernel: C2, 203 local
       // observations per point, 384 against 394 ms per analysis; BASELINE configs[3], 4900 per point, 40 slabs: 7.45 against 6.11 s.)
-      const bool take = c->col_survivors == 1 || (double)hoff[nij1] * (double)nlev * 10.0 > (double)list_bytes;
-      // batches of columns whose survivors fit the workspace (32 B each), at least one column
+      const bool take = c->col_survivors == 1 || (double)sw.hoff[nij1] * (double)nlev * 10.0 > (double)list_bytes;
+      // batches of columns whose survivors fit the workspace (32 B each)
       int64_t c0 = take ? 0 : nij1;
       while (c0 < nij1) {
-        int64_t c1 = c0 + 1;
-        while (c1 < nij1 && (hoff[c1 + 1] - hoff[c0]) * 32 <= list_bytes) ++c1;
-        const int64_t nsv = hoff[c1] - hoff[c0];
-        const size_t need = (size_t)(nsv > 0 ? nsv : 1) * 32 + 256;
-        if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, need)) return rc;
-        // entry e of column b is addressed as sv[4 * sv_off[b] + ...] with the GLOBAL offsets: shift the base
-        double* sv = reinterpret_cast<double*>(c->list_ws) - 4 * hoff[c0];
-        HIP_TRY(letkf::launch_survivors(*t, c0, c1 - c0, rig, rjg, 1, nullptr, reinterpret_cast<const long*>(soff + c0), sv, c->num_cu,
+        const int64_t c1 = chunk_end(sw.hoff, c0, nij1, 1, 32, list_bytes);
+        double* sv = nullptr;
+        if (int rc = survivor_slab(c, &c->list_ws, sw.hoff[c0], sw.hoff[c1], &sv)) return rc;
+        HIP_TRY(letkf::launch_survivors(*t, c0, c1 - c0, rig, rjg, 1, nullptr, reinterpret_cast<const long*>(sw.off + c0), sv, c->num_cu,
                                         c->stream));
         letkf_das_args a = *g;
         a.npts = (c1 - c0) * (int64_t)nlev;
         a.infl_sv = g->infl_sv > 0 ? g->infl_sv : npts;
         a.warm_stride = (int32_t)(c1 - c0);                   // runs up the columns
         int64_t cap = 0;
-        for (int64_t cc = c0; cc < c1; ++cc) cap = std::max(cap, hoff[cc + 1] - hoff[cc]);
-        SurvivorView sview{soff + c0, sv, nij1, c0, cap};
+        for (int64_t cc = c0; cc < c1; ++cc) cap = std::max(cap, sw.hoff[cc + 1] - sw.hoff[cc]);
+        SurvivorView sview{sw.off + c0, sv, nij1, c0, cap};
         if (int rc = das_points_impl(c, &a, t, nullptr, nullptr, rlev, rz, nobs_out, &sview)) return rc;
         c0 = c1;
       }
@@ -880,54 +974,33 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
   }
   // (the searches below -- one count pass, a fill pass per slab -- share the ring-ordered survivors of the dense limited case)
   RingKeep ring_keep_guard(c);
-  // workspace: counts [npts] int32 | obs_off [npts + 1] int64 | scan scratch
-  size_t scan_bytes = 0;
-  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, (size_t)npts + 1, c->stream));
-  const size_t off_counts = 0, off_off = ((size_t)(npts + 1) * 4 + 255) & ~(size_t)255;
-  const size_t off_scan = off_off + (((size_t)(npts + 1) * 8 + 255) & ~(size_t)255);
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
-  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch + off_counts);
-  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
   // ---- count pass over all levels, prefix sum, level boundaries back to the host
-  HIP_TRY(hipMemsetAsync(counts + npts, 0, 4, c->stream));   // (the scan runs over npts + 1 entries: the last one is the total)
-  if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, counts, nullptr, nullptr, nullptr, nullptr,
+  ScanWs sw;
+  if (int rc = scan_ws(c, &c->scratch, (size_t)npts, 0, &sw)) return rc;
+  HIP_TRY(zero_total(c, sw));
+  if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, sw.counts, nullptr, nullptr, nullptr, nullptr,
                                             nullptr, nullptr))
     return rc;
-  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, (size_t)npts + 1, c->stream));
-  if (nobs_out) {
-    HIP_TRY(hipMemcpyAsync(nobs_out, counts, (size_t)npts * 4, hipMemcpyDeviceToDevice, c->stream));
-    // (as the list-free route reports them: the reference does not run obs_local where beta = 0, letkf_tools.f90:333-359)
-    if (g->beta) {
-      hipLaunchKernelGGL(zero_where_beta_is_zero, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, c->stream, npts, g->beta, nobs_out);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  std::vector<int64_t> lev_off((size_t)nlev + 1);
-  HIP_TRY(hipMemcpy2DAsync(lev_off.data(), 8, off, (size_t)nij1 * 8, 8, (size_t)nlev + 1, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  // ---- slabs of levels: as many as fit the list workspace (20 B per entry), at least one
+  HIP_TRY(scan_offsets(c, sw));
+  if (int rc = report_counts(c, sw.counts, npts, g->beta, nobs_out)) return rc;
+  if (int rc = offsets_to_host(c, sw, (size_t)nij1)) return rc;
+  const std::vector<int64_t>& lev_off = sw.hoff;
+  // ---- slabs of levels: as many as fit the list workspace (20 B per entry)
   int l0 = 0;
   while (l0 < nlev) {
-    int l1 = l0 + 1;
-    while (l1 < nlev && (lev_off[l1 + 1] - lev_off[l0]) * 20 <= list_bytes) ++l1;
-    const int64_t nnz = lev_off[l1] - lev_off[l0], p0 = (int64_t)l0 * nij1, np = (int64_t)(l1 - l0) * nij1;
-    const size_t n1 = (size_t)(nnz > 0 ? nnz : 1);
-    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
-    const size_t need = o_rl + n1 * 8 + 256;
-    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, need)) return rc;
-    // the kernels address list entry e of point p as base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
-    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - lev_off[l0];
-    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - lev_off[l0];
-    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - lev_off[l0];
-    if (int rc = letkf_obs_search_columns_dev(c, t, nij1, l1 - l0, rig, rjg, rlev + p0, rz + p0, 1, nullptr, off + p0, idx, rd, rl,
-                                              nullptr, nullptr))
+    const int l1 = (int)chunk_end(lev_off, l0, nlev, 1, 20, list_bytes);
+    const int64_t p0 = (int64_t)l0 * nij1, np = (int64_t)(l1 - l0) * nij1;
+    ListSlab ls;
+    if (int rc = list_slab(c, lev_off[l0], lev_off[l1], &ls)) return rc;
+    if (int rc = letkf_obs_search_columns_dev(c, t, nij1, l1 - l0, rig, rjg, rlev + p0, rz + p0, 1, nullptr, sw.off + p0, ls.idx, ls.rd,
+                                              ls.rl, nullptr, nullptr))
       return rc;
     letkf_das_args a = *g;
     a.npts = np;
-    a.obs_off = off + p0;
-    a.obs_idx = idx;
-    a.rdiag_l = rd;
-    a.rloc_l = rl;
+    a.obs_off = sw.off + p0;
+    a.obs_idx = ls.idx;
+    a.rdiag_l = ls.rd;
+    a.rloc_l = ls.rl;
     a.gues = g->gues + p0 * g->sp;
     a.anal = g->anal + p0 * g->sp;
     if (g->beta) a.beta = g->beta + p0;
@@ -962,8 +1035,7 @@ int letkf_efso_points_dev(letkf_ctx* c, const letkf_efso_args* g) {
   HIP_TRY(hipMemcpyAsync(off.data(), g->obs_off, off.size() * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int64_t p0 = 0; p0 < g->npts;) {
-    int64_t p1 = p0 + 1;   // at least one point, however long its list
-    while (p1 < g->npts && off[p1 + 1] - off[p0] <= cap) ++p1;
+    const int64_t p1 = chunk_end(off, p0, g->npts, 1, 1, cap);   // (the budget in entries: cap of them, 1 B each)
     if (off[p1] - off[p0] > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a point with more than 2^31 local observations");
     letkf::EfsoArgs s = a;
     s.obs_off = a.obs_off + p0;
@@ -988,43 +1060,32 @@ int letkf_efso_columns_dev(letkf_ctx* c, const letkf_efso_args* g, const letkf_s
   if (list_bytes <= 0) list_bytes = (int64_t)8 << 30;
   const int64_t npts = g->npts, per_entry = 20 + efso_entry_bytes(g->nterm);
   RingKeep ring_keep_guard(c);
-  // workspace: counts [npts] int32 | obs_off [npts + 1] int64 | scan scratch
-  size_t scan_bytes = 0;
-  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, (size_t)npts + 1, c->stream));
-  const size_t off_off = ((size_t)(npts + 1) * 4 + 255) & ~(size_t)255;
-  const size_t off_scan = off_off + (((size_t)(npts + 1) * 8 + 255) & ~(size_t)255);
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
-  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch);
-  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
-  HIP_TRY(hipMemsetAsync(counts + npts, 0, 4, c->stream));
-  if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, counts, nullptr, nullptr, nullptr, nullptr,
+  // ---- count pass over all levels, prefix sum, level boundaries back to the host
+  ScanWs sw;
+  if (int rc = scan_ws(c, &c->scratch, (size_t)npts, 0, &sw)) return rc;
+  HIP_TRY(zero_total(c, sw));
+  if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, sw.counts, nullptr, nullptr, nullptr, nullptr,
                                             nullptr, nullptr))
     return rc;
-  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, (size_t)npts + 1, c->stream));
-  std::vector<int64_t> lev_off((size_t)nlev + 1);
-  HIP_TRY(hipMemcpy2DAsync(lev_off.data(), 8, off, (size_t)nij1 * 8, 8, (size_t)nlev + 1, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(scan_offsets(c, sw));
+  if (int rc = offsets_to_host(c, sw, (size_t)nij1)) return rc;
+  const std::vector<int64_t>& lev_off = sw.hoff;
+  // ---- slabs of levels whose lists and pair workspace fit: fill pass, EFSO passes
   int l0 = 0;
   while (l0 < nlev) {
-    int l1 = l0 + 1;
-    while (l1 < nlev && (lev_off[l1 + 1] - lev_off[l0]) * per_entry <= list_bytes && lev_off[l1 + 1] - lev_off[l0] <= kEfsoMaxSlab) ++l1;
-    const int64_t nnz = lev_off[l1] - lev_off[l0], p0 = (int64_t)l0 * nij1, np = (int64_t)(l1 - l0) * nij1;
-    if (nnz > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a level with more than 2^31 local observations");
-    const size_t n1 = (size_t)(nnz > 0 ? nnz : 1);
-    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
-    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, o_rl + n1 * 8 + 256)) return rc;
-    // list entry e of the slab's point p at base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
-    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - lev_off[l0];
-    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - lev_off[l0];
-    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - lev_off[l0];
-    if (int rc = letkf_obs_search_columns_dev(c, t, nij1, l1 - l0, rig, rjg, rlev + p0, rz + p0, 1, nullptr, off + p0, idx, rd, rl,
-                                              nullptr, nullptr))
+    const int l1 = (int)chunk_end(lev_off, l0, nlev, 1, per_entry, list_bytes, kEfsoMaxSlab);
+    const int64_t p0 = (int64_t)l0 * nij1, np = (int64_t)(l1 - l0) * nij1;
+    if (lev_off[l1] - lev_off[l0] > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a level with more than 2^31 local observations");
+    ListSlab ls;
+    if (int rc = list_slab(c, lev_off[l0], lev_off[l1], &ls)) return rc;
+    if (int rc = letkf_obs_search_columns_dev(c, t, nij1, l1 - l0, rig, rjg, rlev + p0, rz + p0, 1, nullptr, sw.off + p0, ls.idx, ls.rd,
+                                              ls.rl, nullptr, nullptr))
       return rc;
     letkf::EfsoArgs s = a;
-    s.obs_off = reinterpret_cast<const long*>(off + p0);
-    s.obs_idx = idx;
-    s.rdiag_l = rd;
-    s.rloc_l = rl;
+    s.obs_off = reinterpret_cast<const long*>(sw.off + p0);
+    s.obs_idx = ls.idx;
+    s.rdiag_l = ls.rd;
+    s.rloc_l = ls.rl;
     s.fcst = a.fcst + p0 * a.sp;
     s.fcer = a.fcer + p0 * a.fsp;
     if (int rc = efso_run_slab(c, s, np, lev_off[l0], lev_off[l1])) return rc;
@@ -1056,8 +1117,8 @@ int letkf_efso_locadv_dev(letkf_ctx* c, int64_t nij1, int32_t nlev, const double
   // the reference's rad2deg = locadv_rate*eft*3600*180/(pi*re), with the grid spacing in place of the arc per degree
   const double ci = locadv_rate * eft * 3600.0 / dx;
   const double cj = locadv_rate * eft * 3600.0 / dy;
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, 256)) return rc;
-  unsigned* bad = reinterpret_cast<unsigned*>(c->scratch);
+  if (int rc = grow(c, &c->scratch, 256)) return rc;
+  unsigned* bad = reinterpret_cast<unsigned*>(c->scratch.p);
   HIP_TRY(hipMemsetAsync(bad, 0, 4, c->stream));
   HIP_TRY(letkf::launch_efso_locadv(nij1, nij1 * (int64_t)nlev, rig, rjg, u0, v0, u1, v1, ci, cj, ri, rj, bad, c->num_cu,
                                     c->stream));
@@ -1081,58 +1142,38 @@ int letkf_efso_search_dev(letkf_ctx* c, const letkf_efso_args* g, const letkf_se
   if (!ri || !rj || !rlev || !rz) return fail(LETKF_E_INVALID, "a point coordinate array is NULL");
   if (t->nctype < 1 || t->ngroup < 1 || t->criterion < 1 || t->criterion > 3)
     return fail(LETKF_E_INVALID, "bad nctype / ngroup / criterion");
-  // the tables with what the host now knows of the limits: the fill passes of the runs read nothing back
-  letkf_search_tables tab = *t;
-  if (tab.limit_hint != 1 && tab.limit_hint != 2) {
-    bool limited = false;
-    if (int rc = tables_limited(c, t, &limited)) return rc;
-    tab.limit_hint = limited ? 2 : 1;
-  }
+  letkf_search_tables tab;
+  if (int rc = tables_hinted(c, t, &tab)) return rc;
   c->last_path = std::string(tab.limit_hint == 2 ? "search_kernel (radix select) + " : "search_kernel + ") +
                  letkf::efso_path_name(g->nterm);
   if (npts == 0 || g->nobs == 0) return LETKF_OK;
   if (list_bytes <= 0) list_bytes = (int64_t)8 << 30;
   const int64_t per_entry = 20 + efso_entry_bytes(g->nterm);
-  const size_t nd = (size_t)npts;
-  // workspace: counts [npts + 1] int32 | obs_off [npts + 1] int64 | scan scratch
-  size_t scan_bytes = 0;
-  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, nd + 1, c->stream));
-  const size_t off_off = ((nd + 1) * 4 + 255) & ~(size_t)255;
-  const size_t off_scan = off_off + (((nd + 1) * 8 + 255) & ~(size_t)255);
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
-  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch);
-  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
   // ---- count pass over all points, prefix sum, the offsets back to the host (the one synchronisation)
-  HIP_TRY(hipMemsetAsync(counts + npts, 0, 4, c->stream));
-  if (int rc = letkf_obs_search_dev(c, &tab, npts, ri, rj, rlev, rz, 0, counts, nullptr, nullptr, nullptr, nullptr)) return rc;
-  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, nd + 1, c->stream));
-  std::vector<int64_t> hoff(nd + 1);
-  HIP_TRY(hipMemcpyAsync(hoff.data(), off, (nd + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  // ---- runs of consecutive points in ascending order, at least one point each: fill pass, EFSO passes
+  ScanWs sw;
+  if (int rc = scan_ws(c, &c->scratch, (size_t)npts, 0, &sw)) return rc;
+  HIP_TRY(zero_total(c, sw));
+  if (int rc = letkf_obs_search_dev(c, &tab, npts, ri, rj, rlev, rz, 0, sw.counts, nullptr, nullptr, nullptr, nullptr)) return rc;
+  HIP_TRY(scan_offsets(c, sw));
+  if (int rc = offsets_to_host(c, sw)) return rc;
+  // ---- runs of consecutive points in ascending order: fill pass, EFSO passes
   for (int64_t p0 = 0; p0 < npts;) {
-    int64_t p1 = p0 + 1;
-    while (p1 < npts && (hoff[p1 + 1] - hoff[p0]) * per_entry <= list_bytes && hoff[p1 + 1] - hoff[p0] <= kEfsoMaxSlab) ++p1;
-    const int64_t nnz = hoff[p1] - hoff[p0];
+    const int64_t p1 = chunk_end(sw.hoff, p0, npts, 1, per_entry, list_bytes, kEfsoMaxSlab);
+    const int64_t nnz = sw.hoff[p1] - sw.hoff[p0];
     if (nnz > kEfsoMaxSlab) return fail(LETKF_E_INVALID, "a point with more than 2^31 local observations");
-    const size_t n1 = (size_t)std::max<int64_t>(nnz, 1);
-    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
-    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, o_rl + n1 * 8 + 256)) return rc;
-    // list entry e of the run's point p at base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
-    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - hoff[p0];
-    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - hoff[p0];
-    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - hoff[p0];
+    ListSlab ls;
+    if (int rc = list_slab(c, sw.hoff[p0], sw.hoff[p1], &ls)) return rc;
     if (nnz > 0) {
-      if (int rc = letkf_obs_search_dev(c, &tab, p1 - p0, ri + p0, rj + p0, rlev + p0, rz + p0, 1, nullptr, off + p0, idx, rd, rl))
+      if (int rc = letkf_obs_search_dev(c, &tab, p1 - p0, ri + p0, rj + p0, rlev + p0, rz + p0, 1, nullptr, sw.off + p0, ls.idx, ls.rd, ls.rl))
         return rc;
       letkf::EfsoArgs s = a;
-      s.obs_off = reinterpret_cast<const long*>(off + p0);
-      s.obs_idx = idx;
-      s.rdiag_l = rd;
-      s.rloc_l = rl;
+      s.obs_off = reinterpret_cast<const long*>(sw.off + p0);
+      s.obs_idx = ls.idx;
+      s.rdiag_l = ls.rd;
+      s.rloc_l = ls.rl;
       s.fcst = a.fcst + p0 * a.sp;
       s.fcer = a.fcer + p0 * a.fsp;
-      if (int rc = efso_run_slab(c, s, p1 - p0, hoff[p0], hoff[p1])) return rc;
+      if (int rc = efso_run_slab(c, s, p1 - p0, sw.hoff[p0], sw.hoff[p1])) return rc;
     }
     p0 = p1;
   }
@@ -1197,11 +1238,11 @@ int letkf_efso_norm_dev(letkf_ctx* c, const letkf_efso_norm_params* prm, int64_t
   c->last_path = letkf::efso_norm_path_name(q.k);
   if (!wlev) {
     // dp/ps from the mean pressure; the bad-column count read back before any output is written
-    const size_t nb = ((size_t)a.npts * 8 + 255) & ~(size_t)255;
-    if (int rc = grow(c, &c->scratch, &c->scratch_bytes, 2 * nb + 256)) return rc;
-    double* pbar = reinterpret_cast<double*>(c->scratch);
-    double* w = reinterpret_cast<double*>(c->scratch + nb);
-    unsigned* bad = reinterpret_cast<unsigned*>(c->scratch + 2 * nb);
+    const size_t nb = align256((size_t)a.npts * 8);
+    if (int rc = grow(c, &c->scratch, 2 * nb + 256)) return rc;
+    double* pbar = reinterpret_cast<double*>(c->scratch.p);
+    double* w = reinterpret_cast<double*>(c->scratch.p + nb);
+    unsigned* bad = reinterpret_cast<unsigned*>(c->scratch.p + 2 * nb);
     HIP_TRY(hipMemsetAsync(bad, 0, 4, c->stream));
     HIP_TRY(letkf::launch_efso_dpw(nij1, nlev, q.k, fcst + q.iv_p * sv, sp, sm, a.rinbv, pbar, w, bad, c->num_cu, c->stream));
     unsigned nbad = 0;
@@ -1232,9 +1273,9 @@ int letkf_efso_summary_dev(letkf_ctx* c, int32_t nterm, int64_t nobs, const doub
   size_t sort_b = 0, scan_b = 0;
   const size_t need = letkf::efso_summary_ws(nobs, nbins, c->stream, &sort_b, &scan_b);
   if (!need) return fail(LETKF_E_HIP, "rocprim workspace query failed");
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
+  if (int rc = grow(c, &c->scratch, need)) return rc;
   HIP_TRY(letkf::launch_efso_summary(nterm, nobs, obsense, elm, typ, lat, qc, nid, elem_uid, nobtype, latbound, count, sum,
-                                     nneg, c->scratch, sort_b, scan_b, c->num_cu, c->stream));
+                                     nneg, c->scratch.p, sort_b, scan_b, c->num_cu, c->stream));
   c->last_path = "efso_bin_kernel + rocprim radix_sort_pairs + efso_binsum_kernel";
   return LETKF_OK;
 }
@@ -1260,18 +1301,13 @@ int letkf_das_obs_dev(letkf_ctx* c, const letkf_das_obs_args* g, const letkf_sea
   const bool qvar = g->tvar >= 0 && g->tvar >= g->iv_q_first && g->tvar <= g->iv_q_last;
   const bool qtop = qvar && g->q_update_top > 0.0;
   const bool qsprd = g->tvar >= 0 && g->tvar == g->iv_q_first && g->q_sprd_max > 0.0;
-  // the tables with what the host now knows of the limits: the fill passes of the chunks read nothing back
-  letkf_search_tables tab = *t;
-  if (tab.limit_hint != 1 && tab.limit_hint != 2) {
-    bool limited = false;
-    if (int rc = tables_limited(c, t, &limited)) return rc;
-    tab.limit_hint = limited ? 2 : 1;
-  }
+  letkf_search_tables tab;
+  if (int rc = tables_hinted(c, t, &tab)) return rc;
   // workspace: ri | rj | rlev | rz [n] | infl [2 n] | gues [2 (k + 2) n] | anal [2 (k + 2) n] | flag word
   const size_t nd = (size_t)n, ps = 2 * (size_t)(k + 2) * nd;
-  const size_t o_flag = (((6 * nd + 2 * ps) * 8) + 255) & ~(size_t)255;
-  if (int rc = grow(c, &c->obsanal_ws, &c->obsanal_ws_bytes, o_flag + 256)) return rc;
-  double* w = reinterpret_cast<double*>(c->obsanal_ws);
+  const size_t o_flag = align256((6 * nd + 2 * ps) * 8);
+  if (int rc = grow(c, &c->obsanal_ws, o_flag + 256)) return rc;
+  double* w = reinterpret_cast<double*>(c->obsanal_ws.p);
   letkf::ObsAnalArgs o;
   std::memset(&o, 0, sizeof(o));
   o.tab = tab;
@@ -1296,42 +1332,27 @@ int letkf_das_obs_dev(letkf_ctx* c, const letkf_das_obs_args* g, const letkf_sea
   o.infl_ws = w + 4 * nd;
   o.gues = w + 6 * nd;
   o.anal = w + 6 * nd + ps;
-  o.flags = reinterpret_cast<unsigned*>(c->obsanal_ws + o_flag);
+  o.flags = reinterpret_cast<unsigned*>(c->obsanal_ws.p + o_flag);
   o.ya = g->ya;
   o.ya_mean = g->ya_mean;
   o.ya_table = g->ya_table;
   o.dep_a = g->dep_a;
-  // workspace: counts [n + 1] int32 | obs_off [n + 1] int64 | scan scratch
-  size_t scan_bytes = 0;
-  HIP_TRY(count_scan(nullptr, &scan_bytes, nullptr, nullptr, nd + 1, c->stream));
-  const size_t off_off = ((nd + 1) * 4 + 255) & ~(size_t)255;
-  const size_t off_scan = off_off + (((nd + 1) * 8 + 255) & ~(size_t)255);
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, off_scan + scan_bytes + 256)) return rc;
-  int32_t* counts = reinterpret_cast<int32_t*>(c->scratch);
-  int64_t* off = reinterpret_cast<int64_t*>(c->scratch + off_off);
   // ---- targets, count pass, prefix sum; the offsets and the argument flags back to the host (the one synchronisation)
+  ScanWs sw;
+  unsigned flags = 0;
+  if (int rc = scan_ws(c, &c->scratch, nd, 0, &sw)) return rc;
   HIP_TRY(hipMemsetAsync(o.flags, 0, 4, c->stream));
   HIP_TRY(letkf::launch_obsanal_targets(o, c->stream));
-  HIP_TRY(hipMemsetAsync(counts + n, 0, 4, c->stream));
-  if (int rc = letkf_obs_search_dev(c, &tab, n, o.ri, o.rj, o.rlev, o.rz, 0, counts, nullptr, nullptr, nullptr, nullptr)) return rc;
-  HIP_TRY(count_scan(c->scratch + off_scan, &scan_bytes, counts, off, nd + 1, c->stream));
-  std::vector<int64_t> hoff(nd + 1);
-  unsigned flags = 0;
-  HIP_TRY(hipMemcpyAsync(hoff.data(), off, (nd + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&flags, o.flags, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(zero_total(c, sw));
+  if (int rc = letkf_obs_search_dev(c, &tab, n, o.ri, o.rj, o.rlev, o.rz, 0, sw.counts, nullptr, nullptr, nullptr, nullptr)) return rc;
+  HIP_TRY(scan_offsets(c, sw));
+  if (int rc = offsets_to_host(c, sw, 1, &flags, o.flags, 4)) return rc;
   if (flags & letkf::kObsAnalBadRow) return fail(LETKF_E_INVALID, "a tgt_row entry outside [0, nobs)");
   if (flags & letkf::kObsAnalNoCtype) return fail(LETKF_E_INVALID, "a target row lies in no ctype block of the tables");
   if (flags & letkf::kObsAnalNoCoord)
     return fail(LETKF_E_INVALID, "the tables need a vertical coordinate of the targets that rlev_tgt / rz_tgt does not give");
-  if (g->nobs_out) {
-    HIP_TRY(hipMemcpyAsync(g->nobs_out, counts, nd * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (g->beta) {   // (as letkf_das_columns_dev reports them: no obs_local where beta = 0)
-      hipLaunchKernelGGL(zero_where_beta_is_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, g->beta, g->nobs_out);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  // ---- chunks of targets whose lists fit the workspace (20 B per entry), at least one target each: fill pass, loop body
+  if (int rc = report_counts(c, sw.counts, n, g->beta, g->nobs_out)) return rc;
+  // ---- chunks of targets whose lists fit the workspace (20 B per entry): fill pass, loop body
   const int64_t list_bytes = g->list_bytes > 0 ? g->list_bytes : ((int64_t)8 << 30);
   letkf_das_args a;
   std::memset(&a, 0, sizeof(a));
@@ -1357,22 +1378,17 @@ int letkf_das_obs_dev(letkf_ctx* c, const letkf_das_obs_args* g, const letkf_sea
   a.infl_sv = n;
   std::string path;
   for (int64_t p0 = 0; p0 < n;) {
-    int64_t p1 = p0 + 1;
-    while (p1 < n && (hoff[p1 + 1] - hoff[p0]) * 20 <= list_bytes) ++p1;
-    const size_t n1 = (size_t)std::max<int64_t>(hoff[p1] - hoff[p0], 1);
-    const size_t o_rd = (n1 * 4 + 255) & ~(size_t)255, o_rl = o_rd + ((n1 * 8 + 255) & ~(size_t)255);
-    if (int rc = grow(c, &c->list_ws, &c->list_ws_bytes, o_rl + n1 * 8 + 256)) return rc;
-    // list entry e of the chunk's target p at base[obs_off[p] + j] with the GLOBAL offsets: shift the bases
-    int32_t* idx = reinterpret_cast<int32_t*>(c->list_ws) - hoff[p0];
-    double* rd = reinterpret_cast<double*>(c->list_ws + o_rd) - hoff[p0];
-    double* rl = reinterpret_cast<double*>(c->list_ws + o_rl) - hoff[p0];
-    if (int rc = letkf_obs_search_dev(c, &tab, p1 - p0, o.ri + p0, o.rj + p0, o.rlev + p0, o.rz + p0, 1, nullptr, off + p0, idx, rd, rl))
+    const int64_t p1 = chunk_end(sw.hoff, p0, n, 1, 20, list_bytes);
+    ListSlab ls;
+    if (int rc = list_slab(c, sw.hoff[p0], sw.hoff[p1], &ls)) return rc;
+    if (int rc = letkf_obs_search_dev(c, &tab, p1 - p0, o.ri + p0, o.rj + p0, o.rlev + p0, o.rz + p0, 1, nullptr, sw.off + p0, ls.idx, ls.rd,
+                                      ls.rl))
       return rc;
     a.npts = p1 - p0;
-    a.obs_off = off + p0;
-    a.obs_idx = idx;
-    a.rdiag_l = rd;
-    a.rloc_l = rl;
+    a.obs_off = sw.off + p0;
+    a.obs_idx = ls.idx;
+    a.rdiag_l = ls.rd;
+    a.rloc_l = ls.rl;
     a.beta = g->beta ? g->beta + p0 : nullptr;
     a.infl = o.infl_ws + p0;
     a.gues = o.gues + p0;
@@ -1490,24 +1506,17 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
   if (nlim == 0) return LETKF_OK;
   const int ng = t->ngroup;
   const size_t ncg = (size_t)nij1 * ng;
-  // aux: counts [ncg + 1] int32 | goff [ncg + 1] int64 | scan scratch | roff [batch]
-  size_t scan_b = 0;
-  HIP_TRY(count_scan(nullptr, &scan_b, nullptr, nullptr, ncg + 1, c->stream));
-  const size_t o_off = ((ncg + 1) * 4 + 255) & ~(size_t)255, o_scan = o_off + (((ncg + 1) * 8 + 255) & ~(size_t)255);
-  const size_t o_roff = o_scan + ((scan_b + 255) & ~(size_t)255);
+  // aux: survivor counts and offsets per (column, group), and behind them roff | kref [ngroup] | min err [nctype] (general ring key)
   const size_t nring1 = (size_t)letkf::search_rings_count() + 1;   // ring starts per (column, group)
-  const size_t roff_b = (ncg * nring1 * 4 + 255) & ~(size_t)255;
-  const size_t o_kref = o_roff + roff_b;                            // kref [ngroup] | min err [nctype] (general ring key)
-  const size_t need_aux = o_kref + ((size_t)ng + (size_t)t->nctype) * 8 + 256;
-  if (int rc = grow(c, &c->ring_aux, &c->ring_aux_bytes, need_aux)) return rc;
-  int32_t* cnt = reinterpret_cast<int32_t*>(c->ring_aux);
-  int64_t* goff = reinterpret_cast<int64_t*>(c->ring_aux + o_off);
-  int32_t* roff = reinterpret_cast<int32_t*>(c->ring_aux + o_roff);
+  const size_t roff_b = align256(ncg * nring1 * 4);
+  ScanWs sw;
+  if (int rc = scan_ws(c, &c->ring_aux, ncg, roff_b + ((size_t)ng + (size_t)t->nctype) * 8, &sw)) return rc;
+  int32_t* roff = reinterpret_cast<int32_t*>(sw.tail);
   double* kref = nullptr;
   if (gen) {
     // reference offsets: the smallest offset an entry of the group can have -- criterion 2: -2 ln(largest factor); criterion 3:
     // 2 ln(smallest error^2 / factor) over the group's types (the smallest error of a type: one small kernel + a read-back)
-    kref = reinterpret_cast<double*>(c->ring_aux + o_kref);
+    kref = reinterpret_cast<double*>(sw.tail + roff_b);
     std::vector<double> emin(t->nctype, 1.0), kr(ng);
     if (t->criterion == 3) {
       HIP_TRY(letkf::launch_ctype_min_err(*t, kref + ng, c->stream));
@@ -1531,16 +1540,14 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
     // (a later call of the same letkf_das_columns_dev: same tables, same columns -- the ring-ordered survivors are still there)
     *taken = true;
     HIP_TRY(letkf::launch_search_rings(*t, 0, nij1, nij1, nlev, rlev, rz, fill, counts, reinterpret_cast<const long*>(obs_off), obs_idx,
-                                       rdiag_l, rloc_l, nobs_ctype, cutd_ctype, reinterpret_cast<const long*>(goff),
-                                       reinterpret_cast<double*>(c->ring_ws), roff, kref, c->num_cu, c->stream));
+                                       rdiag_l, rloc_l, nobs_ctype, cutd_ctype, reinterpret_cast<const long*>(sw.off),
+                                       reinterpret_cast<double*>(c->ring_ws.p), roff, kref, c->num_cu, c->stream));
     return LETKF_OK;
   }
-  HIP_TRY(hipMemsetAsync(cnt + ncg, 0, 4, c->stream));
-  HIP_TRY(letkf::launch_ring_survivors(*t, 0, nij1, rig, rjg, 0, cnt, nullptr, nullptr, nullptr, nullptr, c->num_cu, c->stream));
-  HIP_TRY(count_scan(c->ring_aux + o_scan, &scan_b, cnt, goff, ncg + 1, c->stream));
-  std::vector<int64_t> hoff(ncg + 1);
-  HIP_TRY(hipMemcpyAsync(hoff.data(), goff, (ncg + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(zero_total(c, sw));
+  HIP_TRY(letkf::launch_ring_survivors(*t, 0, nij1, rig, rjg, 0, sw.counts, nullptr, nullptr, nullptr, nullptr, c->num_cu, c->stream));
+  HIP_TRY(scan_offsets(c, sw));
+  if (int rc = offsets_to_host(c, sw)) return rc;
   if (c->limited_rings == 2) {
     // dense = more than one in twenty (column, limited group) pairs overflow the column kernel's LDS buffer and would take its
     // multi-sweep fall-back (20 x the cost of a pair that fits); while they fit, that kernel -- everything of a column resident,
@@ -1549,7 +1556,7 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
     for (size_t i = 0; i < ncg; ++i)
       if (mx[gmem[gstart[i % ng]]] > 0) {
         ++n_lim;
-        n_over += (hoff[i + 1] - hoff[i]) > (int64_t)letkf::search_rings_lds_survivors();
+        n_over += (sw.hoff[i + 1] - sw.hoff[i]) > (int64_t)letkf::search_rings_lds_survivors();
       }
     if (n_over * 20 <= n_lim) {
       if (c->ring_keep || !fill) {   // (remembered for the fill call of this pair / the later calls of this letkf_das_columns_dev)
@@ -1567,33 +1574,24 @@ int search_columns_rings(letkf_ctx* c, const letkf_search_tables* t, int64_t nij
   if (c->ring_keep) {
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
-    const size_t want = (size_t)hoff[ncg] * 32 + 256;
-    keep = want <= c->ring_ws_bytes + fr / 2;
-    if (keep && want > c->ring_ws_bytes) {
+    const size_t want = (size_t)sw.hoff[ncg] * 32 + 256;
+    keep = want <= c->ring_ws.cap + fr / 2;
+    if (keep && want > c->ring_ws.cap) {
       // the exact size (grow would ask for a quarter more), and a failure is no error: the batches below need 8 GiB
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (c->ring_ws) HIP_TRY(hipFree(c->ring_ws));
-      c->ring_ws = nullptr;
-      c->ring_ws_bytes = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&c->ring_ws), want) == hipSuccess) {
-        c->ring_ws_bytes = want;
-      } else {
+      if (int rc = drop(c, &c->ring_ws)) return rc;
+      if (alloc(&c->ring_ws, want) != hipSuccess) {
         (void)hipGetLastError();
-        c->ring_ws = nullptr;
         keep = false;
       }
     }
   }
-  const int64_t budget = keep ? hoff[ncg] * 32 + 256 : ((int64_t)c->ring_batch_mb << 20);
+  const int64_t budget = keep ? sw.hoff[ncg] * 32 + 256 : ((int64_t)c->ring_batch_mb << 20);
   int64_t c0 = 0;
   while (c0 < nij1) {
-    int64_t c1 = c0 + 1;
-    while (c1 < nij1 && (hoff[(size_t)(c1 + 1) * ng] - hoff[(size_t)c0 * ng]) * 32 <= budget) ++c1;
-    const int64_t nsv = hoff[(size_t)c1 * ng] - hoff[(size_t)c0 * ng];
-    const size_t need = (size_t)(nsv > 0 ? nsv : 1) * 32 + 256;
-    if (int rc = grow(c, &c->ring_ws, &c->ring_ws_bytes, need)) return rc;
-    double* sv = reinterpret_cast<double*>(c->ring_ws) - 4 * hoff[(size_t)c0 * ng];
-    const long* gq = reinterpret_cast<const long*>(goff + (size_t)c0 * ng);
+    const int64_t c1 = chunk_end(sw.hoff, c0, nij1, ng, 32, budget);
+    double* sv = nullptr;
+    if (int rc = survivor_slab(c, &c->ring_ws, sw.hoff[(size_t)c0 * ng], sw.hoff[(size_t)c1 * ng], &sv)) return rc;
+    const long* gq = reinterpret_cast<const long*>(sw.off + (size_t)c0 * ng);
     int32_t* rq = roff + (size_t)c0 * ng * nring1;
     HIP_TRY(letkf::launch_ring_survivors(*t, c0, c1 - c0, rig, rjg, 1, nullptr, gq, sv, rq, kref, c->num_cu, c->stream));
     HIP_TRY(letkf::launch_search_rings(*t, c0, c1 - c0, nij1, nlev, rlev, rz, fill, counts, reinterpret_cast<const long*>(obs_off),
@@ -1665,9 +1663,9 @@ int letkf_obs_mesh_sort_dev(letkf_ctx* c, const letkf_mesh* m, int64_t nobs, con
   size_t need = 0;
   long ns = 0;
   HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, nullptr, &need, c->num_cu, c->stream));
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
-  size_t have = c->scratch_bytes;
-  HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, c->scratch, &have, c->num_cu, c->stream));
+  if (int rc = grow(c, &c->scratch, need)) return rc;
+  size_t have = c->scratch.cap;
+  HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, c->scratch.p, &have, c->num_cu, c->stream));
   *nsorted = ns;
   return LETKF_OK;
 }
@@ -1793,8 +1791,8 @@ int letkf_monit_dep_dev(letkf_ctx* c, int32_t nid, const int32_t* elem_uid, int6
     return fail(LETKF_E_INVALID, "bad element table / outputs");
   if (nn > 0 && (!elm || !dep || !qc)) return fail(LETKF_E_INVALID, "an observation array is NULL");
   const size_t need = letkf::monit_scratch_bytes(nid, c->num_cu);
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
-  HIP_TRY(letkf::launch_monit_dep(nid, elem_uid, nn, elm, dep, qc, nobs, bias, rmse, c->scratch, c->num_cu, c->stream));
+  if (int rc = grow(c, &c->scratch, need)) return rc;
+  HIP_TRY(letkf::launch_monit_dep(nid, elem_uid, nn, elm, dep, qc, nobs, bias, rmse, c->scratch.p, c->num_cu, c->stream));
   return LETKF_OK;
 }
 
@@ -1903,8 +1901,8 @@ int letkf_members_alltoall_dev(letkf_ctx* c, void* nccl_comm, int32_t nranks, in
     ptot += pc[r];
   }
   const size_t need = (size_t)(ftot + ptot) * sizeof(double) + 256;
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, need)) return rc;
-  double* fbuf = reinterpret_cast<double*>(c->scratch);
+  if (int rc = grow(c, &c->scratch, need)) return rc;
+  double* fbuf = reinterpret_cast<double*>(c->scratch.p);
   double* pbuf = fbuf + ftot;
   const char* what = "";
   if (dir == 0) {   // member fields -> point-major state
@@ -2012,8 +2010,8 @@ int core_host(int ne, int nobs, int nobsl, const double* hdxb, const double* rdi
   // scratch layout (doubles): hdxb[n*k] rdiag[n] rloc[n] dep[n] depd[n] infl[1] trans[k*k] pao[k*k] transm[k] transmd[k] | ints: nobsl, status
   const size_t nd = n * k + 4 * n + 1 + 2 * k * k + 2 * k;
   const size_t bytes = nd * sizeof(double) + 4 * sizeof(int);
-  if (int rc = grow(c, &c->scratch, &c->scratch_bytes, bytes)) return rc;
-  double* d = reinterpret_cast<double*>(c->scratch);
+  if (int rc = grow(c, &c->scratch, bytes)) return rc;
+  double* d = reinterpret_cast<double*>(c->scratch.p);
   double* d_h = d;
   double* d_rdiag = d_h + n * k;
   double* d_rloc = d_rdiag + n;
