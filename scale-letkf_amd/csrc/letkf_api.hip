@@ -236,7 +236,7 @@ struct EventPair {   // timing events that do not outlive a failed launch
 //   family  serves                                                       kernels
 //   trio    mode 0, nv = 11, k <= 20, no per-point outputs (T, Pa,        letkf_trio_kernel (letkf_trio.hip): three points per wave
 //           w-bar), the trivial pre-pass ran; LETKF_OPT_SMALL_K_TRIO
-//   wave    k <= 100 and nv = 11 (modes 0, 2, 3) or nv = 0 (mode 1),      letkf_wave_kernel (letkf_wave.hip): one wave per point to
+//   wave    k <= 100 and nv = 11 (modes 0, 2, 3) or nv = 0 (mode 1),      letkf_wave_kernel (letkf_wave_dev.h): one wave per point to
 //           but not the staged path's eigen-free calls below               k = 62, two from 63
 //   staged  every other call with nv + 2 <= 16 right-hand sides;          Gram (matrix cores for mode 0, letkf_stage_gram_kernel for
 //           from k = 63 also mode 0 without T / Pa where                  the other modes and beyond k = 512) -> eigen-free stage
@@ -330,7 +330,7 @@ int prepare_wave(letkf_ctx* c, letkf::PointArgs& a, const Route& r, int warm_run
   if (const char* e = LETKF_KNOB("LETKF_AMD_WARM_DBG")) a.warm_dbg = std::atoi(e);
   a.prof = nullptr;
 #ifdef LETKF_CHECKED
-  {   // the violation record of the checked build (letkf_wave.hip LETKF_CHECK): code | workgroup | value | bound
+  {   // the violation record of the checked build (letkf_wave_dev.h LETKF_CHECK): code | workgroup | value | bound
     static unsigned long long* rec = nullptr;
     if (!rec) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rec), 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(rec, 0, 4 * sizeof(unsigned long long), c->stream));

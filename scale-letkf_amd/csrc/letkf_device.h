@@ -41,7 +41,14 @@ inline int resident_blocks(K kern, int block, size_t lds, int fallback) {
   return v;
 }
 
-// Plan of the solve kernel's dynamic run scheduling (letkf_wave.hip), worked out on the host for the grid that is
+// Grid of a grid-stride kernel over n items at `block` threads: one workgroup per block of items, capped at 16 per CU.
+inline int grid_for(long n, int block, int num_cu) {
+  long g = (n + block - 1) / block;
+  const long cap = (long)num_cu * 16;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// Plan of the solve kernels' dynamic run scheduling (letkf_sched_dev.h), worked out on the host for the grid that is
 // launched and read by the kernel from its arguments (scalar loads): per XCD range x of the unit ids
 //   base[x]  first unit id;  whole[x]  units handed out whole;  f[x]  units handed out in quarters (every t[x]-th of
 //   the range, last);  nstat[x]  hand-out positions given to the waves by their position in the grid (no counter);

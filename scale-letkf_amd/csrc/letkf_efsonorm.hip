@@ -21,11 +21,6 @@ namespace {
 
 constexpr int kNormRegK = 64;   // members held in registers by the one-read norm kernel (k <= 64); larger k reads twice
 
-inline int grid_for(long n, int num_cu) {
-  const long g = (n + 255) / 256, cap = (long)num_cu * 16;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 // lnorm's ensmn3d: a sequential sum over the members starting from 0, times rinbv = 1/k
 __device__ inline double member_mean(const double* __restrict__ x, long sm, int k, double rinbv) {
   double s = 0.0;
@@ -215,19 +210,19 @@ hipError_t sort_bins(void* temp, size_t* temp_bytes, const unsigned* keys, unsig
 hipError_t launch_efso_dpw(long nij1, int nlev, int k, const double* fcst_p, long sp, long sm, double rinbv, double* pbar,
                            double* w, unsigned* bad, int num_cu, hipStream_t st) {
   const long npts = nij1 * nlev;
-  hipLaunchKernelGGL(efso_pmean_kernel, dim3(grid_for(npts, num_cu)), dim3(256), 0, st, npts, k, fcst_p, sp, sm, rinbv, pbar);
+  hipLaunchKernelGGL(efso_pmean_kernel, dim3(grid_for(npts, 256, num_cu)), dim3(256), 0, st, npts, k, fcst_p, sp, sm, rinbv, pbar);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(efso_dpw_kernel, dim3(grid_for(nij1, num_cu)), dim3(256), 0, st, nij1, nlev, pbar, w, bad);
+  hipLaunchKernelGGL(efso_dpw_kernel, dim3(grid_for(nij1, 256, num_cu)), dim3(256), 0, st, nij1, nlev, pbar, w, bad);
   return hipGetLastError();
 }
 
 hipError_t launch_efso_norm(const EfsoNormArgs& a, int num_cu, hipStream_t st) {
   if (a.npts <= 0) return hipSuccess;
   if (a.k <= kNormRegK)
-    hipLaunchKernelGGL(efso_norm_kernel<kNormRegK>, dim3(grid_for(a.npts, num_cu)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(efso_norm_kernel<kNormRegK>, dim3(grid_for(a.npts, 256, num_cu)), dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL(efso_norm_kernel<0>, dim3(grid_for(a.npts, num_cu)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(efso_norm_kernel<0>, dim3(grid_for(a.npts, 256, num_cu)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -266,7 +261,7 @@ hipError_t launch_efso_summary(int nterm, long nobs, const double* obsense, cons
   hipError_t e = hipMemsetAsync(cnt, 0, ((size_t)nbins + 1) * 4, st);
   if (e != hipSuccess) return e;
   if (nobs > 0) {
-    hipLaunchKernelGGL(efso_bin_kernel, dim3(grid_for(nobs, num_cu)), dim3(256), 0, st, nobs, elm, typ, lat, qc, T, nobtype,
+    hipLaunchKernelGGL(efso_bin_kernel, dim3(grid_for(nobs, 256, num_cu)), dim3(256), 0, st, nobs, elm, typ, lat, qc, T, nobtype,
                        latbound, nbins, cnt, keys);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     size_t sb = sort_bytes;

@@ -50,7 +50,7 @@ namespace {
 
 typedef __attribute__((address_space(3))) double lds_double;
 
-using jacobi_dev::dpp_shift0;
+using lane_dev::dpp_mov0;
 using jacobi_dev::fast_rcp1;
 using jacobi_dev::fast_rsqrt;
 using jacobi_dev::fast_rsqrt1;
@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(64 * NP * SB, SB == 1 ? 2 : 1) letkf_eig_wg_ke
               // (register-only fences: without them hipcc fetches ALL rows of the neighbour first -- a third column in
               // registers; volatile asm statements keep their order, so each row's fetch waits for the previous row's FMA)
               asm volatile("" : "+v"(a[rr]));
-              const double pr = dpp_shift0<0x130>(a[rr]);    // lane + 1 (0 for lane 63 and for a switched-off lane)
+              const double pr = dpp_mov0<0x130>(a[rr]);    // lane + 1 (0 for lane 63 and for a switched-off lane)
               double q;
               if (rr < RBR) {
                 q = breg[rr < RBR ? rr : 0];
@@ -415,7 +415,7 @@ __global__ void __launch_bounds__(64 * NP * SB, SB == 1 ? 2 : 1) letkf_eig_wg_ke
               // the neighbour's rows are fetched a second time (once for the inner product, once here); laundering a[rr]
               // keeps hipcc from merging the two fetches across the barrier, and orders this row behind the previous one
               asm volatile("" : "+v"(a[rr]));
-              const double pr = dpp_shift0<0x130>(a[rr]);
+              const double pr = dpp_mov0<0x130>(a[rr]);
               // (the left neighbour's element comes from the lane next door for the LDS rows too -- it has just loaded it:
               // two vector moves instead of a second LDS read; the LDS pipe is this kernel's bottleneck)
               double q;
@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(64 * NP * SB, SB == 1 ? 2 : 1) letkf_eig_wg_ke
                 q = pfq[(rr - RBR) % kPF];
                 if (rr + kPF < RP) pfq[(rr - RBR) % kPF] = BT(rr + kPF - RBR);
               }
-              const double ql = dpp_shift0<0x138>(q);        // lane - 1 (0 for lane 0)
+              const double ql = dpp_mov0<0x138>(q);        // lane - 1 (0 for lane 0)
               if (rr < RBR) {
                 xpay_inplace(breg[rr < RBR ? rr : 0], coefR, pr);
               } else {

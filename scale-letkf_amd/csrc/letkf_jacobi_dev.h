@@ -1,21 +1,19 @@
 // letkf_jacobi_dev.h -- the in-register one-sided Jacobi eigensolver (row-split layout) and its small helpers, shared by
-// the wave kernel (letkf_wave.hip: the k x k problem of a grid point) and the large-k workgroup kernel
-// (letkf_kernels.hip: the 32 x 32 problems of its block Jacobi).  Device code only; everything is inlined.
+// the wave kernel (letkf_wave_dev.h: the k x k problem of a grid point), the three-point kernel (letkf_trio.hip: the same
+// rotations on a line shared by three points), the large-k workgroup kernel (letkf_kernels.hip: the 32 x 32 problems of its
+// block Jacobi) and the staged path's eigen stages (letkf_eig.hip, letkf_krylov.hip: tolerances, reciprocals, shifts).
+// The cross-lane primitives it builds on (DPP moves, wave_lds_sync) are letkf_lane_dev.h.  Device code only; everything is inlined.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "letkf_lane_dev.h"
 
 namespace letkf {
 namespace jacobi_dev {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
+using namespace lane_dev;   // wave_lds_sync, dpp_mov0 (the shifts wave_shl:1 0x130 / wave_shr:1 0x138: 0 where there is no source)
 
-// LDS written by some lanes of this wave, read by others: DS instructions of one wave execute in
-// order, so only the compiler has to be kept from reordering across the hand-off.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+typedef double v4d __attribute__((ext_vector_type(4)));
 
 // A grid point is solved by NW wavefronts (NW = 1: k <= 62, 4 independent points per 256-thread workgroup;
 // NW = 2: 62 < k <= 100, one point per 128-thread workgroup).  Hand-offs through LDS between lanes of the point:
@@ -111,14 +109,7 @@ __device__ __forceinline__ double fast_rcp(double x) {
 // instructions at k = 50).  The lanes of unused slots are switched off for the whole iteration: DPP reads from a
 // disabled lane return 0 (bound_ctrl), which is exactly the "no partner" case at both ends of the line.
 // ---------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ double dpp_shift0(double v) {     // wave_shl:1 (0x130) / wave_shr:1 (0x138), 0 if no source
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// The same shift with bound_ctrl = 0: a lane whose source lane does not exist or is switched off KEEPS `old`
+// The shift of dpp_mov0 with bound_ctrl = 0: a lane whose source lane does not exist or is switched off KEEPS `old`
 // (tools/ubench_dpp.hip probes both halves of the rule on the device).
 template <int CTRL>
 __device__ __forceinline__ double dpp_shift_keep(double old, double v) {
@@ -332,7 +323,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
               // (register-only fences keep the rows in order: without them hipcc fetches all rows of the neighbour
               // first -- a third column in registers after all)
               asm volatile("" : "+v"(xa[rr]));
-              const double pr = dpp_shift0<0x130>(xa[rr]);      // A of the right slot
+              const double pr = dpp_mov0<0x130>(xa[rr]);      // A of the right slot
               if (rr & 1) {
                 p1 = fma(xb[rr], pr, p1);
                 asm volatile("" : "+v"(p1));
@@ -344,7 +335,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
           } else {
 #pragma unroll
           for (int rr = 0; rr < H; ++rr) {
-            xb[rr] = dpp_shift0<0x130>(xf[rr]);                 // A of the right slot
+            xb[rr] = dpp_mov0<0x130>(xf[rr]);                 // A of the right slot
             if (rr & 1) p1 = fma(xa[rr], xb[rr], p1);
             else p0 = fma(xa[rr], xb[rr], p0);
           }
@@ -352,9 +343,9 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
           // (ENDS: the slot without a right partner reads its own B here.  Its `rot` is false, so tt = 0, c = wc = 1 and
           // tg = 0 exactly, and the unconditional update below gives alB + 0, isB * 1, scB * 1: the old values bit for bit.
           // Its h and g2 are both 0 and the tangent's intermediate is NaN, which the select on `rot` discards.)
-          const double alAr = ENDS ? dpp_shift_keep<0x130>(copy64(alB), alA) : dpp_shift0<0x130>(alA),
-                       isAr = ENDS ? dpp_shift_keep<0x130>(copy64(isB), isA) : dpp_shift0<0x130>(isA),
-                       scAr = ENDS ? dpp_shift_keep<0x130>(copy64(scB), scA) : dpp_shift0<0x130>(scA);
+          const double alAr = ENDS ? dpp_shift_keep<0x130>(copy64(alB), alA) : dpp_mov0<0x130>(alA),
+                       isAr = ENDS ? dpp_shift_keep<0x130>(copy64(isB), isA) : dpp_mov0<0x130>(isA),
+                       scAr = ENDS ? dpp_shift_keep<0x130>(copy64(scB), scA) : dpp_mov0<0x130>(scA);
           const double ga = slot_sum_nw<NW>(p0 + p1, lds, ph) * (isB * isAr);
           const double a = alB, b = alAr;
           const double g2 = ga * ga, ab = a * b;
@@ -371,7 +362,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
           const double c = fast_rsqrt(w);
           const double tg = tt * ga, wc = w * c;
           // what the right slot needs to rotate its A against this slot's (old) B
-          const double q1 = dpp_shift0<0x138>(-tt * scB);
+          const double q1 = dpp_mov0<0x138>(-tt * scB);
           // position 2m+1 takes c (g_Ar + t g_B), position 2m takes c (g_Bl - t g_A); 1.0 where there is no partner.
           // (ENDS: there tt and q1 are exactly 0 and the products' other factors finite, so the fused form gives exactly
           // 1.0; everywhere else the addend -0.0 leaves the product as it is to the last bit, signed zeros included.)
@@ -388,7 +379,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
             isA = nisA;
             scA = nscA;
           } else {
-            const double q2 = dpp_shift0<0x138>(isB * c), q3 = dpp_shift0<0x138>(scB * wc), q4 = dpp_shift0<0x138>(a - tg);
+            const double q2 = dpp_mov0<0x138>(isB * c), q3 = dpp_mov0<0x138>(scB * wc), q4 = dpp_mov0<0x138>(a - tg);
             if (hasR) {
               alB = b + tg;
               isB = isAr * c;
@@ -410,8 +401,8 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
 #pragma unroll
             for (int rr = 0; rr < H; ++rr) {
               asm volatile("" : "+v"(xa[rr]), "+v"(xb[rr]));
-              const double pr = dpp_shift0<0x130>(xa[rr]);
-              const double ql = dpp_shift0<0x138>(xb[rr]);
+              const double pr = dpp_mov0<0x130>(xa[rr]);
+              const double ql = dpp_mov0<0x138>(xb[rr]);
               // (three-address forms on the element's own register: hipcc's v_fmac accumulates into the FETCHED value's
               // register and copies the result back, one v_mov_b64 per element)
               asm("v_fma_f64 %0, %1, %0, %2" : "+v"(xb[rr]) : "v"(coefR), "v"(pr));
@@ -421,7 +412,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
 #pragma unroll
           for (int rr = 0; rr < H; ++rr) {
             xb[rr] = fma(coefR, xa[rr], xb[rr]);
-            xa[rr] = dpp_shift0<0x138>(xa[rr]);
+            xa[rr] = dpp_mov0<0x138>(xa[rr]);
             xa[rr] = fma(coefL, xf[rr], xa[rr]);
           }
           }

@@ -30,34 +30,21 @@
 
 #include "letkf_device.h"
 #include "letkf_jacobi_dev.h"
+#include "letkf_lane_dev.h"
 #include "letkf_staged_dev.h"
 
 namespace letkf {
 
 // ------------------------------------------------------------------ small helpers
-__device__ __forceinline__ double shfl_xor_d(double v, int mask) { return __shfl_xor(v, mask, 64); }
+using namespace lane_dev;     // wsum, wshfl_xor, dpp_mov0, wave_lds_sync, xcd_remap
+using jacobi_dev::fast_rcp;
 
-template <int W>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < W; m <<= 1) v += shfl_xor_d(v, m);
-  return v;
-}
-
-// DPP move of a double (VALU, no LDS crossbar): 0xB1 quad_perm[1,0,3,2], 0x4E quad_perm[2,3,0,1], 0x141 row_half_mirror
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov_d(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
 // sum over aligned groups of 8 lanes: lane^1, lane^2, then the mirror image inside the 8 (after the first two
 // steps every lane of a quad holds the quad sum, so "7 - lane" is as good as lane^4)
 __device__ __forceinline__ double group8_sum(double v) {
-  v += dpp_mov_d<0xB1>(v);
-  v += dpp_mov_d<0x4E>(v);
-  v += dpp_mov_d<0x141>(v);
+  v += dpp_mov0<0xB1>(v);
+  v += dpp_mov0<0x4E>(v);
+  v += dpp_mov0<0x141>(v);
   return v;
 }
 __device__ __forceinline__ double frsqrt2(double x) {   // v_rsq_f64 seed + 2 Newton steps
@@ -66,23 +53,6 @@ __device__ __forceinline__ double frsqrt2(double x) {   // v_rsq_f64 seed + 2 Ne
   y = fma(y * 0.5, e, y);
   e = fma(-x * y, y, 1.0);
   return fma(y * 0.5, e, y);
-}
-__device__ __forceinline__ double frcp2(double x) {     // v_rcp_f64 seed + 2 Newton steps
-  double r = __builtin_amdgcn_rcp(x);
-  double e = fma(-x, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-x, r, 1.0);
-  return fma(r, e, r);
-}
-
-// Bijective XCD-aware remap (blocks b and b+8 share an XCD and its L2): consecutive logical
-// work items go to the same XCD so neighbouring grid points, which read almost the same obs
-// rows, hit the same L2.  Speed only, never correctness.
-__device__ __forceinline__ long xcd_remap(long orig, long n) {
-  const long q = n >> 3, r = n & 7;
-  const long xcd = orig & 7, j = orig >> 3;
-  const long base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + j;
 }
 
 // round-robin (circle method) tournament: player m-1 fixed, step s in [0, m-1)
@@ -106,7 +76,7 @@ __device__ __forceinline__ void hestenes_cs(double a, double b, double g, double
   const double d = b - a;
   const double x = fma(d, d, 4.0 * g * g);
   const double hh = x * frsqrt2(x);
-  const double t = (2.0 * g) * copysign(1.0, d) * frcp2(fabs(d) + hh);
+  const double t = (2.0 * g) * copysign(1.0, d) * fast_rcp(fabs(d) + hh);
   c = frsqrt2(fma(t, t, 1.0));
   s = c * t;
 }
@@ -203,9 +173,9 @@ __device__ __forceinline__ int jacobi_stream(double* __restrict__ G, const int l
             be = fma(y, y, be);
             ga = fma(x, y, ga);
           }
-          al = group_sum<64>(al);
-          be = group_sum<64>(be);
-          ga = group_sum<64>(ga);
+          al = wsum(al);
+          be = wsum(be);
+          ga = wsum(ga);
           const double g2 = ga * ga, ab = al * be;
           if (g2 > kStopTol2 * ab) notconv = 1;
           if (g2 > kRotTol2 * ab) {
@@ -312,7 +282,7 @@ __device__ __forceinline__ int jacobi_block_mfma(double* __restrict__ G, const i
         for (int r = 0; r < 32; ++r) g[r] = 0.0;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          jacobi_dev::wave_lds_sync();
+          wave_lds_sync();
 #pragma unroll
           for (int reg = 0; reg < 4; ++reg) {
             const int a = q + 4 * reg;
@@ -324,13 +294,13 @@ __device__ __forceinline__ int jacobi_block_mfma(double* __restrict__ G, const i
               scr[c16 * 32 + 16 + a] = tJJ[reg];         // B[16 + a][16 + c16]
             }
           }
-          jacobi_dev::wave_lds_sync();
+          wave_lds_sync();
           if ((lane >> 4) == half) {
 #pragma unroll
             for (int r = 0; r < 32; ++r) g[r] = scr[c16 * 32 + r];
           }
         }
-        jacobi_dev::wave_lds_sync();
+        wave_lds_sync();
         // phantom columns (beyond k) are zero in Y: give them a unit diagonal so that they stay unit vectors of V
         {
           const int mycol = (lane < 16) ? 16 * I + lane : 16 * J + (lane - 16);
@@ -372,7 +342,7 @@ __device__ __forceinline__ int jacobi_block_mfma(double* __restrict__ G, const i
 #pragma unroll
             for (int l = i + 1; l < 32; ++l) g[l] = fma(-rdl(rij, l), f, g[l]);
           }
-          jacobi_dev::wave_lds_sync();
+          wave_lds_sync();
           const int tri = (lane * (lane + 1)) >> 1;
 #pragma unroll
           for (int l = 0; l < 32; ++l)
@@ -414,19 +384,19 @@ __device__ __forceinline__ int jacobi_block_mfma(double* __restrict__ G, const i
         double vop[8][2];
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          jacobi_dev::wave_lds_sync();
+          wave_lds_sync();
           if (lane < 32) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) scr[r * 32 + origin] = g[16 * half + r];
           }
-          jacobi_dev::wave_lds_sync();
+          wave_lds_sync();
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {
             vop[4 * half + s4][0] = scr[(4 * s4 + q) * 32 + c16];
             vop[4 * half + s4][1] = scr[(4 * s4 + q) * 32 + 16 + c16];
           }
         }
-        jacobi_dev::wave_lds_sync();
+        wave_lds_sync();
         // ---- 3. Y <- Y V, 16 rows at a time, in place (this wave owns these 32 columns for the round)
         const int rowa = c16;                            // A operand: row index inside the tile
         auto load_tile = [&](const int t, double (&a)[8]) {
@@ -719,8 +689,8 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
       }
       // adaptive-inflation sums: p1 = sum dep^2 w, p3 = sum rloc (threads < tn hold partials)
       if (A.infl_adaptive) {
-        p1 = group_sum<64>(p1);
-        p3 = group_sum<64>(p3);
+        p1 = wsum(p1);
+        p3 = wsum(p3);
         if ((tid & 63) == 0) {
           atomicAdd(&red[0], p1);
           atomicAdd(&red[1], p3);
@@ -741,7 +711,7 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
           double* gj = G + (size_t)j * ldg;
           double ss = 0.0;
           for (int r = lane; r < k; r += 64) ss = fma(gj[r], gj[r], ss);
-          ss = group_sum<64>(ss);
+          ss = wsum(ss);
           const double l = sqrt(ss);
           const double il = 1.0 / l;
           for (int r = lane; r < k; r += 64) gj[r] *= il;
@@ -769,8 +739,8 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
       }
 #pragma unroll
       for (int mk = 1; mk < 64; mk <<= 1) {
-        lmx = fmax(lmx, shfl_xor_d(lmx, mk));
-        lmn = fmin(lmn, shfl_xor_d(lmn, mk));
+        lmx = fmax(lmx, wshfl_xor(lmx, mk));
+        lmn = fmin(lmn, wshfl_xor(lmn, mk));
       }
       if (!jconv && A.max_sweep >= kMaxSweep) st = 1;   // (converging in the last permitted sweep is converged)
       else if (!(lmx > 0.0)) st = 2;
@@ -889,14 +859,14 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
         if (tid < 64) {
           double sm_ = 0.0;
           for (int mm = tid; mm < k; mm += 64) sm_ += X[v * k + mm];
-          sm_ = group_sum<64>(sm_);
+          sm_ = wsum(sm_);
           const double q_mean = sm_ / (double)k;
           double ss = 0.0;
           for (int mm = tid; mm < k; mm += 64) {
             const double d = X[v * k + mm] - q_mean;
             ss = fma(d, d, ss);
           }
-          ss = group_sum<64>(ss);
+          ss = wsum(ss);
           const double q_sprd = sqrt(ss / km1) / q_mean;
           for (int mm = tid; mm < k; mm += 64) {
             double val = X[v * k + mm];

@@ -44,7 +44,7 @@
 namespace letkf {
 
 using namespace staged_dev;
-using jacobi_dev::dpp_shift0;
+using lane_dev::dpp_mov0;
 
 namespace {
 
@@ -423,15 +423,15 @@ __device__ __forceinline__ bool krylov_point(const Slab& sl, const KryLds& L, co
       double u0 = rl == 0 && m > 0 ? 1.0 : 0.0, u1 = 0.0;     // T_0 e_1
       double y0 = L.cT[0] * u0, y1 = 0.0;
       // T_1
-      double nL = dpp_shift0<0x138>(u1), nR = dpp_shift0<0x130>(u0);
+      double nL = dpp_mov0<0x138>(u1), nR = dpp_mov0<0x130>(u0);
       double v0 = r0 ? fma(d0, u0, fma(eM, u1, eL * nL)) : 0.0;
       double v1 = r1 ? fma(d1, u1, fma(eM, u0, eR * nR)) : 0.0;
       y0 = fma(L.cT[1], v0, y0);
       y1 = fma(L.cT[1], v1, y1);
       const double d0_2 = 2.0 * d0, d1_2 = 2.0 * d1, eL2 = 2.0 * eL, eM2 = 2.0 * eM, eR2 = 2.0 * eR;
       for (int d = 2; d <= deg; ++d) {
-        nL = dpp_shift0<0x138>(v1);
-        nR = dpp_shift0<0x130>(v0);
+        nL = dpp_mov0<0x138>(v1);
+        nR = dpp_mov0<0x130>(v0);
         const double t0 = r0 ? fma(d0_2, v0, fma(eM2, v1, fma(eL2, nL, -u0))) : 0.0;
         const double t1 = r1 ? fma(d1_2, v1, fma(eM2, v0, fma(eR2, nR, -u1))) : 0.0;
         u0 = v0;

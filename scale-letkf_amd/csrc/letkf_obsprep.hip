@@ -198,12 +198,6 @@ __global__ void gather_i32_kernel(const long nrows, const int* __restrict__ src_
     dst[t] = src[src_row[t]];
 }
 
-inline int grid_for(long n, int block, int num_cu) {
-  long g = (n + block - 1) / block;
-  const long cap = (long)num_cu * 16;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 hipError_t launch_obs_departure(const letkf_qc_params& p, long nobs, const int* elm, const double* dat, const double* err,

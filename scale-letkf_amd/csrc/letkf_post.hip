@@ -132,12 +132,6 @@ __global__ void __launch_bounds__(256) addinfl_weight_kernel(const long nij1, co
   }
 }
 
-inline int grid_for(long n, int block, int num_cu) {
-  long g = (n + block - 1) / block;
-  const long cap = (long)num_cu * 16;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 size_t monit_scratch_bytes(int nid, int num_cu) { return (size_t)num_cu * 4 * nid * (2 * sizeof(double) + sizeof(int)) + 256; }

@@ -18,6 +18,7 @@
 #include "../../include/letkf_amd.h"
 #include "letkf_device.h"
 #include "letkf_divby_dev.h"
+#include "letkf_lane_dev.h"
 #include "letkf_search_dev.h"
 
 namespace letkf {
@@ -616,22 +617,9 @@ __device__ __forceinline__ unsigned int wave_max_u32(unsigned int v) {
 }
 // a wave-uniform value, said so: into scalar registers (what hipcc loads through the tables' plain pointers it keeps in
 // vector registers -- and spills to scratch inside the level loop)
-__device__ __forceinline__ int uni(const int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ double uni(const double x) {
-  const long long b = __double_as_longlong(x);
-  const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)b);
-  const unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// number of set bits of a wave mask below this lane (v_mbcnt_lo / _hi: two instructions)
-__device__ __forceinline__ int mbcnt(const unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using lane_dev::mbcnt;
+using lane_dev::uniform;
+using lane_dev::wave_lds_sync;
 
 // want-th smallest (1-based, want <= nreal) of the wave's keys held in REGISTERS (slot u of lane l = candidate 64 u + l;
 // kNoKey = none; every real key < 2^63), and how many of the keys equal to it belong to the selection.
@@ -867,8 +855,8 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
           }
       }
       wave_lds_sync();
-      ns = uni(ns);
-      overflow = uni((int)overflow) != 0;
+      ns = uniform(ns);
+      overflow = uniform((int)overflow) != 0;
       LP_ADD(0, LP_T() - lp0);
       LP_ADD(6, ns);
       const double cut_default = (t.criterion == 1) ? t.hori_loc[icm] * kDistZeroFac : 0.0;   // :1384-1389
@@ -882,18 +870,18 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
 #pragma unroll
       for (int mo = 0; mo < 4; ++mo) {
         const int ic = t.group_member[min(gs + mo, ge - 1)];
-        ic_m[mo] = uni(ic);
-        vm_m[mo] = uni(t.vmode[ic]);
-        vloc_m[mo] = uni(t.vert_loc[ic]);
-        varloc_m[mo] = uni(t.varloc[ic]);
+        ic_m[mo] = uniform(ic);
+        vm_m[mo] = uniform(t.vmode[ic]);
+        vloc_m[mo] = uniform(t.vert_loc[ic]);
+        varloc_m[mo] = uniform(t.varloc[ic]);
         if (varloc_m[mo] < 1e-290) fast = false;                  // (rloc may underflow to 0 inside the cut-off)
         if (vloc_m[mo] != 0.0 && !divby::in_range(vloc_m[mo])) fast = false;
       }
       const bool count_only = !A.fill && !L.cutd_ctype && nmax > 0;
-      const int mbeg1 = uni(mbeg[1]);                             // (INT_MAX: one member)
+      const int mbeg1 = uniform(mbeg[1]);                             // (INT_MAX: one member)
       double yv_m[2];
 #pragma unroll
-      for (int q = 0; q < 2; ++q) yv_m[q] = uni(divby::reciprocal(vloc_m[q]));
+      for (int q = 0; q < 2; ++q) yv_m[q] = uniform(divby::reciprocal(vloc_m[q]));
       double ndh2_r[kKeyS], vobs_r[kKeyS];
       if (fast) {
 #pragma unroll
@@ -956,14 +944,14 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
             }
           }
         } else {
-          const double vz = uni(A.rz[p]), vlnp = uni(log(A.rlev[p]));
-          const double lnrain = uni(log(t.rain_base));
+          const double vz = uniform(A.rz[p]), vlnp = uniform(log(A.rlev[p]));
+          const double lnrain = uniform(log(t.rain_base));
           double vref_m[4], vconst_m[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             vref_m[q] = (vloc_m[q] != 0.0) ? (vm_m[q] == 1 ? vz : vlnp) : 0.0;
             vconst_m[q] = 0.0;
-            if (vm_m[q] == 3 && vloc_m[q] != 0.0) vconst_m[q] = uni(fabs(lnrain - vref_m[q]) / vloc_m[q]);
+            if (vm_m[q] == 3 && vloc_m[q] != 0.0) vconst_m[q] = uniform(fabs(lnrain - vref_m[q]) / vloc_m[q]);
           }
           // ---- (1) vertical part: keys (limited group) or straight emission (no limit)
           int acc_n = 0;
@@ -1075,7 +1063,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
               // scalar unit, then the writes: walked slot by slot with the tie budget carried along, the
               // compare -> ballot -> count -> position chain of each slot waited for the one before)
               const bool ties = thresh != kNoKey;
-              tie_budget = uni(tie_budget);
+              tie_budget = uniform(tie_budget);
               unsigned long long mk[kKeyS], tk[kKeyS];
 #pragma unroll
               for (int u = 0; u < kKeyS; ++u) {
@@ -1550,7 +1538,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
             unsigned long long thresh = kNoKey;
             int tie_budget = 0;
             if (nreal > nmax) hist_thresh<kRingSlots>(keyr, kRingSlots * 64, nreal, nmax, hist, thresh, tie_budget, GEN ? 0.0 : 256.0 / 13.5);
-            tie_budget = uni(tie_budget);
+            tie_budget = uniform(tie_budget);
             const bool ties = thresh != kNoKey;
             int nl = 0;
 #pragma unroll
@@ -1686,7 +1674,7 @@ int search_rings_count() { return kRings; }
 int search_rings_lds_survivors() { return kSurvL; }
 
 // ------------------------------------------------------------------ the horizontal half of obs_local, once per column
-// (the list-free route of letkf_das_columns_dev; the vertical half runs inside the loop body kernel, letkf_wave.hip mode 3).
+// (the list-free route of letkf_das_columns_dev; the vertical half runs inside the loop body kernel, letkf_wave_dev.h mode 3).
 // One wave per column walks the rectangle of sorting-mesh cells of every combined type exactly like the column search and
 // keeps the rows inside the horizontal cut-off, in the reference's list order: entry = (row | ctype << 32 as bits, nd_h,
 // v_obs, err) with v_obs the observation's vertical coordinate in its ctype's mode (lev, ln lev, ln dat); the entries of a

@@ -1,5 +1,5 @@
 // letkf_search_dev.h -- device functions shared by the search kernel (letkf_search.hip) and the fused search of the
-// wave kernel (letkf_wave.hip): obs_local_cal (scale/letkf/letkf_tools.f90:1793-1906), ij_obsgrd_ext
+// wave kernel (letkf_wave_dev.h): obs_local_cal (scale/letkf/letkf_tools.f90:1793-1906), ij_obsgrd_ext
 // (scale/letkf/letkf_obs.f90:1209-1227) and the single-precision cut-off literals of letkf_obs.f90:27-28.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -213,12 +213,6 @@ __global__ void __launch_bounds__(256) assemble_kernel(const FileDev F, const lo
   }
 }
 
-inline int grid_for(long n, int block, int num_cu) {
-  long g = (n + block - 1) / block;
-  const long cap = (long)num_cu * 16;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------

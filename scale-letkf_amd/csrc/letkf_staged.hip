@@ -1,6 +1,6 @@
 // letkf_staged.hip -- the loop body of das_letkf (scale/letkf/letkf_tools.f90:313-527) and letkf_core
 // (common/common_letkf.f90:52-257) as THREE kernels over a batch of grid points, for ensemble sizes beyond the
-// one-/two-wave register kernel (letkf_wave.hip: k <= 100):
+// one-/two-wave register kernel (letkf_wave_dev.h: k <= 100):
 //
 //   1. letkf_stage_gram_kernel   local-obs gather + weights + the symmetric matrix M of the point's eigenproblem
 //   2. letkf_eig_wg_kernel (letkf_eig.hip, orders <= 208) / letkf_eig_block_kernel (letkf_kernels.hip, larger)

@@ -5,15 +5,12 @@
 #include <stdint.h>
 
 #include "letkf_device.h"
+#include "letkf_lane_dev.h"
 
 namespace letkf {
 namespace staged_dev {
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+using lane_dev::wsum;
 
 constexpr int kMaxNb = 16;     // right-hand sides: nv + 2 <= 16
 

@@ -1,9 +1,9 @@
 // letkf_trio.hip -- small ensembles (k <= 20: BASELINE configs[0], the k = 20 workloads): THREE grid points per wavefront.
 //
-// The register kernel of letkf_wave.hip gives one wave to one point; its row-split Jacobi keeps one column PAIR per slot of two
+// The register kernel of letkf_wave_dev.h gives one wave to one point; its row-split Jacobi keeps one column PAIR per slot of two
 // lanes, so at k = 20 ten slots -- 20 of 64 lanes -- work through the eigensolve (43 % of the wave time on C2-k20, 35 % on C1)
 // and every lane computes the rotation of its pair anew.  Here a wave takes three points at a time (below: which three):
-//   front (per point)   the Gram on the matrix cores as in letkf_wave.hip (one 16 x 16 tile of the first 16 members; members
+//   front (per point)   the Gram on the matrix cores as in letkf_wave_dev.h (one 16 x 16 tile of the first 16 members; members
 //                       16 .. 19 by broadcast FMAs, the departure columns by plain FMAs), written as the symmetric matrix
 //                       A = Ys^T Ys + (k-1)/rho I -- with r = Ys^T d and r_det beside it -- into the point's PARK in LDS
 //   eigensolve (once)   the same one-sided Jacobi, odd-even transposition ordering and rotations as jacobi_split, on a line of
@@ -15,15 +15,27 @@
 //                       (U = V^T B, C = D U, Out = V C), RTPS / RTPP, beta, q clamp, analysis members
 // The three points are the same level of three NEIGHBOURING RUNS (a scheduling unit is three runs), walked in step: each point's
 // eigenvectors stay in its park until the next point of ITS run is set up there, and warm-start it (G0 = A Q on the matrix
-// cores, as letkf_wave.hip's warm_start_product_mfma) -- no workspace in memory, the sweep count of the one-point kernel.
+// cores, as letkf_wave_dev.h's warm_start_product_mfma) -- no workspace in memory, the sweep count of the one-point kernel.
 // Serves mode 0 (lists) with nv = 11, no k x k / w-bar outputs, when the streaming pass owns the trivial points
-// (letkf_trivial.hip); everything else stays with letkf_wave.hip.  (scale/letkf/letkf_tools.f90:313-527, common_letkf.f90:52-258)
-#define LETKF_WAVE_UNIT3
-#include "letkf_wave.hip"
+// (letkf_trivial.hip); everything else stays with letkf_wave_dev.h.  (scale/letkf/letkf_tools.f90:313-527, common_letkf.f90:52-258)
+// The run scheduler is letkf_sched_dev.h, the cross-lane helpers letkf_lane_dev.h, the rotations letkf_jacobi_dev.h; the kernel of
+// letkf_wave_dev.h is described here only for comparison and is not part of this unit.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "letkf_device.h"
+#include "letkf_jacobi_dev.h"
+#include "letkf_lane_dev.h"
+#include "letkf_sched_dev.h"
 
 namespace letkf {
 
 namespace {
+
+using namespace jacobi_dev;
+using namespace lane_dev;
 
 // the wave's LDS slice (doubles).  P points per wave: 3 (the code is written for any P whose segments fit the line of 32 slots; with more
 // than three the staging batch shrinks to 192 observations so that the parks fit the 20 KB of a wave -- see launch_trio_kernel).
@@ -155,7 +167,7 @@ __device__ __forceinline__ void jacobi_trio(double* slice, const int k, const un
         {
           double p0 = 0.0, p1 = 0.0;
 #pragma unroll
-          for (int rr = 0; rr < H; ++rr) xb[rr] = dpp_shift0<0x130>(xf[rr]);   // A of the right slot
+          for (int rr = 0; rr < H; ++rr) xb[rr] = dpp_mov0<0x130>(xf[rr]);   // A of the right slot
           if (wrap) {                                                            // (wave-uniform)
             if (lane == 31) {
 #pragma unroll
@@ -167,7 +179,7 @@ __device__ __forceinline__ void jacobi_trio(double* slice, const int k, const un
             if (rr & 1) p1 = fma(xa[rr], xb[rr], p1);
             else p0 = fma(xa[rr], xb[rr], p0);
           }
-          const double alAr = dpp_shift0<0x130>(alA), isAr = dpp_shift0<0x130>(isA), scAr = dpp_shift0<0x130>(scA);
+          const double alAr = dpp_mov0<0x130>(alA), isAr = dpp_mov0<0x130>(isA), scAr = dpp_mov0<0x130>(scA);
           const double ga = slot_sum(p0 + p1) * (isB * isAr);
           const double a = alB, b = alAr;
           const double g2 = ga * ga, ab = a * b;
@@ -182,8 +194,8 @@ __device__ __forceinline__ void jacobi_trio(double* slice, const int k, const un
           const double w = fma(tt, tt, 1.0);
           const double c = fast_rsqrt(w);
           const double tg = tt * ga, wc = w * c;
-          const double q1 = dpp_shift0<0x138>(-tt * scB), q2 = dpp_shift0<0x138>(isB * c),
-                       q3 = dpp_shift0<0x138>(scB * wc), q4 = dpp_shift0<0x138>(a - tg);
+          const double q1 = dpp_mov0<0x138>(-tt * scB), q2 = dpp_mov0<0x138>(isB * c),
+                       q3 = dpp_mov0<0x138>(scB * wc), q4 = dpp_mov0<0x138>(a - tg);
           const double coefR = hasR ? tt * (isB * scAr) : 1.0;
           const double coefL = hasL ? q1 * isA : 1.0;
           if (hasR) {
@@ -199,7 +211,7 @@ __device__ __forceinline__ void jacobi_trio(double* slice, const int k, const un
 #pragma unroll
           for (int rr = 0; rr < H; ++rr) {
             xb[rr] = fma(coefR, xa[rr], xb[rr]);
-            xa[rr] = dpp_shift0<0x138>(xa[rr]);
+            xa[rr] = dpp_mov0<0x138>(xa[rr]);
           }
           if (wrap) {
             if (lane == 32) {
@@ -320,7 +332,7 @@ __device__ __forceinline__ TrioList trio_list(const PointArgs& A, const TrioHead
 template <int KR, int P>
 __device__ __forceinline__ int trio_front(const PointArgs& A, const TrioHead& hd, const TrioList& pl, const int sub, double* slice, const int k, const bool warm, TrioProf& pf) {
   using L = TrioLds<KR, P>;
-  constexpr int RS = KR - 16;                  // members of the narrow second block (letkf_wave.hip STRIP): 4 or 0
+  constexpr int RS = KR - 16;                  // members of the narrow second block (letkf_wave_dev.h STRIP): 4 or 0
   constexpr int NBLK = RS > 0 ? 2 : 1;
   constexpr int RSA = RS > 0 ? RS : 1;
   const int lane = threadIdx.x & 63;
@@ -410,7 +422,7 @@ __device__ __forceinline__ int trio_front(const PointArgs& A, const TrioHead& hd
 #ifndef TRIO_GRAM_DEPTH
 #define TRIO_GRAM_DEPTH 5
 #endif
-    constexpr int PD = TRIO_GRAM_DEPTH;                        // steps in flight (letkf_wave.hip run_steps: why it is written so)
+    constexpr int PD = TRIO_GRAM_DEPTH;                        // steps in flight (letkf_wave_dev.h run_steps: why it is written so)
     Step ts[PD];
 #pragma unroll
     for (int u = 0; u < PD; ++u) {
@@ -589,7 +601,7 @@ __device__ __forceinline__ int trio_front(const PointArgs& A, const TrioHead& hd
 }
 
 // ---------------------------------------------------------------------------------------------
-// back: spectra, status, inflation, apply phase on the matrix cores (letkf_wave.hip MAPPLY), analysis members.
+// back: spectra, status, inflation, apply phase on the matrix cores (letkf_wave_dev.h MAPPLY), analysis members.
 template <int KR, int P>
 __device__ __forceinline__ int trio_back(const PointArgs& A, const long pt, const int sub, double* slice, const int k, TrioProf& pf) {
   using L = TrioLds<KR, P>;
@@ -936,12 +948,7 @@ hipError_t launch_trio(const PointArgs& a, int num_cu, hipStream_t st) {
     if (b.run_len > want) b.run_len = (int)want;
   }
   sched_make_plan(b.plan, a.npts, a.warm_stride, b.run_len, grid, 4, 256, P);   // units of P runs
-  bool draws = false;
-  for (int x = 0; x < 8; ++x) draws = draws || b.plan.whole[x] + 4 * b.plan.f[x] > b.plan.nstat[x];
-  if (draws) {
-    hipError_t e = hipMemsetAsync(a.sched, 0, 512, st);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = sched_reset_counters(b.plan, a.sched, st)) return e;
   hipLaunchKernelGGL((letkf_trio_kernel<KR, P>), dim3(grid), dim3(256), lds, st, b);
   return hipGetLastError();
 }

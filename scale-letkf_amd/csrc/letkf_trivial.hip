@@ -4,7 +4,7 @@
 //   * no local observation (common/common_letkf.f90:89-107): T = sqrt(rho) I, w-bar = 0 in closed form; what is left is
 //     the relaxation (letkf_tools.f90:457-469, :1953-2002), the beta blend, the q clamp (:500-513) and the class copy of
 //     the inflation slot (:396-398).
-// The register kernels (letkf_wave.hip) give such a point a whole wavefront, lane = member: with the reference's
+// The register kernels (letkf_wave_dev.h) give such a point a whole wavefront, lane = member: with the reference's
 // point-fastest state (gues3d(nij1, nlev, nens, nv3d)) every one of its 11 x (k + 1) state values is an 8-byte access
 // npts * 8 bytes from the next -- 70 KB of cache lines fetched and as many written per point for 4.5 KB of data, ~30 us
 // of a wave's time, nothing to hide it behind.  On a domain whose observations sit in a radar disc most points are of
@@ -12,7 +12,7 @@
 // consecutive POINTS (of one variable): they read consecutive addresses of every member plane, so the pass runs at HBM speed.
 // PointArgs::skip_trivial tells the solve kernel that these points are done.
 //
-// The arithmetic follows the solve kernel's closed-form branch (letkf_wave.hip, `!solved`) statement by statement.
+// The arithmetic follows the solve kernel's closed-form branch (letkf_wave_dev.h, `!solved`) statement by statement.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>

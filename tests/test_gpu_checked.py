@@ -1,4 +1,4 @@
-"""The CHECKED twin of the library (scale-letkf_amd/Makefile CHECKED=1, csrc/letkf_wave.hip LETKF_CHECK): the column-survivor mode
+"""The CHECKED twin of the library (scale-letkf_amd/Makefile CHECKED=1, csrc/letkf_wave_dev.h LETKF_CHECK): the column-survivor mode
 of the loop-body kernel with every device-derived index tested against the host's buffer sizes.  Round 3 lost a test process to an
 abort inside letkf_das_columns_dev whose message pytest's capture swallowed; this is the run that says WHICH bound
 a launch violates instead of dying on it.  The twin is loaded in a process of its own (one library per process)."""

@@ -1,4 +1,4 @@
-"""The solve kernel's dynamic run scheduling (scale-letkf_amd/csrc/letkf_wave.hip: sched_make_plan on the host,
+"""The solve kernel's dynamic run scheduling (scale-letkf_amd/csrc/letkf_sched_dev.h: sched_make_plan on the host,
 sched_unit on the device) hands out every run of a launch exactly once -- whole, or as its four quarters -- whatever the
 problem size, run direction, run length and grid.  letkf_sched_plan_check builds the plan of such a launch and walks
 every hand-out position of every XCD range through the very function the kernel runs (it is compiled for both sides);
