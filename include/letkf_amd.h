@@ -584,6 +584,12 @@ int letkf_obs_allgatherv_dev(letkf_ctx *ctx, void *nccl_comm, int32_t nranks, in
  *                             slots mstart .. mstart + mcount - 1 of x (element (i, lev, m, v) at (i + nij1*lev)*sp + m*sm + v*sv).
  *                             dir 0 deals the fields to the slots, dir 1 assembles the fields from them; blocks of true size
  *                             (the reference pads to nij1max), packed / unpacked by the kernel of letkf_member_points_dev.
+ *                             A rank without points (nranks > nlon*nlat: nij1 = 0 on the high ranks, as nij1 = nij1max - 1 = 0 in
+ *                             common_mpi_scale.f90:267-273, where such a rank still enters MPI_ALLTOALL(V) with an empty v3d)
+ *                             TAKES PART with an empty state: x may be NULL there and only there, nothing is read from or
+ *                             written to it, and the rank still sends / receives the field of a member it holds.  It must
+ *                             make the call: its peers' groups count on it.  x == NULL on a rank that owns points is
+ *                             LETKF_E_INVALID.  mcount = 0 (an empty batch) returns LETKF_OK and posts nothing on any rank.
  * nranks = 1 needs no communicator (NULL): everything is the own block.  LETKF_E_INVALID when RCCL is not loadable. */
 int letkf_alltoallv_dev(letkf_ctx *ctx, void *nccl_comm, int32_t nranks, int32_t myrank, const int64_t *send_counts,
                         const int64_t *send_offs, const int64_t *recv_counts, const int64_t *recv_offs, int64_t row_bytes,

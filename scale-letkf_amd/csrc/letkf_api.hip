@@ -1883,13 +1883,17 @@ int letkf_members_alltoall_dev(letkf_ctx* c, void* nccl_comm, int32_t nranks, in
                                int64_t sp, int64_t sm, int64_t sv) {
   if (int rc = check_ctx(c)) return rc;
   if ((nranks > 1 && !nccl_comm) || nranks < 1 || myrank < 0 || myrank >= nranks || nlev < 1 || nlon < 1 || nlat < 1 || nv3d < 1 ||
-      mstart < 0 || mcount < 0 || mcount > nranks || !x || (dir != 0 && dir != 1))
+      mstart < 0 || mcount < 0 || mcount > nranks || (dir != 0 && dir != 1))
     return fail(LETKF_E_INVALID, "bad argument");
   const bool holder = myrank < mcount;                    // this rank holds / receives the whole field of member mstart + myrank
   if (holder && !v3dg) return fail(LETKF_E_INVALID, "v3dg is NULL on a rank that holds a member");
   const long nxy = (long)nlon * nlat;
   auto share = [&](int r) { return (nxy - r + nranks - 1) / nranks; };   // points r, r + nranks, ... (grd_to_buf)
   const long nij1 = share(myrank), npl = (long)nlev * nij1;
+  // a rank beyond the last point (nranks > nlon * nlat: nij1 = 0, common_mpi_scale.f90:267-273) has an empty state and still
+  // takes part: it may hold a member, and its peers' groups count on it
+  if (!x && nij1 > 0) return fail(LETKF_E_INVALID, "x is NULL on a rank that owns points");
+  if (mcount == 0) return LETKF_OK;                       // an empty batch: nothing to move, nothing posted
   std::vector<int64_t> fc(nranks), fo(nranks), pc(nranks), po(nranks);   // field side (all points of my member), point side (my points of every member)
   int64_t ftot = 0, ptot = 0;
   for (int r = 0; r < nranks; ++r) {

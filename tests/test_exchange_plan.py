@@ -4,7 +4,9 @@ driven with a RECORDING stand-in for RCCL behind its run-time binding (bind_rccl
 image first): every rank of a 4-rank job must post, inside ONE group, a send of its own rows to every rank (itself
 included) and a receive from every rank that has rows, at the rank-major offsets of the receive buffer obsbufr -- zero-count
 ranks neither send nor are received from, and byte counts beyond 2^31 stay exact.  No GPU is involved: the stand-in never
-touches the pointers.  (A one-GPU box cannot run more than one rank of the real thing; the driver's 8-GPU scaling run does.)"""
+touches the pointers, so no data moves here: the entries' nranks > 1 code on real buffers, with 2 .. 9 simulated ranks on one GPU
+and a loop-back stand-in that copies device memory, is tests/test_gpu_exchange_ranks.py.  (More than one rank of the real
+RCCL needs more than one GPU: the driver's 8-GPU scaling run.)"""
 import json
 import os
 import subprocess

@@ -1,9 +1,11 @@
 """The exchange entry of the library (C ABI section 8, letkf_obs_allgatherv_dev = MPI_ALLGATHERV of
 scale/letkf/letkf_obs.f90:1036-1046 as grouped ncclSend / ncclRecv) on a real RCCL communicator.  One GPU is all a test
 box has, so the communicator has one rank (send-to-self inside the group): that exercises the run-time binding of
-RCCL, the communicator hand-over from the host, stream ordering and the byte arithmetic; what every rank of an N-rank
-job posts is checked on the CPU against a recording stand-in for RCCL (tests/test_exchange_plan.py), the Python twin by
-tests/test_sharding_gloo.py.
+RCCL, the communicator hand-over from the host, stream ordering and the byte arithmetic.  More than one rank: what every
+rank of an N-rank job posts is checked on the CPU against a recording stand-in for RCCL (tests/test_exchange_plan.py), the
+entries' own nranks > 1 code runs on this one GPU with 2 .. 9 simulated ranks behind a loop-back stand-in that really moves
+the bytes (tests/test_gpu_exchange_ranks.py -- not RCCL: it proves the arithmetic, not that RCCL comes up on N devices), the
+Python twin is checked by tests/test_sharding_gloo.py.
 
 The communicator is created the way a host of the library creates it -- ncclGetUniqueId + ncclCommInitRank, as bench.py
 --exchange lib does -- in a fresh child process with RCCL's own log switched on.  History: in round 2 ncclCommInitAll,
