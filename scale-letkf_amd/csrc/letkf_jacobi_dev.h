@@ -8,6 +8,12 @@
 
 #include "letkf_lane_dev.h"
 
+// Warm-started runs hand their eigenvectors on sorted by eigenvalue (1, the default) or in the order the iteration stopped in
+// (-DLETKF_WARM_SORT=0, for an A/B twin): letkf_wave_dev.h warm_rank, letkf_trio.hip jacobi_trio.
+#ifndef LETKF_WARM_SORT
+#define LETKF_WARM_SORT 1
+#endif
+
 namespace letkf {
 namespace jacobi_dev {
 

@@ -253,15 +253,37 @@ __device__ __forceinline__ void jacobi_trio(double* slice, const int k, const un
     sb = slot_sum(sb);
     const double lamA = sqrt(sa), lamB = sqrt(sb);
     const double ilA = sa > 0.0 ? 1.0 / lamA : 0.0, ilB = sb > 0.0 ? 1.0 / lamB : 0.0;
+    int dstA = colA, dstB = colB;
+#if LETKF_WARM_SORT
+    {
+      // park the columns sorted by eigenvalue (letkf_wave_dev.h warm_rank: descending, ties by position, zero columns last; keys
+      // made unique by the position in their low 6 bits, so the ranks are a bijection of the point's own line positions whatever
+      // lam holds) instead of in the order the iteration stopped in: the next point of the run starts its line from them.  Every
+      // point is ranked inside its own segment; the lanes read are those of the segment, which are active together.
+      const unsigned keyA = (sa > 0.0 ? ((unsigned)__double2hiint(lamA) & ~63u) : 0u) | (unsigned)(63 - colA);
+      const unsigned keyB = (sb > 0.0 ? ((unsigned)__double2hiint(lamB) & ~63u) : 0u) | (unsigned)(63 - colB);
+      const int seg0 = slot - sin;                 // first lane of the segment (even-row half: both halves read the same keys)
+      dstA = dstB = 0;
+#pragma unroll
+      for (int i = 0; i < H; ++i) {
+        const int src = seg0 + (i < S ? i : 0);
+        const unsigned oa = (unsigned)__shfl((int)keyA, src, 64), ob = (unsigned)__shfl((int)keyB, src, 64);
+        if (i < S) {
+          dstA += (oa > keyA ? 1 : 0) + (ob > keyA ? 1 : 0);
+          dstB += (oa > keyB ? 1 : 0) + (ob > keyB ? 1 : 0);
+        }
+      }
+    }
+#endif
 #pragma unroll
     for (int rr = 0; rr < H; ++rr) {
-      base[colA * KR + 2 * rr + par] = xa[rr] * ilA;
-      base[colB * KR + 2 * rr + par] = xb[rr] * ilB;
+      base[dstA * KR + 2 * rr + par] = xa[rr] * ilA;
+      base[dstB * KR + 2 * rr + par] = xb[rr] * ilB;
     }
     if (par == 0) {
       double* lv = slice + L::lam + seg * 32;
-      lv[colA] = lamA;
-      lv[colB] = lamB;
+      lv[dstA] = lamA;
+      lv[dstB] = lamB;
     }
     // per point: sweeps, converged (the counters live in the ACTIVE lanes: the first lane of the point's segment writes them)
     if (sin == 0 && par == 0) {

@@ -481,6 +481,33 @@ __device__ __forceinline__ void warm_start_product_strip(double (&g)[KR], const 
   wave_lds_sync();
 }
 
+// Hand-over order of the eigenvectors (LETKF_WARM_SORT, default on; -DLETKF_WARM_SORT=0 gives the lane-order store for an A/B;
+// LETKF_AMD_WARM_DBG bit 4 selects it at run time).  Rotate-and-swap moves the columns along the line and a solve stops after a
+// partial cycle, so the lane order in which a point leaves its eigenvectors is a permutation that drifts further from any
+// order with every point of a run; cyclic Jacobi converges faster when neighbours on the line have the closest eigenvalues
+// (the large rotation angles are met in the first two steps of a cycle).  One-wave points therefore store the column of lane j
+// into workspace column warm_rank(j): eigenvalue descending, ties by lane, columns without an eigenvector (the inert zero
+// column of an odd k, lanes >= k) last.  The key is the high dword of lam with its low 6 bits replaced by 63 - lane: unique
+// per lane whatever the bits of lam are, so the rank is a bijection of the line's lanes for any input, NaN included, and
+// lanes outside the line keep their own column (they hold zeros, and so do all columns sorted last: the products find
+// their zero padding where it was).  Cost: readlane + compare + add-with-carry per line lane, 3 min(KR, 64) instructions
+// per point.  (The switch itself is letkf_jacobi_dev.h's: the three-point kernel parks its eigenvectors the same way.)
+template <int KR>
+__device__ __forceinline__ int warm_rank(const double lam, const bool colvalid, const int lane) {
+  constexpr int NLN = KR < 64 ? KR : 64;       // lanes of the line
+  const unsigned tie = 63u - (unsigned)(lane & 63);
+  unsigned key = colvalid ? (((unsigned)__double2hiint(lam) & ~63u) | tie) : tie;
+  int rank = 0;
+#pragma unroll
+  for (int i = 0; i < NLN; ++i) {
+    // (8 keys in scalar registers at a time: left alone hipcc reads all NLN lanes first, and the scalar registers that takes
+    // are paid for in the apply phase, which then re-loads the kernel arguments 58 times per point instead of keeping them)
+    if ((i & 7) == 0) asm volatile("" : "+v"(key), "+v"(rank));
+    rank += ((unsigned)__builtin_amdgcn_readlane((int)key, i) > key) ? 1 : 0;
+  }
+  return lane < NLN ? rank : lane;
+}
+
 // smallest k the instantiation <KR, NW> is dispatched for (launch_wave_kernel walks the instances in this order)
 __host__ __device__ constexpr int wave_kmin(int KR, int NW) {
   return NW == 1 ? (KR == 16 ? 1 : KR == 20 ? 17 : KR == 32 ? 17 : KR == 48 ? 33 : KR == 50 ? 49 : KR == 64 ? 51 : 1)
@@ -1443,6 +1470,11 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         // (the pointer is laundered every 8 rows: otherwise all KR row addresses are hoisted out of the point loop
         // as 64-bit values, spilled, and reloaded one by one in front of each store -- same serialisation)
         unsigned long long pa = reinterpret_cast<unsigned long long>(uws);
+        if constexpr (LETKF_WARM_SORT && NW == 1) {
+          // column `lane` goes to workspace column warm_rank (sorted by eigenvalue); warm_dbg bit 4: lane order
+          const int rk = warm_rank<KR>(lam, colvalid, lane);
+          pa += (long long)(((A.warm_dbg & 16) ? lane : rk) - lane) * (long long)sizeof(double);
+        }
 #pragma unroll
         for (int r = 0; r < KR; ++r) {
           if ((r & 7) == 0) asm volatile("" : "+v"(pa));
