@@ -620,7 +620,8 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_krylov
     }
     const int ldg = staged_ld(m);
     if (tid < 16) sl.G[(size_t)m * ldg + tid] = 0.0;         // (read as padding columns of the last rows: must be finite)
-    if (ldg > m + 1) {                                       // rows padded to the alignment: the padding is read against zero rows of the residual block
+    if (ldg > m) {                                           // padded rows (an even order's one word of m | 1 too): the padding is read against
+                                                             // zero rows of the residual block, and 0 x NaN left by an earlier call is NaN
       const int npad = ldg - m;
       for (int e = tid; e < m * npad; e += nthr) sl.G[(size_t)(e / npad) * ldg + m + e % npad] = 0.0;
     }

@@ -33,6 +33,7 @@ ROUTES = {
     "staged_poly_nv7": (20, 7, None, ["staged:", "letkf_stage_krylov_kernel"], []),
     "staged_wg": (144, 11, "trans", ["staged:", "letkf_eig_wg_kernel"], ["letkf_eig_block_kernel", "krylov"]),
     "staged_block": (250, 11, None, ["staged:", "letkf_eig_block_kernel"], []),
+    "staged_block_nopoly": (250, 11, "nopoly", ["staged:", "/ letkf_eig_block_kernel"], ["krylov"]),
     "point": (20, 15, None, ["letkf_point_kernel"], []),
     "point_big": (144, 15, None, ["letkf_point_kernel<BIG>"], []),
 }
