@@ -15,6 +15,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/letkf_amd.h"
 #include "letkf_device.h"
 #include "letkf_divby_dev.h"
@@ -353,17 +355,50 @@ __global__ void __launch_bounds__(256) letkf_search_kernel(const SearchArgs A) {
   }
 }
 
+// a wave-uniform value, said so: into scalar registers (what hipcc loads through the tables' plain pointers it keeps in
+// vector registers -- and spills to scratch inside the level loop)
+using lane_dev::mbcnt;
+using lane_dev::readlane_d;
+using lane_dev::uniform;
+using lane_dev::wave_lds_sync;
+
 // ---------------------------------------------------------------------------------------------
 // Column-cooperative search (no-limit mode): one wavefront per horizontal point ij does ALL its levels.
 // The horizontal part of obs_local_cal (two subtractions, a square root, a division, the cut-off test) depends only
 // on (ij, observation), so it is evaluated once per column and observation instead of once per level (60 times at
-// C2); the survivors wait in LDS with everything the vertical part needs (row, nd_h, the vertical coordinate already
-// through its log where the type calls for one, the error) and every level then runs only
+// C2); the survivors wait in LDS with everything the vertical part needs (nd_h, the vertical coordinate already
+// through its log where the type calls for one; for the lists also the row and the error) and every level then runs only
 //   nd_v = |v_obs - v_point| / vert_loc,  nd = nd_h^2 + nd_v^2,  rloc = varloc exp(-nd/2),  rdiag = err^2 / rloc
-// over them.  Same expressions in the same order as local_cal_v (compiled without fusion), same candidate order, so
-// the lists are identical to the per-point kernel's, entry for entry.
+// over them.  Same expressions in the same order as local_cal_v (compiled without fusion; the quotient through
+// letkf_divby_dev.h, which is the division's own value), same candidate order, so the lists are identical to the
+// per-point kernel's, entry for entry.
+//
+// The two passes of the CSR build walk the buffered survivors differently:
+//   count (FILL = false)  lane = LEVEL.  Only acceptance is asked, and inside the cut-off the weight cannot vanish
+//     (nd <= 13.3: exp(-nd / 2) >= 1.2e-3) unless the type's variable localisation sits at the bottom of the exponent
+//     range (not wsafe).  So every lane keeps its own level's reference coordinate and a private counter, and the wave
+//     reads survivor after survivor as an LDS broadcast: three compares per (level, survivor), no ballot, no
+//     popcount, no per-level LDS traffic, levels in groups of 64.  Types that are not wsafe need the exponential to
+//     decide and go lane = survivor, level by level; so does a call with so few levels (a slab) that most lanes would
+//     hold none.
+//   fill (FILL = true)  lane = SURVIVOR, level by level, in two steps.  The cut-off tests run over the 64-wide
+//     survivor chunks, of which well under half the lanes pass at a level (C2: ~203 of ~480); who passes is queued
+//     (survivor slot and nd) in a small per-wave LDS ring by ballot prefix, in order.  Whenever 64 are queued, and at
+//     the end of the level, ONE full wave evaluates the exponential and the error division -- four fifths of the
+//     instructions -- tests rloc != 0 and appends to the level's list.
 // ---------------------------------------------------------------------------------------------
-constexpr int kSurv = 512;                  // survivors buffered per wave (32 B each)
+#ifndef LETKF_COL_SURV_FILL
+#define LETKF_COL_SURV_FILL 384
+#endif
+constexpr int kSurv = 512;                    // survivors buffered per wave, counting pass: 16 B each, 4 workgroups per CU
+constexpr int kSurvFill = LETKF_COL_SURV_FILL;   // ... fill pass: 28 B each; with the ring 3 workgroups per CU
+constexpr int kColQueue = 128;                // ring of accepted candidates (12 B each): < 64 waiting + <= 64 of one chunk
+static_assert(kSurv % 64 == 0 && kSurvFill % 64 == 0 && kSurvFill <= kSurv, "survivor buffers hold whole chunks");
+
+// LDS bytes per wave (a multiple of 16)
+__host__ __device__ constexpr size_t col_wave_bytes(const bool fill, const int nlev) {
+  return (fill ? (size_t)kSurvFill * 28 + kColQueue * 12 : (size_t)kSurv * 16) + 8 * (size_t)((nlev + 1) & ~1);
+}
 
 struct ColArgs {
   letkf_search_tables t;
@@ -382,37 +417,67 @@ struct ColArgs {
   int* nobs_ctype;       // [npts][nctype] accepted rows per combined type (nobsl_t of obs_local), or null
 };
 
+// Inside both cut-offs of obs_local_cal's vertical part?  nd is the squared distance.  MODE names how nd_v comes about, so
+// that the loops over the survivors are free of branches (hipcc does not hoist the wave-uniform tests out of them):
+//   0  nd_v is the level's constant ndv_c (no vertical localisation, or the rain-base mode);
+//   1  |v_obs - v_ref| / vloc through the refined reciprocal yv (letkf_divby_dev.h: the division's own value);
+//   2  the division itself (a vertical scale outside divby's range).
+template <int MODE>
+__device__ __forceinline__ bool col_cutoff(const double2 hv, const double vref, const double ndv_c, const double vloc,
+                                           const double yv, double& nd) {
+#pragma clang fp contract(off)
+  double nd_v;
+  if (MODE == 0) {
+    nd_v = ndv_c;                                                 // :1851-1865
+  } else {
+    const double a = fabs(hv.y - vref);
+    nd_v = MODE == 1 ? divby::quotient(a, vloc, yv) : a / vloc;
+  }
+  nd = hv.x * hv.x + nd_v * nd_v;                                 // :1888
+  return !(nd_v > kDistZeroFac) && !(nd > kDistZeroFacSq);        // :1869, :1891
+}
+
 // FILL = false is the counting pass of the two-phase CSR build: no weights are needed there, only whether a row is accepted.
 template <bool FILL>
 __global__ void __launch_bounds__(256) letkf_search_columns_kernel(const ColArgs A) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double smem_col[];
+  constexpr int kS = FILL ? kSurvFill : kSurv;
   const letkf_search_tables& t = A.t;
   const int lane = threadIdx.x & 63;
   // (scalar: one column / point per WAVE -- derived from threadIdx alone hipcc takes everything that hangs on it, the
   // mesh walk, the survivor counts, the select's loop, for divergent and wraps it in exec-mask loops)
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nlev = A.nlev;
-  const int cstride = 4 * kSurv + 2 * ((nlev + 1) & ~1);         // doubles per wave: survivors + 2 level counter arrays
-  double* sb = smem_col + (size_t)wv * cstride;                  // [kSurv][4]: row bits, nd_h, v_obs, err
-  int* cntl = reinterpret_cast<int*>(sb + 4 * kSurv);            // [nlev] entries emitted so far per level
-  int* cprev = cntl + 2 * ((nlev + 1) & ~1);                     // [nlev] the same at the start of the current ctype
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int nl2 = (nlev + 1) & ~1;
+  char* wb = reinterpret_cast<char*>(smem_col) + (size_t)wv * col_wave_bytes(FILL, nlev);
+  double2* s_hv = reinterpret_cast<double2*>(wb);                 // [kS] nd_h, v_obs
+  double* s_err = reinterpret_cast<double*>(s_hv + kS);           // [kS]        (the fill pass's from here ...
+  double* q_nd = s_err + kS;                                      // [kColQueue] nd of a queued candidate
+  int* s_row = reinterpret_cast<int*>(q_nd + kColQueue);          // [kS]
+  int* q_si = s_row + kS;                                         // [kColQueue] its survivor slot   ... to here)
+  int* cntl = FILL ? q_si + kColQueue : reinterpret_cast<int*>(s_hv + kS);   // [nlev] entries accepted so far per level
+  int* cprev = cntl + nl2;                                        // [nlev] the same at the start of the current ctype
+  // lane = level pays while at least half of the lanes of its level groups hold a level (a slab of 6 levels would keep 6
+  // lanes busy); below that the counting pass goes lane = survivor as well
+  const bool by_level = !FILL && 2 * nlev >= 64 * ((nlev + 63) / 64);
 
   for (long col = (long)blockIdx.x * 4 + wv; col < A.nij1; col += (long)gridDim.x * 4) {
     const double ri = A.rig[col], rj = A.rjg[col];
     for (int l = lane; l < nlev; l += 64) cntl[l] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     for (int m = 0; m < t.group_start[t.ngroup]; ++m) {
       const int ic = t.group_member[m];
-      const double varloc = t.varloc[ic];
+      const double varloc = uniform(t.varloc[ic]);
       if (varloc < kTiny) continue;                               // local_cal :1843
-      const int vm = t.vmode[ic];
+      const int vm = uniform(t.vmode[ic]);
+      // inside the cut-off nd <= 13.3, exp(-nd / 2) >= 1.2e-3, so the weight cannot vanish unless the variable
+      // localisation is itself at the bottom of the exponent range: only then does counting need the exponential
       const bool wsafe = varloc > 1e-290;
-      const double vloc = t.vert_loc[ic], hloc = t.hori_loc[ic];
+      const double vloc = uniform(t.vert_loc[ic]), hloc = t.hori_loc[ic];
+      const bool fdiv = divby::in_range(vloc);
+      const double yv = uniform(divby::reciprocal(fdiv ? vloc : 1.0));
       const double dzi = hloc * kDistZeroFac / t.dx, dzj = hloc * kDistZeroFac / t.dy;
       int imin, imax, jmin, jmax;
       ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
@@ -428,72 +493,125 @@ __global__ void __launch_bounds__(256) letkf_search_columns_kernel(const ColArgs
       if (A.nobs_ctype)
         for (int l = lane; l < nlev; l += 64) cprev[l] = cntl[l];
 
-      // every level against the buffered survivors, then the buffer is empty again
-      auto vertical = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int lev = 0; lev < nlev; ++lev) {
-          const long p = col + A.nij1 * (long)lev;
-          double vref = 0.0;
-          if (vloc != 0.0) {
-            if (vm == 1) vref = A.rz[p];
-            else vref = log(A.rlev[p]);
-          }
-          const double vconst = (vm == 3 && vloc != 0.0) ? fabs(log(t.rain_base) - vref) / vloc : 0.0;
-          int emitted = cntl[lev];
-          const long out = FILL ? A.obs_off[p] : 0;
-          for (int s0 = 0; s0 < ns; s0 += 64) {
-            const int si = s0 + lane;
-            bool acc = false;
-            double rloc = 0.0, rdiag = 0.0;
-            int row = 0;
-            if (si < ns) {
-              const double2 a2 = *reinterpret_cast<const double2*>(&sb[4 * si]);
-              const double2 b2 = *reinterpret_cast<const double2*>(&sb[4 * si + 2]);
-              row = (int)__double_as_longlong(a2.x);
-              const double nd_h = a2.y;
-              double nd_v;
-              if (vloc == 0.0) nd_v = 0.0;                        // :1851-1865
-              else if (vm == 3) nd_v = vconst;
-              else nd_v = fabs(b2.x - vref) / vloc;
-              if (!(nd_v > kDistZeroFac)) {                       // :1869
-                const double nd = nd_h * nd_h + nd_v * nd_v;      // :1888
-                if (!(nd > kDistZeroFacSq)) {                     // :1891
-                  if (FILL || !wsafe) {
-                    rloc = varloc * exp(-0.5 * nd);               // :1899
-                    rdiag = b2.y * b2.y / rloc;                   // :1903
-                    acc = rloc != 0.0;                            // letkf_tools.f90:1460
-                  } else {
-                    // counting pass: inside the cut-off nd <= 13.3, exp(-nd / 2) >= 1.2e-3, so the weight cannot vanish
-                    // unless the variable localisation is itself at the bottom of the exponent range (wsafe): the
-                    // exponential and the division -- half of this loop's instructions -- are the fill pass's alone
-                    acc = true;
-                  }
-                }
-              }
-            }
-            const unsigned long long mk = __ballot(acc);
-            if (FILL && acc) {
-              const long o = out + emitted + __popcll(mk & lt_mask);
-              A.obs_idx[o] = row;
-              A.rdiag_l[o] = rdiag;
-              A.rloc_l[o] = rloc;
-            }
-            emitted += __popcll(mk);
-          }
-          if (lane == 0) cntl[lev] = emitted;
+      // the level's reference coordinate and the vertical distance of the modes that have one per level (:1851-1865)
+      auto level_ref = [&](const long p, double& vref, double& ndv_c) {
+        vref = 0.0;
+        if (vloc != 0.0) {
+          if (vm == 1) vref = A.rz[p];
+          else vref = log(A.rlev[p]);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        ns = 0;
+        ndv_c = (vm == 3 && vloc != 0.0) ? fabs(log(t.rain_base) - vref) / vloc : 0.0;
       };
 
-      for (int j = jmin; j <= jmax; ++j) {
-        const int lo = t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-        const int hi = t.ac_ext[acb + imax + (long)ld * (j - 1)];
-        for (int base = lo; base < hi; base += 64) {
+      // every level against the buffered survivors, then the buffer is empty again
+      auto vertical_mode = [&](auto mode_c) {
+        constexpr int MODE = decltype(mode_c)::value;
+        wave_lds_sync();
+        if (!FILL && wsafe && by_level) {
+          // ---- count, lane = level: the survivors pass by as broadcast reads
+          for (int l0 = 0; l0 < nlev; l0 += 64) {
+            const int lev = min(l0 + lane, nlev - 1);             // (the lanes past the last level count it again, for nothing)
+            double vref, ndv_c;
+            level_ref(col + A.nij1 * (long)lev, vref, ndv_c);
+            int c = 0;
+#pragma unroll 4
+            for (int s = 0; s < ns; ++s) {
+              double nd;
+              c += col_cutoff<MODE>(s_hv[s], vref, ndv_c, vloc, yv, nd) ? 1 : 0;
+            }
+            if (l0 + lane < nlev) cntl[l0 + lane] += c;
+          }
+        } else {
+          // ---- lane = survivor, level by level.  What a level brings along (reference coordinate, list start, entries so
+          // far) is fetched for 64 levels at once, one per lane, and handed to the wave by v_readlane: one wait for memory
+          // per flush instead of one per level (rz / rlev / obs_off of a column's levels lie nij1 elements apart)
+          int head = 0;                                           // start of the ring
+          for (int l0 = 0; l0 < nlev; l0 += 64) {
+            const int ll = min(l0 + lane, nlev - 1);
+            const long pl = col + A.nij1 * (long)ll;
+            double vref_v, ndv_v;
+            level_ref(pl, vref_v, ndv_v);
+            const long out_v = FILL ? A.obs_off[pl] : 0;
+            int cnt_v = cntl[ll];
+            const int nl = min(64, nlev - l0);
+            for (int k = 0; k < nl; ++k) {
+              const double vref = readlane_d(vref_v, k), ndv_c = readlane_d(ndv_v, k);
+              int emitted = __builtin_amdgcn_readlane(cnt_v, k);
+              if (FILL) {
+                const long out = ((long)__builtin_amdgcn_readlane((int)(out_v >> 32), k) << 32) |
+                                 (unsigned int)__builtin_amdgcn_readlane((int)out_v, k);
+                int nq = 0;                                       // queued
+                // the first n <= 64 of the ring: weights, the rloc != 0 test, the three stores
+                auto drain = [&](const int n) {
+                  wave_lds_sync();
+                  bool acc = false;
+                  double rloc = 0.0, rdiag = 0.0;
+                  int row = 0;
+                  if (lane < n) {
+                    const int q = (head + lane) & (kColQueue - 1);
+                    const int si = q_si[q];
+                    const double nd = q_nd[q], err = s_err[si];
+                    row = s_row[si];
+                    rloc = varloc * exp(-0.5 * nd);                 // :1899
+                    rdiag = err * err / rloc;                       // :1903
+                    acc = rloc != 0.0;                              // letkf_tools.f90:1460
+                  }
+                  const unsigned long long mk = __ballot(acc);
+                  if (acc) {
+                    const long o = out + emitted + mbcnt(mk);
+                    A.obs_idx[o] = row;
+                    A.rdiag_l[o] = rdiag;
+                    A.rloc_l[o] = rloc;
+                  }
+                  emitted += __popcll(mk);
+                  head = (head + n) & (kColQueue - 1);
+                  nq -= n;
+                };
+                for (int s0 = 0; s0 < ns; s0 += 64) {
+                  const int si = s0 + lane;
+                  double nd = 0.0;
+                  bool cand = false;
+                  if (si < ns) cand = col_cutoff<MODE>(s_hv[si], vref, ndv_c, vloc, yv, nd);
+                  const unsigned long long mk = __ballot(cand);
+                  if (cand) {
+                    const int q = (head + nq + mbcnt(mk)) & (kColQueue - 1);
+                    q_nd[q] = nd;
+                    q_si[q] = si;
+                  }
+                  nq += __popcll(mk);
+                  if (nq >= 64) drain(64);
+                }
+                if (nq > 0) drain(nq);
+              } else {
+                for (int s0 = 0; s0 < ns; s0 += 64) {
+                  const int si = s0 + lane;
+                  double nd = 0.0;
+                  bool acc = false;
+                  if (si < ns) acc = col_cutoff<MODE>(s_hv[si], vref, ndv_c, vloc, yv, nd);
+                  if (!wsafe && acc) acc = varloc * exp(-0.5 * nd) != 0.0;   // :1899, letkf_tools.f90:1460
+                  emitted += __popcll(__ballot(acc));
+                }
+              }
+              if (lane == k) cnt_v = emitted;
+            }
+            if (l0 + lane < nlev) cntl[l0 + lane] = cnt_v;
+          }
+        }
+        wave_lds_sync();
+        ns = 0;
+      };
+      auto vertical = [&]() {
+        if (vloc == 0.0 || vm == 3) vertical_mode(std::integral_constant<int, 0>{});
+        else if (fdiv) vertical_mode(std::integral_constant<int, 1>{});
+        else vertical_mode(std::integral_constant<int, 2>{});
+      };
+
+      // one round past the last mesh row: the flush of what is left
+      for (int j = jmin; j <= jmax + 1; ++j) {
+        const bool last = j > jmax;
+        const int lo = last ? 0 : t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
+        const int hi = last ? 0 : t.ac_ext[acb + imax + (long)ld * (j - 1)];
+        for (int base = lo; base < hi || (last && base == 0 && ns > 0); base += 64) {
           const int row = base + lane;
           bool ok = false;
           double nd_h = 0.0, vobs = 0.0, err = 0.0;
@@ -508,29 +626,29 @@ __global__ void __launch_bounds__(256) letkf_search_columns_kernel(const ColArgs
                 else if (vm == 2) vobs = log(t.ob_dat[row]);
                 else if (vm != 3) vobs = log(t.ob_lev[row]);
               }
-              err = t.ob_err[row];
+              if (FILL) err = t.ob_err[row];
             }
           }
           const unsigned long long mk = __ballot(ok);
           if (ok) {
-            const int si = ns + __popcll(mk & lt_mask);
-            *reinterpret_cast<double2*>(&sb[4 * si]) = double2{__longlong_as_double((long)row), nd_h};
-            *reinterpret_cast<double2*>(&sb[4 * si + 2]) = double2{vobs, err};
+            const int si = ns + mbcnt(mk);
+            s_hv[si] = double2{nd_h, vobs};
+            if (FILL) {
+              s_err[si] = err;
+              s_row[si] = row;
+            }
           }
           ns += __popcll(mk);
-          if (ns > kSurv - 64) vertical();
+          if (ns > kS - 64 || last) vertical();
         }
       }
-      if (ns > 0) vertical();
       if (A.nobs_ctype)                                           // nobsl_t (letkf_tools.f90:1473-1475)
         for (int l = lane; l < nlev; l += 64)
           A.nobs_ctype[(col + A.nij1 * (long)l) * t.nctype + ic] = cntl[l] - cprev[l];
     }
     if (!FILL)
       for (int l = lane; l < nlev; l += 64) A.counts[col + A.nij1 * (long)l] = cntl[l];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
 }
 
@@ -615,11 +733,6 @@ __device__ __forceinline__ unsigned int wave_max_u32(unsigned int v) {
   v = max(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false));
   return (unsigned int)__builtin_amdgcn_readlane((int)v, 63);
 }
-// a wave-uniform value, said so: into scalar registers (what hipcc loads through the tables' plain pointers it keeps in
-// vector registers -- and spills to scratch inside the level loop)
-using lane_dev::mbcnt;
-using lane_dev::uniform;
-using lane_dev::wave_lds_sync;
 
 // want-th smallest (1-based, want <= nreal) of the wave's keys held in REGISTERS (slot u of lane l = candidate 64 u + l;
 // kNoKey = none; every real key < 2^63), and how many of the keys equal to it belong to the selection.
@@ -1777,11 +1890,13 @@ hipError_t launch_search_columns(const letkf_search_tables& t, long nij1, int nl
                                  const long* obs_off, int* obs_idx, double* rdiag_l, double* rloc_l, int* nobs_ctype,
                                  int num_cu, hipStream_t st) {
   ColArgs a{t, nij1, nlev, rig, rjg, rlev, rz, fill, counts, obs_off, obs_idx, rdiag_l, rloc_l, nobs_ctype};
-  const size_t lds = (size_t)4 * (4 * kSurv + 2 * ((nlev + 1) & ~1)) * sizeof(double);
+  const size_t lds = 4 * col_wave_bytes(fill != 0, nlev);
   auto kern = fill ? &letkf_search_columns_kernel<true> : &letkf_search_columns_kernel<false>;
   if (hipError_t e = lds_opt_in(kern, lds)) return e;
+  // one column per wave while that takes no more than 64 workgroups per CU: the columns' costs differ (empty ones beside
+  // dense ones) and the dispatcher evens them out; beyond that the waves stride over the columns
   const long nwg = (nij1 + 3) / 4;
-  const long g = (long)num_cu * 8;
+  const long g = (long)num_cu * 64;
   const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
