@@ -13,6 +13,10 @@
 #ifndef LETKF_WARM_SORT
 #define LETKF_WARM_SORT 1
 #endif
+// Sorted, the column of rank r goes to line position r ^ 1 (1, the default) or r (-DLETKF_WARM_ORDER=0): letkf_wave_dev.h warm_position.
+#ifndef LETKF_WARM_ORDER
+#define LETKF_WARM_ORDER 1
+#endif
 
 namespace letkf {
 namespace jacobi_dev {

@@ -508,6 +508,16 @@ __device__ __forceinline__ int warm_rank(const double lam, const bool colvalid, 
   return lane < NLN ? rank : lane;
 }
 
+// Line position of rank r (LETKF_WARM_ORDER, default on; -DLETKF_WARM_ORDER=0 gives position = rank for an A/B; LETKF_AMD_WARM_DBG
+// bit 5 selects that at run time).  The ordering is odd-even transposition with rotate-and-swap: a column that starts at an even
+// position travels right, one that starts at an odd position left.  With rank r at position r the ranks (2m, 2m+1) meet in step 1,
+// but (2m+1, 2m+2) move apart and meet at the very end of the cycle; with rank r at position r ^ 1 they meet in step 2, so every
+// eigenvalue-adjacent pair is rotated in the first step pair -- and the reversal a full cycle applies keeps that pattern.  Only
+// whole pairs of ranks with an eigenvector swap ((r | 1) < nvalid): the unpaired last rank of an odd count keeps its position and
+// the columns sorted last (zeros) keep theirs, so the map is an involution of the line's lanes whatever nvalid is, and with the
+// rank it stays a bijection in bounds for any input, NaN included.
+__device__ __forceinline__ int warm_position(const int rank, const int nvalid) { return (rank | 1) < nvalid ? (rank ^ 1) : rank; }
+
 // smallest k the instantiation <KR, NW> is dispatched for (launch_wave_kernel walks the instances in this order)
 __host__ __device__ constexpr int wave_kmin(int KR, int NW) {
   return NW == 1 ? (KR == 16 ? 1 : KR == 20 ? 17 : KR == 32 ? 17 : KR == 48 ? 33 : KR == 50 ? 49 : KR == 64 ? 51 : 1)
@@ -1471,8 +1481,13 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         // as 64-bit values, spilled, and reloaded one by one in front of each store -- same serialisation)
         unsigned long long pa = reinterpret_cast<unsigned long long>(uws);
         if constexpr (LETKF_WARM_SORT && NW == 1) {
-          // column `lane` goes to workspace column warm_rank (sorted by eigenvalue); warm_dbg bit 4: lane order
-          const int rk = warm_rank<KR>(lam, colvalid, lane);
+          // column `lane` goes to the workspace column of its rank by eigenvalue (warm_rank, warm_position); warm_dbg bit 4:
+          // lane order, bit 5: position = rank
+          int rk = warm_rank<KR>(lam, colvalid, lane);
+          if constexpr (LETKF_WARM_ORDER) {
+            const int nvalid = __popcll(__ballot(colvalid && lane < (KR < 64 ? KR : 64)));
+            if (lane < (KR < 64 ? KR : 64) && !(A.warm_dbg & 32)) rk = warm_position(rk, nvalid);
+          }
           pa += (long long)(((A.warm_dbg & 16) ? lane : rk) - lane) * (long long)sizeof(double);
         }
 #pragma unroll

@@ -3,13 +3,16 @@ iteration (letkf_jacobi_dev.h: odd-even transposition on a line, rotate and swap
 checked once per step pair) run up the columns of a bench workload, every level warm-started from the level below.
 
 Q is handed over in the order its columns sit on the line when the iteration stops ("sit": what the kernel did before
-LETKF_WARM_SORT) or sorted by eigenvalue, descending, columns without an eigenvector (the inert zero column of an odd k) last
-("sorted": letkf_wave_dev.h warm_rank).  Printed: the mean of ceil(step pairs / S) over the warm-started points -- the kernel's
-nsweep -- and the mean of step pairs / S, for both orders and both stop rules (early: a quiet cycle at |cos| <= 1e-8 and
+LETKF_WARM_SORT), sorted by eigenvalue, descending, columns without an eigenvector (the inert zero column of an odd k) last
+("sorted": letkf_wave_dev.h warm_rank), or sorted with rank r at position r ^ 1 ("pair": LETKF_WARM_ORDER -- a column that
+starts at an even position travels right and one at an odd position left, so ranks (2m, 2m+1) meet in step 1 either way, but
+(2m+1, 2m+2) meet at the end of the cycle when sorted and in step 2 when paired; valid columns only, an unpaired last valid
+rank keeps its position).  Printed: the mean of ceil(step pairs / S) over the warm-started points -- the kernel's
+nsweep -- and the mean of step pairs / S, for every order and both stop rules (early: a quiet cycle at |cos| <= 1e-8 and
 |t| <= 1e-6 ends the iteration as well; strict: only the 1e-12 rule).  CPU only; the absolute counts are the model's, the
-difference between the two orders is what it is for.
+difference between the orders is what it is for.
 
-Usage: tools/sim_warm_order.py [WORKLOAD=C2-mini] [NCOL=5] [--json]
+Usage: tools/sim_warm_order.py [WORKLOAD=C2-mini] [NCOL=5] [SEED=1] [--json]
   WORKLOAD  a name of bench_workload.CONFIGS, or C2-sim / C2-k20-sim: C2's / C2-k20's lattice and 60 levels on a 20 x 20 grid"""
 import json
 import math
@@ -55,18 +58,34 @@ def jacobi(G, early, max_sweep=60):
     return pairs, G
 
 
+MODES = ("sit", "sorted", "pair")
+
+
+def hand_over_order(lam, valid, mode):
+    """order[p]: the column (line position when the iteration stopped) that the next point finds at position p."""
+    ncol = len(lam)
+    if mode == "sit":
+        return np.arange(ncol)
+    order = np.lexsort((np.arange(ncol), -lam, ~valid))   # valid first, eigenvalue descending, ties by position
+    if mode == "pair":
+        nvalid = int(valid.sum())
+        pos = np.arange(ncol)
+        pos = np.where((pos | 1) < nvalid, pos ^ 1, pos)      # position of rank r; ranks >= nvalid and an unpaired last one stay
+        out = np.empty(ncol, dtype=order.dtype)
+        out[pos] = order
+        order = out
+    return order
+
+
 def hand_over(G, mode):
     """Normalised columns of G in the order the next point starts from."""
     lam = np.sqrt((G * G).sum(0))
     valid = lam > 0.0
     Q = G * np.where(valid, 1.0 / np.where(valid, lam, 1.0), 0.0)
-    if mode == "sorted":
-        order = np.lexsort((np.arange(len(lam)), -lam, ~valid))   # valid first, eigenvalue descending, ties by position
-        Q = Q[:, order]
-    return Q
+    return Q[:, hand_over_order(lam, valid, mode)]
 
 
-def simulate(name, ncols, seed=1):
+def simulate(name, ncols, seed=1, modes=MODES):
     if name.endswith("-sim"):     # the full-size workload's lattice and levels on a small horizontal grid
         bw.CONFIGS[name] = dict(bw.CONFIGS[name[:-4]], nx=20, ny=20)
     w = bw.build(name, torch.device("cpu"))
@@ -87,7 +106,7 @@ def simulate(name, ncols, seed=1):
     cols = np.random.default_rng(seed).choice(nij, ncols, replace=False)
     res = {}
     for early in (True, False):
-        for mode in ("sit", "sorted"):
+        for mode in modes:
             sweeps, frac = [], []
             for col in cols:
                 Q = None
@@ -112,12 +131,13 @@ def simulate(name, ncols, seed=1):
 
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    r = simulate(args[0] if args else "C2-mini", int(args[1]) if len(args) > 1 else 5)
+    r = simulate(args[0] if args else "C2-mini", int(args[1]) if len(args) > 1 else 5, int(args[2]) if len(args) > 2 else 1)
     if "--json" in sys.argv:
         print(json.dumps(r))
     else:
         print(f"{r['workload']}: k = {r['k']}, {r['columns']} columns x {r['levels']} levels, mean n = {r['n_mean']:.1f}")
         for rule in ("early", "strict"):
-            a, b = r[f"{rule}_sit"], r[f"{rule}_sorted"]
+            a, b, c = r[f"{rule}_sit"], r[f"{rule}_sorted"], r[f"{rule}_pair"]
             print(f"  {rule:6s} stop rule, {a['points']} warm points: nsweep as they sit {a['nsweep_mean']:.3f}, sorted {b['nsweep_mean']:.3f} "
-                  f"({100 * (b['nsweep_mean'] / a['nsweep_mean'] - 1):+.1f} %); cycles {a['cycles_mean']:.3f} -> {b['cycles_mean']:.3f}")
+                  f"({100 * (b['nsweep_mean'] / a['nsweep_mean'] - 1):+.1f} %), rank ^ 1 {c['nsweep_mean']:.3f}; "
+                  f"cycles {a['cycles_mean']:.3f} -> {b['cycles_mean']:.3f} -> {c['cycles_mean']:.3f}")
