@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "letkf_rules_dev.h"
 #include "letkf_staged_dev.h"
 
 namespace letkf {
@@ -130,15 +131,7 @@ __global__ void __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) letkf_stage_gram_m
       if (small != (NWV == 4)) continue;
       if (!small && (kGmPanelBig / nbx >= 4) != TC4) continue;
     } else if (!(TC4 && NWV == GRAM_SMALL_WAVES)) continue;
-    // inflation slot that drives the solve (first updated variable of the class, letkf_tools.f90:387-418)
-    double infl_old;
-    {
-      bool qskip = false;
-      if (A.q_update_top > 0.0) qskip = A.gues[pt * A.sp + k * A.sm + A.iv_p * A.sv] < A.q_update_top;
-      int v0 = 0;
-      while (v0 < A.nv && (!((A.var_mask >> v0) & 1u) || (qskip && v0 >= A.iv_q_first && v0 <= A.iv_q_last))) ++v0;
-      infl_old = v0 < A.nv ? A.infl[pt + A.infl_sv * (long)v0] : 1.0;
-    }
+    const double infl_old = rules_dev::solve_inflation(A, pt, A.nv, rules_dev::q_update_skipped(A, A.gues + pt * A.sp + k * A.sm, A.sv));
     const double shift = km1 / infl_old;              // common_letkf.f90:140-143
     const bool dual = n < k;
     if (dual != DUAL) continue;                       // (the other instantiation's point)

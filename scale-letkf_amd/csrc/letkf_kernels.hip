@@ -31,12 +31,14 @@
 #include "letkf_device.h"
 #include "letkf_jacobi_dev.h"
 #include "letkf_lane_dev.h"
+#include "letkf_rules_dev.h"
 #include "letkf_staged_dev.h"
 
 namespace letkf {
 
 // ------------------------------------------------------------------ small helpers
 using namespace lane_dev;     // wsum, wshfl_xor, dpp_mov0, wave_lds_sync, xcd_remap
+using namespace rules_dev;
 using jacobi_dev::fast_rcp;
 
 // sum over aligned groups of 8 lanes: lane^1, lane^2, then the mirror image inside the 8 (after the first two
@@ -83,7 +85,6 @@ __device__ __forceinline__ void hestenes_cs(double a, double b, double g, double
 
 constexpr double kRotTol2 = 1e-30;   // rotate when gamma^2 > kRotTol2 * alpha * beta  (|cos| > 1e-15)
 constexpr double kStopTol2 = 1e-20;  // converged when a whole sweep saw only |cos| <= 1e-10 (all still rotated away in it)
-constexpr int kMaxSweep = 60;
 
 // ------------------------------------------------------------------ Jacobi, 8 lanes per pair, rows in registers
 template <int RMAX>
@@ -534,14 +535,14 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
     if (A.mode == 0 && beta == 0.0) {            // letkf_tools.f90:333-359
       for (int e = tid; e < nv * k; e += nthr) {
         const int v = e / k, mm = e - v * k;
-        if ((A.var_mask >> v) & 1u) a0[mm * A.sm + v * A.sv] = g0[k * A.sm + v * A.sv] + g0[mm * A.sm + v * A.sv];
+        if (in_class(A, v)) a0[mm * A.sm + v * A.sv] = g0[k * A.sm + v * A.sv] + g0[mm * A.sm + v * A.sv];
       }
       if (A.det_run)
         for (int v = tid; v < nv; v += nthr)
-          if ((A.var_mask >> v) & 1u) a0[(k + 1) * A.sm + v * A.sv] = g0[(k + 1) * A.sm + v * A.sv];
+          if (in_class(A, v)) a0[(k + 1) * A.sm + v * A.sv] = g0[(k + 1) * A.sm + v * A.sv];
       if (A.rtps_out)
         for (int v = tid; v < nv; v += nthr)
-          if ((A.var_mask >> v) & 1u) A.rtps_out[pt + A.infl_sv * (long)v] = 1.0;
+          if (in_class(A, v)) A.rtps_out[pt + A.infl_sv * (long)v] = 1.0;
       if (tid == 0) {
         if (A.status) A.status[pt] = 0;
         if (A.nsweep) A.nsweep[pt] = 0;
@@ -549,15 +550,8 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
       continue;
     }
 
-    // variable skip mask for Q_UPDATE_TOP (letkf_tools.f90:371) and the solve's inflation slot
-    bool qskip = false;
-    if (A.mode == 0 && A.q_update_top > 0.0) qskip = g0[k * A.sm + A.iv_p * A.sv] < A.q_update_top;
-    int v0 = 0;                                  // first variable of this class that is actually updated
-    while (v0 < nv && (!((A.var_mask >> v0) & 1u) || (qskip && v0 >= A.iv_q_first && v0 <= A.iv_q_last))) ++v0;
-    double* infl_p = nullptr;
-    if (A.mode == 0) infl_p = (v0 < nv) ? &A.infl[pt + A.infl_sv * (long)v0] : nullptr;
-    else infl_p = &A.infl[pt];
-    const double infl_old = infl_p ? *infl_p : 1.0;
+    const bool qskip = A.mode == 0 && q_update_skipped(A, g0 + k * A.sm, A.sv);
+    const double infl_old = A.mode == 0 ? solve_inflation(A, pt, nv, qskip) : A.infl[pt];
 
     __syncthreads();                             // previous point's LDS fully consumed
 
@@ -729,8 +723,8 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
       __syncthreads();
     }
 
-    // ---------------- status: spectrum checks (common_mtx.f90:66-78)
-    int st = 0;
+    // ---------------- status: spectrum checks
+    int st;
     {
       double lmx = 0.0, lmn = 1e300;
       for (int j = tid & 63; j < k; j += 64) {
@@ -742,14 +736,12 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
         lmx = fmax(lmx, wshfl_xor(lmx, mk));
         lmn = fmin(lmn, wshfl_xor(lmn, mk));
       }
-      if (!jconv && A.max_sweep >= kMaxSweep) st = 1;   // (converging in the last permitted sweep is converged)
-      else if (!(lmx > 0.0)) st = 2;
-      else if (lmn < lmx * 1.4901161193847656e-08) st = 3;       // sqrt(DBL_EPSILON)
+      st = eig_status(jconv, A.max_sweep, lmx, lmn);
     }
     for (int j = tid; j < k; j += nthr) {
-      const double l = lam[j];
-      sc1[j] = sqrt(km1 / l);
-      sc2[j] = 1.0 / l;
+      const Spectra sc = spectra(lam[j], km1, true);
+      sc1[j] = sc.sc1;
+      sc2[j] = sc.sc2;
     }
 
     // ---------------- phase 4a: stage perturbations X[v][m], means, det member
@@ -784,26 +776,22 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
       (b == 0 ? wbar : wbard)[mm] = sacc;
     }
     if (A.mode == 0) {
-      // RTPS needs var_g = |x'|^2 and var_a = x'^T Pa x' = sum_j U_jv^2 / lam_j (letkf_tools.f90:1982-1989)
+      // var_g = |x'|^2, var_a = x'^T Pa x' = sum_j U_jv^2 / lam_j
       for (int v = tid; v < nv; v += nthr) {
-        const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391
+        const double parm = relax_parm(A, pt, v);
         double cf = 1.0, cd = 0.0;
-        if (A.relax_alpha != 0.0) {              // RTPP :1960-1963
-          cf = 1.0 - A.relax_alpha;
-          cd = A.relax_alpha * sqrt(parm);
-        } else if (A.relax_alpha_spread != 0.0) { // RTPS :1990-1999
+        if (A.relax_alpha != 0.0) {
+          cf = rtpp_factor(A);
+          cd = rtpp_diag(A, parm);
+        } else if (A.relax_alpha_spread != 0.0) {
           double var_g = 0.0, var_a = 0.0;
           for (int mm = 0; mm < k; ++mm) var_g = fma(X[v * k + mm], X[v * k + mm], var_g);
           for (int j = 0; j < k; ++j) var_a = fma(U[j * nb + 2 + v] * U[j * nb + 2 + v], sc2[j], var_a);
-          if (var_g > 0.0 && var_a > 0.0)
-            cf = A.relax_alpha_spread * sqrt(var_g * parm / (var_a * km1)) - A.relax_alpha_spread + 1.0;
+          cf = rtps_factor(A, parm, var_g, var_a, km1);
         }
         cfac[v] = cf;
         cdiag[v] = cd;
-        if (A.rtps_out && ((A.var_mask >> v) & 1u)) {   // work3da (letkf_tools.f90:460-462)
-          const bool skipv = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-          A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skipv) ? cf : 1.0;
-        }
+        if (A.rtps_out && in_class(A, v)) A.rtps_out[pt + A.infl_sv * (long)v] = rtps_reported(A, var_skipped(A, qskip, v), cf);
       }
     }
     __syncthreads();
@@ -818,42 +806,31 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
     }
     __syncthreads();
 
-    // ---------------- adaptive inflation (common_letkf.f90:233-254); uses the OLD rho above
+    // ---------------- adaptive inflation; uses the OLD rho above
     double infl_new = infl_old;
-    if (A.infl_adaptive && n > 0) {
-      const double parm1 = red[0], parm3 = red[1], parm2 = red[2] / km1;
-      const double parm4 = (parm1 - parm3) / parm2 - infl_old;
-      const double tq = (infl_old * parm2 + parm3) / parm2;
-      const double sigma_o = 2.0 / parm3 * (tq * tq);
-      const double gain = 0.04 * 0.04 / (sigma_o + 0.04 * 0.04);
-      infl_new = infl_old + gain * parm4;
-    }
+    if (A.infl_adaptive && n > 0) infl_new = adaptive_inflation(infl_old, red[0], red[2] / km1, red[1]);
 
-    // ---------------- phase 5: analysis members  (letkf_tools.f90:472-513)
+    // ---------------- phase 5: analysis members
     if (A.mode == 0) {
       for (int e = tid; e < nv * k; e += nthr) {
         const int v = e / k, mm = e - v * k;
-        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
+        const bool skip = var_skipped(A, qskip, v);
         double out;
         if (skip) {
           out = xmean[v] + X[e];
         } else {
           double tx = 0.0;                       // (T x'_v)[mm] = sum_j V[mm][j] sqrt((k-1)/lam_j) U[j][v]
           for (int j = 0; j < k; ++j) tx = fma(G[(size_t)j * ldg + mm], sc1[j] * U[j * nb + 2 + v], tx);
-          const double pert = cfac[v] * tx + cdiag[v] * X[e];
-          out = xmean[v] + beta * (pert + sdot[v]) + (1.0 - beta) * X[e];
+          out = analysis_value(xmean[v], X[e], beta, cfac[v] * tx + cdiag[v] * X[e], sdot[v]);
         }
         if (A.q_sprd_max > 0.0 && v == A.iv_q_first && !skip) X[e] = out;   // keep for the clamp
-        else if ((A.var_mask >> v) & 1u) a0[mm * A.sm + v * A.sv] = out;
+        else if (in_class(A, v)) a0[mm * A.sm + v * A.sv] = out;
       }
       if (A.det_run) {
-        for (int v = tid; v < nv; v += nthr) {
-          const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-          if ((A.var_mask >> v) & 1u)
-            a0[(k + 1) * A.sm + v * A.sv] = skip ? xdet[v] : xdet[v] + sdotd[v] * beta;   // :489-497
-        }
+        for (int v = tid; v < nv; v += nthr)
+          if (in_class(A, v)) a0[(k + 1) * A.sm + v * A.sv] = var_skipped(A, qskip, v) ? xdet[v] : xdet[v] + sdotd[v] * beta;   // :489-497
       }
-      if (A.q_sprd_max > 0.0 && !(qskip) && ((A.var_mask >> A.iv_q_first) & 1u)) {   // :500-513, variable iv3d_q only
+      if (A.q_sprd_max > 0.0 && !qskip && in_class(A, A.iv_q_first)) {   // variable iv3d_q only
         __syncthreads();
         const int v = A.iv_q_first;
         if (tid < 64) {
@@ -869,18 +846,14 @@ __global__ void __launch_bounds__(BIG ? 768 : 256) letkf_point_kernel(const Poin
           ss = wsum(ss);
           const double q_sprd = sqrt(ss / km1) / q_mean;
           for (int mm = tid; mm < k; mm += 64) {
-            double val = X[v * k + mm];
-            if (q_sprd > A.q_sprd_max) val = q_mean + (val - q_mean) * A.q_sprd_max / q_sprd;
-            a0[mm * A.sm + v * A.sv] = val;
+            const double val = X[v * k + mm];
+            a0[mm * A.sm + v * A.sv] = q_clamped(val, q_mean, val - q_mean, q_sprd, A.q_sprd_max);
           }
         }
       }
-      if (A.infl_adaptive) {                     // :396-398: every updated variable of the class gets its first slot's value
-        for (int v = tid; v < nv; v += nthr) {
-          const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-          if (!skip && ((A.var_mask >> v) & 1u)) A.infl[pt + A.infl_sv * (long)v] = infl_new;
-        }
-      }
+      if (A.infl_adaptive)
+        for (int v = tid; v < nv; v += nthr)
+          if (var_updated(A, qskip, v)) A.infl[pt + A.infl_sv * (long)v] = infl_new;
     } else if (A.infl_adaptive && n > 0 && tid == 0) {
       A.infl[pt] = infl_new;
     }

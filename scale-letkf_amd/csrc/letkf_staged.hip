@@ -29,11 +29,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "letkf_rules_dev.h"
 #include "letkf_staged_dev.h"
 
 namespace letkf {
 
 using namespace staged_dev;
+using namespace rules_dev;
 
 namespace {
 
@@ -107,17 +109,8 @@ __global__ void __launch_bounds__(kGBlock) letkf_stage_gram_kernel(const StagedA
       }
       continue;
     }
-    // inflation slot that drives the solve (first updated variable of the class, letkf_tools.f90:387-418)
-    double infl_old;
-    if (A.mode == 0) {
-      bool qskip = false;
-      if (A.q_update_top > 0.0) qskip = A.gues[pt * A.sp + k * A.sm + A.iv_p * A.sv] < A.q_update_top;
-      int v0 = 0;
-      while (v0 < A.nv && (!((A.var_mask >> v0) & 1u) || (qskip && v0 >= A.iv_q_first && v0 <= A.iv_q_last))) ++v0;
-      infl_old = v0 < A.nv ? A.infl[pt + A.infl_sv * (long)v0] : 1.0;
-    } else {
-      infl_old = A.infl[pt];
-    }
+    const double infl_old =
+        A.mode == 0 ? solve_inflation(A, pt, A.nv, q_update_skipped(A, A.gues + pt * A.sp + k * A.sm, A.sv)) : A.infl[pt];
     const double shift = km1 / infl_old;              // common_letkf.f90:140-143
     const bool dual = n < k;
     const int m = dual ? n : k;
@@ -409,10 +402,10 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
     if (mode == 0) {                                   // beta == 0: letkf_tools.f90:333-359
       for (int e = tid; e < nv * k; e += nthr) {
         const int v = e / k, mm = e - v * k;
-        if ((A.var_mask >> v) & 1u) a0[mm * A.sm + v * A.sv] = g0[k * A.sm + v * A.sv] + g0[mm * A.sm + v * A.sv];
+        if (in_class(A, v)) a0[mm * A.sm + v * A.sv] = g0[k * A.sm + v * A.sv] + g0[mm * A.sm + v * A.sv];
       }
       for (int v = tid; v < nv; v += nthr)
-        if ((A.var_mask >> v) & 1u) {
+        if (in_class(A, v)) {
           if (A.det_run) a0[(k + 1) * A.sm + v * A.sv] = g0[(k + 1) * A.sm + v * A.sv];
           if (A.rtps_out) A.rtps_out[pt + A.infl_sv * (long)v] = 1.0;
         }
@@ -492,10 +485,7 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
         lmx = fmax(lmx, shift);
         lmn = fmin(lmn, shift);
       }
-      const bool conv = (solver == 0 || S.info[2 * it + 1] != 0) && !any_nan;
-      if (!conv) st = 1;
-      else if (!(lmx > 0.0)) st = 2;
-      else if (lmn < lmx * 1.4901161193847656e-08) st = 3;       // sqrt(DBL_EPSILON)
+      st = spectrum_status((solver == 0 || S.info[2 * it + 1] != 0) && !any_nan, lmx, lmn);
     }
     const double sqc = sqrt(shift), sqkm1 = sqrt(km1);
     const double tau0 = dual ? sqrt(km1 / shift) : 0.0;            // f_T(c) = sqrt(rho)
@@ -587,15 +577,15 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
       __syncthreads();
     }
 
-    // ---------------- relaxation scalars per variable (letkf_tools.f90:457-469, :1953-2002)
+    // ---------------- relaxation scalars per variable
     if (das)
       for (int v = tid; v < nv; v += nthr) {
-        const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391
+        const double parm = relax_parm(A, pt, v);
         double cf = 1.0, cd = 0.0;
-        if (A.relax_alpha != 0.0) {                    // RTPP
-          cf = 1.0 - A.relax_alpha;
-          cd = A.relax_alpha * sqrt(parm);
-        } else if (A.relax_alpha_spread != 0.0) {      // RTPS: var_a = x'^T Pa x' = pi0 |x'|^2 + sum_j pi_j P_j^2
+        if (A.relax_alpha != 0.0) {
+          cf = rtpp_factor(A);
+          cd = rtpp_diag(A, parm);
+        } else if (A.relax_alpha_spread != 0.0) {      // var_a = x'^T Pa x' = pi0 |x'|^2 + sum_j pi_j P_j^2
           const double var_g = varg[v];
           double var_a = 0.0;
           if (poly) {
@@ -607,8 +597,7 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
             }
           }
           var_a = fma(pi0, var_g, var_a);
-          if (var_g > 0.0 && var_a > 0.0)
-            cf = A.relax_alpha_spread * sqrt(var_g * parm / (var_a * km1)) - A.relax_alpha_spread + 1.0;
+          cf = rtps_factor(A, parm, var_g, var_a, km1);
         }
         cfac[v] = cf;
         cdiag[v] = cd;
@@ -726,20 +715,12 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
     const double* wbar = sl.OUT;
     const double* wbard = sl.OUT + k;
 
-    // ---------------- adaptive inflation (common_letkf.f90:233-254); T and w-bar above used the OLD rho
+    // ---------------- adaptive inflation; T and w-bar above used the OLD rho
     double infl_new = infl_old;
-    if (A.infl_adaptive && n > 0) {
-      const double parm1 = sl.SC[0], parm3 = sl.SC[1], parm2 = sl.SC[2] / km1;
-      const double parm4 = (parm1 - parm3) / parm2 - infl_old;
-      const double tq = (infl_old * parm2 + parm3) / parm2;
-      const double sigma_o = 2.0 / parm3 * (tq * tq);
-      const double gain = 0.04 * 0.04 / (sigma_o + 0.04 * 0.04);
-      infl_new = infl_old + gain * parm4;
-    }
+    if (A.infl_adaptive && n > 0) infl_new = adaptive_inflation(infl_old, sl.SC[0], sl.SC[2] / km1, sl.SC[1]);
 
     if (das) {
-      bool qskip = false;
-      if (A.q_update_top > 0.0) qskip = xmean[A.iv_p] < A.q_update_top;
+      const bool qskip = q_update_skipped(A, xmean, 1);
       // x'_v . w-bar, x'_v . w-bar_det
       for (int e = wv; e < 2 * nv; e += nwv) {
         const int v = e < nv ? e : e - nv;
@@ -750,33 +731,31 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
         if (lane == 0) (e < nv ? sdot : sdotd)[v] = s;
       }
       __syncthreads();
-      // ---------------- analysis members (letkf_tools.f90:472-513)
-      const bool clampq = A.q_sprd_max > 0.0 && !qskip && ((A.var_mask >> A.iv_q_first) & 1u);
+      // ---------------- analysis members
+      const bool clampq = A.q_sprd_max > 0.0 && !qskip && in_class(A, A.iv_q_first);
       for (int e = tid; e < nv * k; e += nthr) {
         const int v = e / k, mm = e - v * k;
-        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
+        const bool skip = var_skipped(A, qskip, v);
         const double xp = sl.X[e];
         double out;
         if (skip) {
           out = xmean[v] + xp;
         } else {
           const double tx = sl.OUT[(size_t)(2 + v) * k + mm];
-          const double pert = cfac[v] * tx + cdiag[v] * xp;
-          out = xmean[v] + beta * (pert + sdot[v]) + (1.0 - beta) * xp;
+          out = analysis_value(xmean[v], xp, beta, cfac[v] * tx + cdiag[v] * xp, sdot[v]);
         }
         if (clampq && v == A.iv_q_first) sl.TT[mm] = out;          // kept for the clamp (TT is free now)
-        else if ((A.var_mask >> v) & 1u) a0[mm * A.sm + v * A.sv] = out;
+        else if (in_class(A, v)) a0[mm * A.sm + v * A.sv] = out;
       }
       for (int v = tid; v < nv; v += nthr) {
-        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-        if ((A.var_mask >> v) & 1u) {
+        const bool skip = var_skipped(A, qskip, v);
+        if (in_class(A, v)) {
           if (A.det_run) a0[(k + 1) * A.sm + v * A.sv] = skip ? xdet[v] : xdet[v] + sdotd[v] * beta;   // :489-497
-          if (A.rtps_out)
-            A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skip) ? cfac[v] : 1.0;
-          if (A.infl_adaptive && !skip) A.infl[pt + A.infl_sv * (long)v] = infl_new;   // :396-398
+          if (A.rtps_out) A.rtps_out[pt + A.infl_sv * (long)v] = rtps_reported(A, skip, cfac[v]);
+          if (A.infl_adaptive && !skip) A.infl[pt + A.infl_sv * (long)v] = infl_new;
         }
       }
-      if (clampq) {                                    // :500-513, variable iv3d_q only
+      if (clampq) {                                    // variable iv3d_q only
         __syncthreads();
         const int v = A.iv_q_first;
         if (tid < 64) {
@@ -792,9 +771,8 @@ __global__ void __launch_bounds__(NTHR, MINW) letkf_stage_apply_kernel(const Sta
           ss = wsum(ss);
           const double q_sprd = sqrt(ss / km1) / q_mean;
           for (int mm = tid; mm < k; mm += 64) {
-            double val = sl.TT[mm];
-            if (q_sprd > A.q_sprd_max) val = q_mean + (val - q_mean) * A.q_sprd_max / q_sprd;
-            a0[mm * A.sm + v * A.sv] = val;
+            const double val = sl.TT[mm];
+            a0[mm * A.sm + v * A.sv] = q_clamped(val, q_mean, val - q_mean, q_sprd, A.q_sprd_max);
           }
         }
       }

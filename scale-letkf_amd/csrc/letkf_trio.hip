@@ -28,6 +28,7 @@
 #include "letkf_device.h"
 #include "letkf_jacobi_dev.h"
 #include "letkf_lane_dev.h"
+#include "letkf_rules_dev.h"
 #include "letkf_sched_dev.h"
 
 namespace letkf {
@@ -36,6 +37,7 @@ namespace {
 
 using namespace jacobi_dev;
 using namespace lane_dev;
+using namespace rules_dev;
 
 // the wave's LDS slice (doubles).  P points per wave: 3 (the code is written for any P whose segments fit the line of 32 slots; with more
 // than three the staging batch shrinks to 192 observations so that the parks fit the 20 KB of a wave -- see launch_trio_kernel).
@@ -366,11 +368,7 @@ __device__ __forceinline__ int trio_front(const PointArgs& A, const TrioHead& hd
   if (beta == 0.0) return 0;
   if (n == 0) return 1;
   const double* g0 = A.gues + pt * A.sp;
-  bool qskip = false;
-  if (A.q_update_top > 0.0) qskip = g0[k * A.sm + A.iv_p * A.sv] < A.q_update_top;
-  int v0 = 0;
-  while (v0 < A.nv && (!((A.var_mask >> v0) & 1u) || (qskip && v0 >= A.iv_q_first && v0 <= A.iv_q_last))) ++v0;
-  const double infl_old = (v0 < A.nv) ? A.infl[pt + A.infl_sv * (long)v0] : 1.0;
+  const double infl_old = solve_inflation(A, pt, A.nv, q_update_skipped(A, g0 + k * A.sm, A.sv));
 
   v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
   [[maybe_unused]] double accS[RSA][NBLK];
@@ -640,31 +638,16 @@ __device__ __forceinline__ int trio_back(const PointArgs& A, const long pt, cons
   const bool jconv = uniform(st_[ST_CONV]) != 0.0;
   const double lam = lane < ncol ? slice[L::lam + sub * 32 + lane] : 0.0;
   const bool colvalid = lam > 0.0;
-  int st = 0;
-  {
-    const double lmx = wave_max(colvalid ? lam : 0.0);
-    const double lmn = wave_min(colvalid ? lam : 1e300);
-    if (!jconv && A.max_sweep >= 60) st = 1;
-    else if (!(lmx > 0.0)) st = 2;
-    else if (lmn < lmx * 1.4901161193847656e-08) st = 3;
-  }
-  const double sc1 = colvalid ? sqrt(km1 / lam) : 0.0;      // T spectrum
-  const double sc2 = colvalid ? 1.0 / lam : 0.0;            // Pa spectrum
+  const int st = eig_status(jconv, A.max_sweep, wave_max(colvalid ? lam : 0.0), wave_min(colvalid ? lam : 1e300));
+  const Spectra sc = spectra(lam, km1, colvalid);
+  const double sc1 = sc.sc1, sc2 = sc.sc2;                  // T spectrum, Pa spectrum
   double infl_new = infl_old;
-  if (A.infl_adaptive) {                                     // common_letkf.f90:233-254
-    const double parm1 = uniform(st_[ST_P1]), parm2 = uniform(st_[ST_P2]), parm3 = uniform(st_[ST_P3]);
-    const double parm4 = (parm1 - parm3) / parm2 - infl_old;
-    const double tq = (infl_old * parm2 + parm3) / parm2;
-    const double sigma_o = 2.0 / parm3 * (tq * tq);
-    const double gain = 0.04 * 0.04 / (sigma_o + 0.04 * 0.04);
-    infl_new = infl_old + gain * parm4;
-  }
+  if (A.infl_adaptive) infl_new = adaptive_inflation(infl_old, uniform(st_[ST_P1]), uniform(st_[ST_P2]), uniform(st_[ST_P3]));
   const double* g0 = A.gues + pt * A.sp;
   double* a0 = A.anal + pt * A.sp;
   long moff = (long)lane * A.sm;
   asm volatile("" : "+v"(moff));
-  bool qskip = false;
-  if (A.q_update_top > 0.0) qskip = g0[k * A.sm + A.iv_p * A.sv] < A.q_update_top;
+  const bool qskip = q_update_skipped(A, g0 + k * A.sm, A.sv);
   double xv[NV];
   double xm_l = 0.0, xd_l = 0.0;
   {
@@ -744,7 +727,7 @@ __device__ __forceinline__ int trio_back(const PointArgs& A, const long pt, cons
       }
     }
   }
-  // RTPS factor per variable (letkf_tools.f90:1982-1999) in the lanes of column c = 2 + v
+  // RTPS factor per variable in the lanes of column c = 2 + v
   va += wshfl_xor(va, 16);
   va += wshfl_xor(va, 32);
   vg += wshfl_xor(vg, 16);
@@ -753,17 +736,9 @@ __device__ __forceinline__ int trio_back(const PointArgs& A, const long pt, cons
   {
     const int v = c - 2;
     const bool isv = c >= 2 && c < NB;
-    double cfv = 1.0;
-    if (A.relax_alpha != 0.0) {
-      cfv = 1.0 - A.relax_alpha;
-    } else if (A.relax_alpha_spread != 0.0) {
-      const double parm = (A.relax_to_inflated_prior && isv) ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391
-      if (vg > 0.0 && va > 0.0) cfv = A.relax_alpha_spread * sqrt(vg * parm / (va * km1)) - A.relax_alpha_spread + 1.0;
-    }
-    if (A.rtps_out && q == 0 && isv && ((A.var_mask >> v) & 1u)) {   // work3da (letkf_tools.f90:460-462)
-      const bool skipv = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-      A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skipv) ? cfv : 1.0;
-    }
+    const double parm = (wants_variances(A) && isv) ? relax_parm(A, pt, v) : 1.0;
+    const double cfv = relax_factor(A, parm, vg, va, km1);
+    if (A.rtps_out && q == 0 && isv && in_class(A, v)) A.rtps_out[pt + A.infl_sv * (long)v] = rtps_reported(A, var_skipped(A, qskip, v), cfv);
 #pragma unroll
     for (int vv = 0; vv < NV; ++vv) cf[vv] = readlane_d(cfv, 2 + vv);
   }
@@ -785,12 +760,12 @@ __device__ __forceinline__ int trio_back(const PointArgs& A, const long pt, cons
     }
   }
   pf.mark(5);
-  // ------------------------------------------------------------ analysis members (letkf_tools.f90:472-513)
+  // ------------------------------------------------------------ analysis members
   {
     double* ap = a0 + moff;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
+      const bool skip = var_skipped(A, qskip, v);
       const double x = xv[v];
       const double xm = readlane_d(xm_l, v), xdt = readlane_d(xd_l, v);
       const double sdot = wave_sum(x * out[0]);
@@ -799,31 +774,24 @@ __device__ __forceinline__ int trio_back(const PointArgs& A, const long pt, cons
       if (skip) {
         val = xm + x;
       } else {
-        double cdv = 0.0;
-        if (A.relax_alpha != 0.0) {              // RTPP diagonal term alpha*sqrt(parm), parm read before the update
-          const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;
-          cdv = A.relax_alpha * sqrt(parm);
-        }
-        const double pert = cf[v] * out[2 + v] + cdv * x;
-        val = xm + beta * (pert + sdot) + (1.0 - beta) * x;
-        if (A.q_sprd_max > 0.0 && v == A.iv_q_first) {      // :500-513
+        const double pert = cf[v] * out[2 + v] + rtpp_diag(A, pt, v) * x;
+        val = analysis_value(xm, x, beta, pert, sdot);
+        if (A.q_sprd_max > 0.0 && v == A.iv_q_first) {
           const double q_mean = wave_sum(lane < k ? val : 0.0) / (double)k;
           const double dq = (lane < k) ? val - q_mean : 0.0;
           const double q_sprd = sqrt(wave_sum(dq * dq) / km1) / q_mean;
-          if (q_sprd > A.q_sprd_max) val = q_mean + dq * A.q_sprd_max / q_sprd;
+          val = q_clamped(val, q_mean, dq, q_sprd, A.q_sprd_max);
         }
       }
-      const bool inclass = (A.var_mask >> v) & 1u;
+      const bool inclass = in_class(A, v);
       if (lane < k && inclass) *ap = val;
       ap += A.sv;
       if (A.det_run && lane == 0 && inclass) a0[(k + 1) * A.sm + v * A.sv] = skip ? xdt : xdt + sdotd * beta;     // :489-497
     }
-    if (A.infl_adaptive) {                       // :396-398, after every parm read above
+    if (A.infl_adaptive) {                       // after every parm read above
 #pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-        if (!skip && lane == 0 && ((A.var_mask >> v) & 1u)) A.infl[pt + A.infl_sv * (long)v] = infl_new;
-      }
+      for (int v = 0; v < NV; ++v)
+        if (lane == 0 && var_updated(A, qskip, v)) A.infl[pt + A.infl_sv * (long)v] = infl_new;
     }
   }
   if (lane == 0) {

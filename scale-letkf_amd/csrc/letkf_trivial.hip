@@ -2,8 +2,7 @@
 // to solve, as ONE streaming pass with a thread per (point, variable):
 //   * beta == 0 (letkf_tools.f90:333-359: above the radar top / outside the buffer zone): analysis = first guess;
 //   * no local observation (common/common_letkf.f90:89-107): T = sqrt(rho) I, w-bar = 0 in closed form; what is left is
-//     the relaxation (letkf_tools.f90:457-469, :1953-2002), the beta blend, the q clamp (:500-513) and the class copy of
-//     the inflation slot (:396-398).
+//     the relaxation, the beta blend, the q clamp and the class copy of the inflation slot (letkf_rules_dev.h).
 // The register kernels (letkf_wave_dev.h) give such a point a whole wavefront, lane = member: with the reference's
 // point-fastest state (gues3d(nij1, nlev, nens, nv3d)) every one of its 11 x (k + 1) state values is an 8-byte access
 // npts * 8 bytes from the next -- 70 KB of cache lines fetched and as many written per point for 4.5 KB of data, ~30 us
@@ -18,8 +17,11 @@
 #include <stdint.h>
 
 #include "letkf_device.h"
+#include "letkf_rules_dev.h"
 
 namespace letkf {
+
+using namespace rules_dev;
 
 // One thread per (point, variable), points fastest: 11 x the threads of a thread-per-point pass and chains of 3 k instead
 // of 33 k dependent accesses -- with few trivial points (C2-mini-disc: 3520 of them = 55 waves) the pass is bound by the
@@ -36,7 +38,7 @@ __global__ void __launch_bounds__(256) letkf_trivial_points_kernel(const PointAr
   if (n != 0 && beta != 0.0) return;
   const int k = A.k;
   const double km1 = (double)(k - 1);
-  const bool inclass = (A.var_mask >> v) & 1u;
+  const bool inclass = in_class(A, v);
   const double* __restrict__ gv = A.gues + pt * A.sp + v * A.sv;
   double* __restrict__ av = A.anal + pt * A.sp + v * A.sv;
   const long sm = A.sm;
@@ -64,30 +66,22 @@ __global__ void __launch_bounds__(256) letkf_trivial_points_kernel(const PointAr
     return;
   }
 
-  bool qskip = false;
-  if (A.q_update_top > 0.0) qskip = A.gues[pt * A.sp + k * sm + A.iv_p * A.sv] < A.q_update_top;
-  // first variable of the class that is updated: its inflation slot is the point's rho (letkf_tools.f90:387-418)
-  int v0 = 0;
-  while (v0 < nv && (!((A.var_mask >> v0) & 1u) || (qskip && v0 >= A.iv_q_first && v0 <= A.iv_q_last))) ++v0;
-  const double infl_old = v0 < nv ? A.infl[pt + A.infl_sv * (long)v0] : 1.0;
+  const bool qskip = q_update_skipped(A, A.gues + pt * A.sp + k * sm, A.sv);
+  const double infl_old = solve_inflation(A, pt, nv, qskip);
   const double lam = km1 / infl_old;                   // every eigenvalue of A = (k-1)/rho I
-  const double sc1 = sqrt(km1 / lam);                  // T = sqrt(rho) I
-  const double sc2 = 1.0 / lam;                        // Pa = rho/(k-1) I
+  const Spectra sc = spectra(lam, km1, true);          // T = sqrt(rho) I, Pa = rho/(k-1) I
   if (v == 0) {
-    if (A.status) A.status[pt] = lam > 0.0 ? 0 : 2;    // common_mtx.f90:66-78
+    if (A.status) A.status[pt] = spectrum_status(true, lam, lam);
     if (A.nsweep) A.nsweep[pt] = 0;
     if (A.nobs_out) A.nobs_out[pt] = 0;
   }
   if (!inclass) return;
 
-  const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
+  const bool skip = var_skipped(A, qskip, v);
   const double xm = gv[k * sm];
-  const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391, read before the update below
-  double cfv = 1.0;
-  if (A.relax_alpha != 0.0) {                          // RTPP (:1953-1966)
-    cfv = 1.0 - A.relax_alpha;
-  } else if (A.relax_alpha_spread != 0.0) {            // RTPS (:1971-2002) with Pa = sc2 I
-    double var_g = 0.0;
+  const double parm = relax_parm(A, pt, v);
+  double var_g = 0.0;
+  if (wants_variances(A)) {                            // Pa = sc2 I
     for (int m0 = 0; m0 < k; m0 += U) {
       double x[U];
 #pragma unroll
@@ -96,18 +90,15 @@ __global__ void __launch_bounds__(256) letkf_trivial_points_kernel(const PointAr
       for (int u = 0; u < U; ++u)
         if (m0 + u < k) var_g = fma(x[u], x[u], var_g);
     }
-    const double var_a = var_g * sc2;
-    if (var_g > 0.0 && var_a > 0.0)
-      cfv = A.relax_alpha_spread * sqrt(var_g * parm / (var_a * km1)) - A.relax_alpha_spread + 1.0;
   }
-  if (A.rtps_out)
-    A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skip) ? cfv : 1.0;
-  const double cdv = (!skip && A.relax_alpha != 0.0) ? A.relax_alpha * sqrt(parm) : 0.0;
-  // one member's analysis value (letkf_tools.f90:472-487 with w-bar = 0)
-  auto value = [&](const double x) { return skip ? xm + x : xm + beta * (cfv * (sc1 * x) + cdv * x) + (1.0 - beta) * x; };
+  const double cfv = relax_factor(A, parm, var_g, var_g * sc.sc2, km1);
+  if (A.rtps_out) A.rtps_out[pt + A.infl_sv * (long)v] = rtps_reported(A, skip, cfv);
+  const double cdv = rtpp_diag(A, parm);
+  // one member's analysis value, w-bar = 0
+  auto value = [&](const double x) { return skip ? xm + x : analysis_value(xm, x, beta, cfv * (sc.sc1 * x) + cdv * x, 0.0); };
   double q_mean = 0.0, q_sprd = 0.0;
   bool do_clamp = false;
-  if (!skip && A.q_sprd_max > 0.0 && v == A.iv_q_first) {   // :500-513
+  if (!skip && A.q_sprd_max > 0.0 && v == A.iv_q_first) {
     double s_ = 0.0;
     for (int m0 = 0; m0 < k; m0 += U) {
       double x[U];
@@ -141,7 +132,7 @@ __global__ void __launch_bounds__(256) letkf_trivial_points_kernel(const PointAr
     for (int u = 0; u < U; ++u)
       if (m0 + u < k) {
         double val = value(x[u]);
-        if (do_clamp) val = q_mean + (val - q_mean) * A.q_sprd_max / q_sprd;
+        if (do_clamp) val = q_clamped(val, q_mean, val - q_mean, q_sprd, A.q_sprd_max);
         av[(m0 + u) * sm] = val;
       }
   }

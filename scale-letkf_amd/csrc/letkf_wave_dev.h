@@ -27,12 +27,14 @@
 #include "letkf_search_dev.h"
 #include "letkf_jacobi_dev.h"
 #include "letkf_lane_dev.h"
+#include "letkf_rules_dev.h"
 #include "letkf_sched_dev.h"
 
 namespace letkf {
 
 using namespace jacobi_dev;
 using namespace lane_dev;
+using namespace rules_dev;
 
 // sum / max / min over all lanes of the point.  With two waves the partials meet in a 4-double LDS scratch; `slot`
 // alternates between consecutive calls (each call has its own barrier, so slot s is free again two calls later).
@@ -870,7 +872,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
 
     bool qskip = false;
     if (das && A.q_update_top > 0.0) qskip = g0[k * A.sm + A.iv_p * A.sv] < A.q_update_top;
-    // first variable of this variable-localisation class that is actually updated: its inflation slot drives the solve
+    // (rules_dev::q_update_skipped and solve_inflation, restated: as calls they move this kernel's register allocation)
     int v0 = 0;
     while (v0 < nv && (!((A.var_mask >> v0) & 1u) || (qskip && v0 >= A.iv_q_first && v0 <= A.iv_q_last))) ++v0;
     double* infl_p = das ? ((v0 < nv) ? &A.infl[pt + A.infl_sv * (long)v0] : nullptr) : &A.infl[pt];
@@ -1433,14 +1435,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
 #pragma unroll
       for (int r = 0; r < KR; ++r) g[r] *= il;
 
-      // adaptive inflation (common_letkf.f90:233-254), old rho everywhere above
-      if (A.infl_adaptive) {
-        const double parm4 = (parm1 - parm3) / parm2 - infl_old;
-        const double tq = (infl_old * parm2 + parm3) / parm2;
-        const double sigma_o = 2.0 / parm3 * (tq * tq);
-        const double gain = 0.04 * 0.04 / (sigma_o + 0.04 * 0.04);
-        p1 = infl_old + gain * parm4;            // reuse p1 as infl_new
-      }
+      if (A.infl_adaptive) p1 = adaptive_inflation(infl_old, parm1, parm2, parm3);   // reuse p1 as infl_new
       }
     }
     // apply phase on the matrix cores (see below); these instantiations also give points without observations a
@@ -1499,19 +1494,17 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       }
     }
 
-    // ------------------------------------------------------------ status (common_mtx.f90:66-78)
-    int st = 0;
+    // ------------------------------------------------------------ status
+    int st;
     {
       const double lmx = preduce<NW, 1>(colvalid ? lam : 0.0, red, rslot);
       const double lmn = preduce<NW, 2>(colvalid ? lam : 1e300, red, rslot);
-      if (!jconv && A.max_sweep >= 60) st = 1;   // (a solve that converges in the last permitted sweep is converged)
-      else if (!(lmx > 0.0)) st = 2;
-      else if (lmn < lmx * 1.4901161193847656e-08) st = 3;
+      st = eig_status(jconv, A.max_sweep, lmx, lmn);
     }
     // (a point without observations hands nothing on: its V = I would be a cold start anyway)
     have_u = uws != nullptr && st == 0 && solved;
-    const double sc1 = colvalid ? sqrt(km1 / lam) : 0.0;      // T spectrum
-    const double sc2 = colvalid ? 1.0 / lam : 0.0;            // Pa spectrum
+    const Spectra sc = spectra(lam, km1, colvalid);
+    const double sc1 = sc.sc1, sc2 = sc.sc2;                  // T spectrum, Pa spectrum
 
     PROF_MARK(5)
     // ------------------------------------------------------------ apply phase
@@ -1548,15 +1541,15 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           double cfv = 1.0;
           if (A.relax_alpha != 0.0) {
             cfv = 1.0 - A.relax_alpha;
-          } else if (A.relax_alpha_spread != 0.0) {
-            const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391
+          } else if (A.relax_alpha_spread != 0.0) {   // (rules_dev::relax_factor, restated)
+            const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;
             const double var_g = wave_sum(xv[v] * xv[v]);
             const double var_a = var_g * uniform(sc2);
             if (var_g > 0.0 && var_a > 0.0)
               cfv = A.relax_alpha_spread * sqrt(var_g * parm / (var_a * km1)) - A.relax_alpha_spread + 1.0;
           }
           cf[v] = uniform(cfv);
-          if (A.rtps_out && lane == 0 && ((A.var_mask >> v) & 1u)) {
+          if (A.rtps_out && lane == 0 && ((A.var_mask >> v) & 1u)) {   // (rules_dev::rtps_reported, restated)
             const bool skipv = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
             A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skipv) ? cfv : 1.0;
           }
@@ -1644,7 +1637,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         }
       }
       PROF_MARK(6)
-      // RTPS factor per variable (letkf_tools.f90:1982-1999) in the lanes of column c = 2 + v:
+      // RTPS factor per variable in the lanes of column c = 2 + v:
       // var_a = x'^T Pa x' = sum_j U_jv^2 / lam_j, var_g = sum_m x'_v[m]^2 (both still split over the 4 q groups)
       va += wshfl_xor(va, 16);
       va += wshfl_xor(va, 32);
@@ -1657,10 +1650,9 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         if (A.relax_alpha != 0.0) {
           cfv = 1.0 - A.relax_alpha;
         } else if (A.relax_alpha_spread != 0.0) {
-          const double parm = (A.relax_to_inflated_prior && isv) ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391
-          if (vg > 0.0 && va > 0.0) cfv = A.relax_alpha_spread * sqrt(vg * parm / (va * km1)) - A.relax_alpha_spread + 1.0;
+          cfv = rtps_factor(A, isv ? relax_parm(A, pt, v) : 1.0, vg, va, km1);
         }
-        if (A.rtps_out && q == 0 && isv && ((A.var_mask >> v) & 1u)) {   // work3da (letkf_tools.f90:460-462); skipped variables keep 1
+        if (A.rtps_out && q == 0 && isv && ((A.var_mask >> v) & 1u)) {   // (rules_dev::rtps_reported, restated)
           const bool skipv = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
           A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skipv) ? cfv : 1.0;
         }
@@ -1724,15 +1716,15 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         if ((r & 1) == 1) pin_acc<NB>(crow);
       }
       PROF_MARK(6)
-      // RTPS factor per variable (letkf_tools.f90:1982-1999), kept in SGPRs: var_a = x'^T Pa x' = sum_j U_jv^2 / lam_j
+      // RTPS factor per variable, kept in SGPRs: var_a = x'^T Pa x' = sum_j U_jv^2 / lam_j
       if (NV > 0) {
   #pragma unroll
         for (int v = 0; v < NV; ++v) {
           double cfv = 1.0;
           if (A.relax_alpha != 0.0) {
             cfv = 1.0 - A.relax_alpha;
-          } else if (A.relax_alpha_spread != 0.0) {
-            const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;   // :387-391
+          } else if (A.relax_alpha_spread != 0.0) {   // (rules_dev::relax_factor, restated)
+            const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;
             const double x = (lane < k) ? bmat[mrow_l * NBP + 2 + v] : 0.0;
             const double var_g = preduce<NW, 0>(x * x, red, rslot);
             const double var_a = preduce<NW, 0>(crow[2 + v] * crow[2 + v] * sc2, red, rslot);
@@ -1740,7 +1732,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
               cfv = A.relax_alpha_spread * sqrt(var_g * parm / (var_a * km1)) - A.relax_alpha_spread + 1.0;
           }
           cf[v] = uniform(cfv);
-          if (A.rtps_out && lane == 0 && ((A.var_mask >> v) & 1u)) {   // work3da (letkf_tools.f90:460-462); skipped variables keep 1
+          if (A.rtps_out && lane == 0 && ((A.var_mask >> v) & 1u)) {   // (rules_dev::rtps_reported, restated)
             const bool skipv = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
             A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skipv) ? cfv : 1.0;
           }
@@ -1756,12 +1748,12 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
 
     }
     PROF_MARK(7)
-    // ------------------------------------------------------------ analysis members (letkf_tools.f90:472-513)
+    // ------------------------------------------------------------ analysis members
     if (NV > 0 && das) {
       double* ap = a0 + moff;
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
-        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
+        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;   // (rules_dev::var_skipped, restated)
         double x, xm, xdt;
         if constexpr (MAPPLY) {
           // x' comes back from the LDS copy of B (it survives the output transposition): keeping the 22 registers of xv
@@ -1782,18 +1774,13 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         if (skip) {
           val = xm + x;
         } else {
-          double cdv = 0.0;
-          if (A.relax_alpha != 0.0) {              // RTPP diagonal term alpha*sqrt(parm), parm read before the update
-            const double parm = A.relax_to_inflated_prior ? A.infl[pt + A.infl_sv * (long)v] : 1.0;
-            cdv = A.relax_alpha * sqrt(parm);
-          }
-          const double pert = cf[v] * out[2 + v] + cdv * x;
-          val = xm + beta * (pert + sdot) + (1.0 - beta) * x;
-          if (A.q_sprd_max > 0.0 && v == A.iv_q_first) {      // :500-513
+          const double pert = cf[v] * out[2 + v] + rtpp_diag(A, pt, v) * x;
+          val = analysis_value(xm, x, beta, pert, sdot);
+          if (A.q_sprd_max > 0.0 && v == A.iv_q_first) {
             const double q_mean = preduce<NW, 0>(lane < k ? val : 0.0, red, rslot) / (double)k;
             const double dq = (lane < k) ? val - q_mean : 0.0;
             const double q_sprd = sqrt(preduce<NW, 0>(dq * dq, red, rslot) / km1) / q_mean;
-            if (q_sprd > A.q_sprd_max) val = q_mean + dq * A.q_sprd_max / q_sprd;
+            val = q_clamped(val, q_mean, dq, q_sprd, A.q_sprd_max);
           }
         }
         const bool inclass = (A.var_mask >> v) & 1u;
@@ -1802,7 +1789,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
         if (A.det_run && lane == 0 && inclass)
           a0[(k + 1) * A.sm + v * A.sv] = skip ? xdt : xdt + sdotd * beta;     // :489-497
       }
-      if (A.infl_adaptive) {                       // :396-398 (also without obs: the class copies its first slot), after every parm read above
+      if (A.infl_adaptive) {                       // (rules_dev::var_updated, restated; also without obs: the class copies its first slot), after every parm read above
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
           const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
