@@ -114,8 +114,8 @@ struct PointArgs {
   letkf_search_tables stab;
   const double *pri, *prj, *prlev, *prz;
   int* nobs_out;       // [npts] local observation count (modes 2, 3), or null
-  // mode 3: the horizontal survivors of each column (letkf_survivors_kernel): entry = 4 doubles (row | ctype << 32 as bits,
-  // nd_h, v_obs, err) in surv[], column b of this launch owns entries sv_off[b] .. sv_off[b + 1]; the points of the launch are
+  // mode 3: the horizontal survivors of each column (letkf_survivors_kernel), survivor entries (letkf_search_dev.h) in
+  // surv[], column b of this launch owns entries sv_off[b] .. sv_off[b + 1]; the points of the launch are
   // p = pt0 + a * pt_stride + b, a < npts / warm_stride levels, b < warm_stride columns
   const long* sv_off;
   const double* surv;

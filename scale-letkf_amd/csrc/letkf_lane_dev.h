@@ -93,6 +93,11 @@ __device__ __forceinline__ int mbcnt(const unsigned long long m) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
 }
 
+// the wave mask of the lanes below `lane`, for __popcll(m & lanes_below(lane)) where the mask is kept over many ballots
+__device__ __forceinline__ unsigned long long lanes_below(const int lane) {
+  return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+}
+
 // LDS written by some lanes of this wave, read by others: DS instructions of one wave execute in
 // order, so only the compiler has to be kept from reordering across the hand-off.
 __device__ __forceinline__ void wave_lds_sync() {

@@ -28,6 +28,8 @@ namespace letkf {
 namespace {
 
 using namespace search_dev;
+using lane_dev::lanes_below;
+using lane_dev::mbcnt;
 
 __device__ __forceinline__ unsigned long long key_bits(int criterion, const CalOut& c) {
   // monotone map key -> uint64 (all keys are positive doubles): smaller pattern == better candidate
@@ -55,26 +57,15 @@ __device__ __forceinline__ int sweep_group(const SearchArgs& A, const int gs, co
                                            SelState& st, unsigned int* hist) {
   const letkf_search_tables& t = A.t;
   const int lane = threadIdx.x & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   int cnt = 0;
   for (int m = gs; m < ge; ++m) {
     const int ic = t.group_member[m];
-    const double dzi = t.hori_loc[ic] * kDistZeroFac / t.dx;        // obs_local_range :1775-1778
-    const double dzj = t.hori_loc[ic] * kDistZeroFac / t.dy;
-    int imin, imax, jmin, jmax;
-    ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
-    ij_obsgrd_ext(t, ic, ri + dzi, rj + dzj, imax, jmax);
-    // the reference requires the extended mesh to cover the rectangle (DEBUG check :1780); clamp defensively
-    imin = max(imin, 1);
-    jmin = max(jmin, 1);
-    imax = min(imax, t.ngrdext_i[ic]);
-    jmax = min(jmax, t.ngrdext_j[ic]);
-    if (imin > imax || jmin > jmax) continue;
-    const long acb = t.ac_off[ic];
-    const int ld = t.ngrdext_i[ic] + 1;
-    for (int j = jmin; j <= jmax; ++j) {
-      const int lo = t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-      const int hi = t.ac_ext[acb + imax + (long)ld * (j - 1)];
+    const CellRect rc = cell_rect(t, ic, ri, rj);
+    if (rc.empty()) continue;
+    for (int j = rc.jmin; j <= rc.jmax; ++j) {
+      int lo, hi;
+      row_span(t, rc, j, lo, hi);
       for (int base = lo; base < hi; base += 64) {
         const int row = base + lane;
         CalOut c{0.0, -1.0, -1.0};
@@ -184,25 +175,15 @@ __device__ __forceinline__ int cache_group(const SearchArgs& A, const int gs, co
                                            const double rj, const double rlev, const double rz, double* cache) {
   const letkf_search_tables& t = A.t;
   const int lane = threadIdx.x & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   int cnt = 0;
   for (int m = gs; m < ge; ++m) {
     const int ic = t.group_member[m];
-    const double dzi = t.hori_loc[ic] * kDistZeroFac / t.dx;
-    const double dzj = t.hori_loc[ic] * kDistZeroFac / t.dy;
-    int imin, imax, jmin, jmax;
-    ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
-    ij_obsgrd_ext(t, ic, ri + dzi, rj + dzj, imax, jmax);
-    imin = max(imin, 1);
-    jmin = max(jmin, 1);
-    imax = min(imax, t.ngrdext_i[ic]);
-    jmax = min(jmax, t.ngrdext_j[ic]);
-    if (imin > imax || jmin > jmax) continue;
-    const long acb = t.ac_off[ic];
-    const int ld = t.ngrdext_i[ic] + 1;
-    for (int j = jmin; j <= jmax; ++j) {
-      const int lo = t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-      const int hi = t.ac_ext[acb + imax + (long)ld * (j - 1)];
+    const CellRect rc = cell_rect(t, ic, ri, rj);
+    if (rc.empty()) continue;
+    for (int j = rc.jmin; j <= rc.jmax; ++j) {
+      int lo, hi;
+      row_span(t, rc, j, lo, hi);
       for (int base = lo; base < hi; base += 64) {
         const int row = base + lane;
         CalOut c{0.0, -1.0, -1.0};
@@ -228,7 +209,7 @@ __device__ __forceinline__ int cache_group(const SearchArgs& A, const int gs, co
 __device__ __forceinline__ int select_from_cache(const SearchArgs& A, const int nc, const int nmax, const long out,
                                                  const double* cache, unsigned int* hist) {
   const int lane = threadIdx.x & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -357,7 +338,6 @@ __global__ void __launch_bounds__(256) letkf_search_kernel(const SearchArgs A) {
 
 // a wave-uniform value, said so: into scalar registers (what hipcc loads through the tables' plain pointers it keeps in
 // vector registers -- and spills to scratch inside the level loop)
-using lane_dev::mbcnt;
 using lane_dev::readlane_d;
 using lane_dev::uniform;
 using lane_dev::wave_lds_sync;
@@ -478,17 +458,8 @@ __global__ void __launch_bounds__(256) letkf_search_columns_kernel(const ColArgs
       const double vloc = uniform(t.vert_loc[ic]), hloc = t.hori_loc[ic];
       const bool fdiv = divby::in_range(vloc);
       const double yv = uniform(divby::reciprocal(fdiv ? vloc : 1.0));
-      const double dzi = hloc * kDistZeroFac / t.dx, dzj = hloc * kDistZeroFac / t.dy;
-      int imin, imax, jmin, jmax;
-      ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
-      ij_obsgrd_ext(t, ic, ri + dzi, rj + dzj, imax, jmax);
-      imin = max(imin, 1);
-      jmin = max(jmin, 1);
-      imax = min(imax, t.ngrdext_i[ic]);
-      jmax = min(jmax, t.ngrdext_j[ic]);
-      if (imin > imax || jmin > jmax) continue;
-      const long acb = t.ac_off[ic];
-      const int ld = t.ngrdext_i[ic] + 1;
+      const CellRect rc = cell_rect(t, ic, ri, rj);
+      if (rc.empty()) continue;
       int ns = 0;                                                 // survivors in the buffer
       if (A.nobs_ctype)
         for (int l = lane; l < nlev; l += 64) cprev[l] = cntl[l];
@@ -607,22 +578,19 @@ __global__ void __launch_bounds__(256) letkf_search_columns_kernel(const ColArgs
       };
 
       // one round past the last mesh row: the flush of what is left
-      for (int j = jmin; j <= jmax + 1; ++j) {
-        const bool last = j > jmax;
-        const int lo = last ? 0 : t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-        const int hi = last ? 0 : t.ac_ext[acb + imax + (long)ld * (j - 1)];
+      for (int j = rc.jmin; j <= rc.jmax + 1; ++j) {
+        const bool last = j > rc.jmax;
+        const int lo = last ? 0 : row_lo(t, rc, j), hi = last ? 0 : row_hi(t, rc, j);
         for (int base = lo; base < hi || (last && base == 0 && ns > 0); base += 64) {
           const int row = base + lane;
           bool ok = false;
           double nd_h = 0.0, vobs = 0.0, err = 0.0;
           if (row < hi) {
-            const double rdx = (ri - t.ob_ri[row]) * t.dx;        // :1876-1878
-            const double rdy = (rj - t.ob_rj[row]) * t.dy;
-            nd_h = sqrt(rdx * rdx + rdy * rdy) / hloc;
-            ok = !(nd_h > kDistZeroFac);                          // :1881
+            nd_h = horizontal_nd(t, hloc, ri, rj, row);
+            ok = inside_cutoff(nd_h);                             // :1881
             if (ok) {
-              if (vloc != 0.0) {
-                if (vm == 1) vobs = t.ob_lev[row];
+              if (vloc != 0.0) {                                  // vertical_obs_coord restated: as a call it reorders the
+                if (vm == 1) vobs = t.ob_lev[row];                // counting pass (profiles/r10_README.md)
                 else if (vm == 2) vobs = log(t.ob_dat[row]);
                 else if (vm != 3) vobs = log(t.ob_lev[row]);
               }
@@ -749,7 +717,7 @@ __device__ __forceinline__ void hist_thresh(const unsigned long long (&key_in)[K
                                             unsigned int* hist, unsigned long long& thresh, int& tie_budget,
                                             const double lin_scale = 0.0) {
   const int lane = threadIdx.x & 63;
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   unsigned long long key[KS];
 #pragma unroll
   for (int u = 0; u < KS; ++u) key[u] = key_in[u];
@@ -874,7 +842,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
   double* sb = smem_lim + (size_t)wv * cstride;                   // [kSurvL][4]: nd_h, v_obs, row, err
   int* cntl = reinterpret_cast<int*>(sb + 4 * kSurvL);            // [nlev] entries emitted so far per level
   unsigned int* hist = hist_all[wv];
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   SearchArgs PA;                                                  // for the per-point fall-back
   PA.t = t;
   PA.fill = A.fill;
@@ -914,35 +882,20 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
         const bool skip = t.varloc[ic] < kTiny;                   // local_cal :1843
         const int vm = t.vmode[ic];
         const double vloc = t.vert_loc[ic], hloc = t.hori_loc[ic];
-        const double dzi = hloc * kDistZeroFac / t.dx, dzj = hloc * kDistZeroFac / t.dy;
-        int imin, imax, jmin, jmax;
-        ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
-        ij_obsgrd_ext(t, ic, ri + dzi, rj + dzj, imax, jmax);
-        imin = max(imin, 1);
-        jmin = max(jmin, 1);
-        imax = min(imax, t.ngrdext_i[ic]);
-        jmax = min(jmax, t.ngrdext_j[ic]);
-        if (skip || imin > imax) jmax = jmin - 1;                 // (nothing to walk)
-        const long acb = t.ac_off[ic];
-        const int ld = t.ngrdext_i[ic] + 1;
-        for (int j = jmin; j <= jmax && !overflow; ++j) {
-          const int lo = t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-          const int hi = t.ac_ext[acb + imax + (long)ld * (j - 1)];
+        CellRect rc = cell_rect(t, ic, ri, rj);
+        if (skip || rc.imin > rc.imax) rc.jmax = rc.jmin - 1;     // (nothing to walk)
+        for (int j = rc.jmin; j <= rc.jmax && !overflow; ++j) {
+          int lo, hi;
+          row_span(t, rc, j, lo, hi);
           for (int base = lo; base < hi; base += 64) {
             const int row = base + lane;
             bool ok = false;
             double nd_h = 0.0, vobs = 0.0, err = 0.0;
             if (row < hi) {
-              const double rdx = (ri - t.ob_ri[row]) * t.dx;      // :1876-1878
-              const double rdy = (rj - t.ob_rj[row]) * t.dy;
-              nd_h = sqrt(rdx * rdx + rdy * rdy) / hloc;
-              ok = !(nd_h > kDistZeroFac);                        // :1881
+              nd_h = horizontal_nd(t, hloc, ri, rj, row);
+              ok = inside_cutoff(nd_h);                           // :1881
               if (ok) {
-                if (vloc != 0.0) {
-                  if (vm == 1) vobs = t.ob_lev[row];
-                  else if (vm == 2) vobs = log(t.ob_dat[row]);
-                  else if (vm != 3) vobs = log(t.ob_lev[row]);
-                }
+                vobs = vertical_obs_coord(t, vm, vloc, row);
                 err = t.ob_err[row];
               }
             }
@@ -1277,6 +1230,14 @@ __global__ void __launch_bounds__(256, 2) letkf_search_columns_limited_kernel(co
   LP_FLUSH();
 }
 
+// The grid of a kernel whose workgroup of four waves takes four columns (or points) at a time and strides on: one workgroup
+// per four while that is no more than wg_per_cu per CU, and never an empty grid.
+static int search_grid(const long n, const int num_cu, const int wg_per_cu) {
+  const long nwg = (n + 3) / 4;
+  const long g = (long)num_cu * wg_per_cu;
+  return (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
+}
+
 hipError_t launch_search_columns_limited(const letkf_search_tables& t, long nij1, int nlev, const double* rig,
                                          const double* rjg, const double* rlev, const double* rz, int fill, int* counts,
                                          const long* obs_off, int* obs_idx, double* rdiag_l, double* rloc_l,
@@ -1285,9 +1246,7 @@ hipError_t launch_search_columns_limited(const letkf_search_tables& t, long nij1
                cutd_ctype};
   const size_t lds = (size_t)4 * (4 * kSurvL + ((nlev + 1) & ~1)) * sizeof(double);
   if (hipError_t e = lds_opt_in(&letkf_search_columns_limited_kernel, lds)) return e;
-  const long nwg = (nij1 + 3) / 4;
-  const long g = (long)num_cu * 8;
-  const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
+  const int grid = search_grid(nij1, num_cu, 8);
 #ifdef LETKF_WAVE_PROF
   unsigned long long z[8] = {0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lim_prof), z, sizeof z);
@@ -1322,7 +1281,7 @@ struct RingBuildArgs {
   const double *rig, *rjg;
   int* counts;           // FILL = 0: [ncol * ngroup] survivors per (column, group)
   const long* goff;      // FILL = 1: [ncol * ngroup + 1] entry offsets (absolute), group-fastest
-  double* sv;            // entries: (row | ctype << 32 as bits, nd_h, v_obs, err)
+  double* sv;            // survivor entries (letkf_search_dev.h)
   int* roff;             // FILL = 1: [ncol * ngroup][kRings + 1] ring starts relative to the (column, group)'s first entry
   int gen;               // general ring key (r4, see ring_offset): criterion 3, and criterion 2 with several factors in a group
   const double* kref;    // gen: [ngroup] the group's reference offset (a lower estimate of its entries' offsets)
@@ -1347,7 +1306,7 @@ __global__ void __launch_bounds__(256) letkf_ring_survivors_kernel(const RingBui
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int* rpos = rpos_all[wv];
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   for (long cb = (long)blockIdx.x * 4 + wv; cb < A.ncol; cb += (long)gridDim.x * 4) {
     const long col = A.col0 + cb;
     const double ri = A.rig[col], rj = A.rjg[col];
@@ -1362,29 +1321,18 @@ __global__ void __launch_bounds__(256) letkf_ring_survivors_kernel(const RingBui
           if (t.varloc[ic] < kTiny) continue;                       // local_cal :1843
           const int vm = t.vmode[ic];
           const double vloc = t.vert_loc[ic], hloc = t.hori_loc[ic];
-          const double dzi = hloc * kDistZeroFac / t.dx, dzj = hloc * kDistZeroFac / t.dy;
-          int imin, imax, jmin, jmax;
-          ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
-          ij_obsgrd_ext(t, ic, ri + dzi, rj + dzj, imax, jmax);
-          imin = max(imin, 1);
-          jmin = max(jmin, 1);
-          imax = min(imax, t.ngrdext_i[ic]);
-          jmax = min(jmax, t.ngrdext_j[ic]);
-          if (imin > imax || jmin > jmax) continue;
-          const long acb = t.ac_off[ic];
-          const int ld = t.ngrdext_i[ic] + 1;
-          for (int j = jmin; j <= jmax; ++j) {
-            const int lo = t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-            const int hi = t.ac_ext[acb + imax + (long)ld * (j - 1)];
+          const CellRect rc = cell_rect(t, ic, ri, rj);
+          if (rc.empty()) continue;
+          for (int j = rc.jmin; j <= rc.jmax; ++j) {
+            int lo, hi;
+            row_span(t, rc, j, lo, hi);
             for (int base = lo; base < hi; base += 64) {
               const int row = base + lane;
               bool ok = false;
               double nd_h = 0.0;
               if (row < hi) {
-                const double rdx = (ri - t.ob_ri[row]) * t.dx;      // :1876-1878
-                const double rdy = (rj - t.ob_rj[row]) * t.dy;
-                nd_h = sqrt(rdx * rdx + rdy * rdy) / hloc;
-                ok = !(nd_h > kDistZeroFac);                        // :1881
+                nd_h = horizontal_nd(t, hloc, ri, rj, row);
+                ok = inside_cutoff(nd_h);                           // :1881
               }
               const unsigned long long mk = __ballot(ok);
               double hk = nd_h * nd_h;
@@ -1400,17 +1348,9 @@ __global__ void __launch_bounds__(256) letkf_ring_survivors_kernel(const RingBui
                   const unsigned long long mr = __ballot(ok && ring == r);
                   if (!mr) continue;
                   const int b0 = rpos[r];
-                  if (what == 2 && ok && ring == r) {
-                    double vobs = 0.0;
-                    if (vloc != 0.0) {
-                      if (vm == 1) vobs = t.ob_lev[row];
-                      else if (vm == 2) vobs = log(t.ob_dat[row]);
-                      else if (vm != 3) vobs = log(t.ob_lev[row]);
-                    }
-                    const long o = 4 * (out + b0 + __popcll(mr & lt_mask));
-                    *reinterpret_cast<double2*>(&A.sv[o]) = double2{__longlong_as_double((long)row | ((long)ic << 32)), nd_h};
-                    *reinterpret_cast<double2*>(&A.sv[o + 2]) = double2{vobs, t.ob_err[row]};
-                  }
+                  if (what == 2 && ok && ring == r)
+                    survivor_store(A.sv, out + b0 + __popcll(mr & lt_mask), row, ic, nd_h, vertical_obs_coord(t, vm, vloc, row),
+                                   t.ob_err[row]);
                   wave_lds_sync();
                   if (lane == 0) rpos[r] = b0 + __popcll(mr);
                   wave_lds_sync();
@@ -1491,7 +1431,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
   long* brw = brw_all[wv];
   double* berr = berr_all[wv];
   int* nct = s_nct[wv];
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   for (int i = threadIdx.x; i < t.nctype; i += 256) {
     s_vm[i] = t.vmode[i];
     s_vloc[i] = t.vert_loc[i];
@@ -1521,7 +1461,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
         const int* ro = A.roff + (cb * ng + ig) * (kRings + 1);
         // one entry -> its selection key (the squared normalised distance as bits), or kNoKey
         auto entry_key = [&](const double2 a2, const double2 b2, double& nd_out) -> bool {
-          const int ic = (int)(__double_as_longlong(a2.x) >> 32);
+          const int ic = survivor_ctype(survivor_bits(a2.x));
           const int vm = s_vm[ic];
           const double vloc = s_vloc[ic];
           const double vref = vm == 1 ? vz : vlnp;
@@ -1551,12 +1491,12 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
             }
             const unsigned long long mk = __ballot(acc);
             if (acc) {
-              const long rw = __double_as_longlong(a2.x);
-              const int ic = (int)(rw >> 32);
+              const long rw = survivor_bits(a2.x);
+              const int ic = survivor_ctype(rw);
               if (A.fill) {
                 const long o = out0 + emitted + nsel + __popcll(mk & lt_mask);
                 const double rloc = s_varloc[ic] * exp(-0.5 * nd);                       // :1899
-                A.obs_idx[o] = (int)(rw & 0xffffffffL);
+                A.obs_idx[o] = survivor_row(rw);
                 A.rdiag_l[o] = b2.y * b2.y / rloc;                                        // :1903
                 A.rloc_l[o] = rloc;
               }
@@ -1624,12 +1564,12 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
                 const int e = pos + (u - nbs) * 64 + lane;
                 double nd;
                 if (e < n_g && entry_key(ta[u], tb[u], nd)) {
-                  rwr[u] = __double_as_longlong(ta[u].x);
+                  rwr[u] = survivor_bits(ta[u].x);
                   if constexpr (!GEN) {
                     keyr[u] = (unsigned long long)__double_as_longlong(nd);
                     errr[u] = tb[u].y;
                   } else {
-                    const double rloc = s_varloc[(int)(rwr[u] >> 32)] * exp(-0.5 * nd);          // :1899
+                    const double rloc = s_varloc[survivor_ctype(rwr[u])] * exp(-0.5 * nd);          // :1899
                     if (t.criterion == 2) {
                       keyr[u] = 0x7FFFFFFFFFFFFFFFull - (unsigned long long)__double_as_longlong(rloc);
                       errr[u] = tb[u].y;
@@ -1700,7 +1640,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
           if (A.fill) {
             for (int j = lane; j < nB; j += 64) {
               const long rw = brw[j];
-              const int ic = (int)(rw >> 32);
+              const int ic = survivor_ctype(rw);
               double rloc, rdiag;
               if constexpr (!GEN) {
                 const double nd = __longlong_as_double((long long)bkey[j]);
@@ -1714,7 +1654,7 @@ __global__ void __launch_bounds__(256, 2) letkf_search_rings_kernel(const RingSe
                 rdiag = __longlong_as_double((long long)bkey[j]);
               }
               const long o = out0 + emitted + j;
-              A.obs_idx[o] = (int)(rw & 0xffffffffL);
+              A.obs_idx[o] = survivor_row(rw);
               A.rdiag_l[o] = rdiag;
               A.rloc_l[o] = rloc;
             }
@@ -1759,9 +1699,7 @@ hipError_t launch_ring_survivors(const letkf_search_tables& t, long col0, long n
                                  int* counts, const long* goff, double* sv, int* roff, const double* kref, int num_cu, hipStream_t st) {
   if (ncol <= 0) return hipSuccess;
   RingBuildArgs a{t, col0, ncol, rig, rjg, counts, goff, sv, roff, kref != nullptr ? 1 : 0, kref};
-  const long nwg = (ncol + 3) / 4;
-  const long g = (long)num_cu * 8;
-  const int grid = (int)(nwg < g ? nwg : g);
+  const int grid = search_grid(ncol, num_cu, 8);
   if (fill) hipLaunchKernelGGL(letkf_ring_survivors_kernel<true>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(letkf_ring_survivors_kernel<false>, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
@@ -1774,9 +1712,7 @@ hipError_t launch_search_rings(const letkf_search_tables& t, long col0, long nco
   if (ncol <= 0) return hipSuccess;
   RingSearchArgs a{t, col0, ncol, nij1, nlev, rlev, rz, fill, counts, obs_off, obs_idx, rdiag_l, rloc_l, nobs_ctype, cutd_ctype,
                    goff, sv, roff, kref};
-  const long nwg = (ncol + 3) / 4;
-  const long g = (long)num_cu * 4;
-  const int grid = (int)(nwg < g ? nwg : g);
+  const int grid = search_grid(ncol, num_cu, 4);
   if (kref) hipLaunchKernelGGL(letkf_search_rings_kernel<true>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(letkf_search_rings_kernel<false>, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
@@ -1789,9 +1725,8 @@ int search_rings_lds_survivors() { return kSurvL; }
 // ------------------------------------------------------------------ the horizontal half of obs_local, once per column
 // (the list-free route of letkf_das_columns_dev; the vertical half runs inside the loop body kernel, letkf_wave_dev.h mode 3).
 // One wave per column walks the rectangle of sorting-mesh cells of every combined type exactly like the column search and
-// keeps the rows inside the horizontal cut-off, in the reference's list order: entry = (row | ctype << 32 as bits, nd_h,
-// v_obs, err) with v_obs the observation's vertical coordinate in its ctype's mode (lev, ln lev, ln dat); the entries of a
-// type are padded to a multiple of 64.
+// keeps the rows inside the horizontal cut-off, in the reference's list order, as survivor entries (letkf_search_dev.h); the
+// entries of a type are padded to a multiple of 64.
 // FILL = false: counts[col] = survivors of the column; FILL = true: writes them at sv + 4 * sv_off[col].
 struct SurvArgs {
   letkf_search_tables t;
@@ -1808,7 +1743,7 @@ __global__ void __launch_bounds__(256) letkf_survivors_kernel(const SurvArgs A) 
   const letkf_search_tables& t = A.t;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lanes_below(lane);
   for (long cb = (long)blockIdx.x * 4 + wv; cb < A.ncol; cb += (long)gridDim.x * 4) {
     const long col = A.col0 + cb;
     const double ri = A.rig[col], rj = A.rjg[col];
@@ -1819,54 +1754,30 @@ __global__ void __launch_bounds__(256) letkf_survivors_kernel(const SurvArgs A) 
       if (t.varloc[ic] < kTiny) continue;                         // local_cal :1843
       const int vm = t.vmode[ic];
       const double vloc = t.vert_loc[ic], hloc = t.hori_loc[ic];
-      const double dzi = hloc * kDistZeroFac / t.dx, dzj = hloc * kDistZeroFac / t.dy;
-      int imin, imax, jmin, jmax;
-      ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
-      ij_obsgrd_ext(t, ic, ri + dzi, rj + dzj, imax, jmax);
-      imin = max(imin, 1);
-      jmin = max(jmin, 1);
-      imax = min(imax, t.ngrdext_i[ic]);
-      jmax = min(jmax, t.ngrdext_j[ic]);
-      if (imin > imax || jmin > jmax) continue;
-      const long acb = t.ac_off[ic];
-      const int ld = t.ngrdext_i[ic] + 1;
-      for (int j = jmin; j <= jmax; ++j) {
-        const int lo = t.ac_ext[acb + (imin - 1) + (long)ld * (j - 1)];
-        const int hi = t.ac_ext[acb + imax + (long)ld * (j - 1)];
+      const CellRect rc = cell_rect(t, ic, ri, rj);
+      if (rc.empty()) continue;
+      for (int j = rc.jmin; j <= rc.jmax; ++j) {
+        int lo, hi;
+        row_span(t, rc, j, lo, hi);
         for (int base = lo; base < hi; base += 64) {
           const int row = base + lane;
           bool ok = false;
           double nd_h = 0.0;
           if (row < hi) {
-            const double rdx = (ri - t.ob_ri[row]) * t.dx;        // :1876-1878
-            const double rdy = (rj - t.ob_rj[row]) * t.dy;
-            nd_h = sqrt(rdx * rdx + rdy * rdy) / hloc;
-            ok = !(nd_h > kDistZeroFac);                          // :1881
+            nd_h = horizontal_nd(t, hloc, ri, rj, row);
+            ok = inside_cutoff(nd_h);                             // :1881
           }
           const unsigned long long mk = __ballot(ok);
-          if (FILL && ok) {
-            double vobs = 0.0;
-            if (vloc != 0.0) {
-              if (vm == 1) vobs = t.ob_lev[row];
-              else if (vm == 2) vobs = log(t.ob_dat[row]);
-              else if (vm != 3) vobs = log(t.ob_lev[row]);
-            }
-            const long o = 4 * (out + ns + __popcll(mk & lt_mask));
-            const long rw = (long)row | ((long)ic << 32);
-            *reinterpret_cast<double2*>(&A.sv[o]) = double2{__longlong_as_double(rw), nd_h};
-            *reinterpret_cast<double2*>(&A.sv[o + 2]) = double2{vobs, t.ob_err[row]};
-          }
+          if (FILL && ok)
+            survivor_store(A.sv, out + ns + __popcll(mk & lt_mask), row, ic, nd_h, vertical_obs_coord(t, vm, vloc, row),
+                           t.ob_err[row]);
           ns += __popcll(mk);
         }
       }
       // every type's segment is padded to whole chunks of 64 entries (nd_h = 1e30: outside every cut-off), so that a chunk
       // of the loop body kernel is of ONE type and reads the type's numbers through the scalar cache
       const long npad = (64 - (ns & 63)) & 63;
-      if (FILL && lane < npad) {
-        const long o = 4 * (out + ns + lane);
-        *reinterpret_cast<double2*>(&A.sv[o]) = double2{__longlong_as_double((long)ic << 32), 1e30};
-        *reinterpret_cast<double2*>(&A.sv[o + 2]) = double2{0.0, 1.0};
-      }
+      if (FILL && lane < npad) survivor_store_pad(A.sv, out + ns + lane, ic);
       ns += npad;
     }
     if (!FILL && lane == 0) A.counts[cb] = (int)ns;
@@ -1877,9 +1788,7 @@ hipError_t launch_survivors(const letkf_search_tables& t, long col0, long ncol, 
                             int* counts, const long* sv_off, double* sv, int num_cu, hipStream_t st) {
   if (ncol <= 0) return hipSuccess;
   SurvArgs a{t, col0, ncol, rig, rjg, counts, sv_off, sv};
-  const long nwg = (ncol + 3) / 4;
-  const long g = (long)num_cu * 8;
-  const int grid = (int)(nwg < g ? nwg : g);
+  const int grid = search_grid(ncol, num_cu, 8);
   if (fill) hipLaunchKernelGGL(letkf_survivors_kernel<true>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(letkf_survivors_kernel<false>, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
@@ -1895,17 +1804,13 @@ hipError_t launch_search_columns(const letkf_search_tables& t, long nij1, int nl
   if (hipError_t e = lds_opt_in(kern, lds)) return e;
   // one column per wave while that takes no more than 64 workgroups per CU: the columns' costs differ (empty ones beside
   // dense ones) and the dispatcher evens them out; beyond that the waves stride over the columns
-  const long nwg = (nij1 + 3) / 4;
-  const long g = (long)num_cu * 64;
-  const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
+  const int grid = search_grid(nij1, num_cu, 64);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
 hipError_t launch_search(const SearchArgs& a, int num_cu, hipStream_t st) {
-  const long nwg = (a.npts + 3) / 4;
-  const long g = (long)num_cu * 8;
-  const int grid = (int)(nwg < g ? (nwg > 0 ? nwg : 1) : g);
+  const int grid = search_grid(a.npts, num_cu, 8);
   // the candidate cache is only touched in limited mode: without a limit the kernel keeps its full occupancy
   const size_t lds = a.limited ? (size_t)4 * 4 * kCacheCap * sizeof(double) : 0;
   if (hipError_t e = lds_opt_in(&letkf_search_kernel, lds)) return e;

@@ -750,7 +750,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           const long ptn = two ? pt + (A.pt_stride ? A.pt_stride : S) : pt;
           const double v_z = A.prz[pt], v_p = log(A.prlev[pt]), l_rain = log(t.rain_base);
           const double v_z1 = A.prz[ptn], v_p1 = log(A.prlev[ptn]);
-          const unsigned long long lt_mask = (wlane == 0) ? 0ull : (~0ull >> (64 - wlane));
+          const unsigned long long lt_mask = lanes_below(wlane);
           long s_lo = A.sv_off[rb], s_hi = A.sv_off[rb + 1];
 #ifdef LETKF_CHECKED
           {   // the run's column is one of the launch's, its survivors fit the slot the host sized, the slot is one of the grid's
@@ -791,8 +791,8 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
             int ic_s = -1, vm_s = 0;
             double vloc_s = 0.0, varloc_s = 0.0;
             auto eval = [&](const double2& ca, const double2& cb, const bool live) {
-              const long rw = __double_as_longlong(ca.x);
-              const int ic0 = __builtin_amdgcn_readfirstlane((int)(rw >> 32));
+              const long rw = survivor_bits(ca.x);
+              const int ic0 = __builtin_amdgcn_readfirstlane(survivor_ctype(rw));
               if (ic0 != ic_s) {
                 ic_s = ic0;
                 vm_s = t.vmode[ic0];
@@ -805,7 +805,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
                 const unsigned long long mk = __ballot(acc_);
                 if (acc_ && LETKF_CHECK(ntot + __popcll(mk) <= A.sl_cap, 5, ntot + __popcll(mk), A.sl_cap)) {
                   const long j = o0 + ntot + __popcll(mk & lt_mask);
-                  A.sl_idx[j] = (int)(rw & 0xffffffffL);
+                  A.sl_idx[j] = survivor_row(rw);
                   A.sl_rd[j] = vo.rdiag;
                   A.sl_rl[j] = vo.rloc;
                 }
@@ -817,7 +817,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
                 const unsigned long long mk = __ballot(acc_);
                 if (acc_ && LETKF_CHECK(ntot1 + __popcll(mk) <= A.sl_cap, 6, ntot1 + __popcll(mk), A.sl_cap)) {
                   const long j = o1 + ntot1 + __popcll(mk & lt_mask);
-                  A.sl_idx[j] = (int)(rw & 0xffffffffL);
+                  A.sl_idx[j] = survivor_row(rw);
                   A.sl_rd[j] = vo.rdiag;
                   A.sl_rl[j] = vo.rloc;
                 }
@@ -1076,7 +1076,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           using namespace search_dev;
           const letkf_search_tables& t = A.stab;
           const double ri = A.pri[pt], rj = A.prj[pt], rlev = A.prlev[pt], rz = A.prz[pt];
-          const unsigned long long lt_mask = (wlane == 0) ? 0ull : (~0ull >> (64 - wlane));
+          const unsigned long long lt_mask = lanes_below(wlane);
           int cnt = 0, ntot = 0, nconv = 0;                   // staged entries / accepted so far / entries at the front
                                                               // that are already in final form (wave-uniform)
           // stage buffer, phase A: (row, rdiag, rloc) as the candidates are accepted; phase B (convert): lane = entry,
@@ -1102,7 +1102,8 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           for (int m = 0; m < t.group_start[t.ngroup]; ++m) {
             const int ic = t.group_member[m];
             const int vm = t.vmode[ic];
-            const double dzi = t.hori_loc[ic] * kDistZeroFac / t.dx;        // obs_local_range :1775-1778
+            // search_dev::cell_rect restated (as a call it moves this kernel's scratch: profiles/r10_README.md)
+            const double dzi = t.hori_loc[ic] * kDistZeroFac / t.dx;
             const double dzj = t.hori_loc[ic] * kDistZeroFac / t.dy;
             int imin, imax, jmin, jmax;
             ij_obsgrd_ext(t, ic, ri - dzi, rj - dzj, imin, jmin);
@@ -1132,7 +1133,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
             for (int j0 = jmin; j0 <= jmax; j0 += 64) {                      // 64 mesh rows at a time: lane = row
               const int nr = min(64, jmax - j0 + 1);
               int lo_l = 0, hi_l = 0;
-              if (wlane < nr) {
+              if (wlane < nr) {                                              // search_dev::row_span restated, lane = mesh row
                 lo_l = t.ac_ext[acb + (imin - 1) + (long)ld * (j0 + wlane - 1)];
                 hi_l = t.ac_ext[acb + imax + (long)ld * (j0 + wlane - 1)];
               }
