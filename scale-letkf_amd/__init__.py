@@ -168,13 +168,10 @@ def obs_mesh_dims(typ_ctype, hori_loc_ctype, obs_sort_grid_spacing, max_nobs_per
     mx = np.ascontiguousarray(max_nobs_per_grid, dtype=np.int32)
     ms = np.ascontiguousarray(obs_min_spacing, dtype=np.float64)
     nc = len(ty)
-    o = {n: np.zeros(max(nc, 1), dtype=np.int32) for n in ("ngrd_i", "ngrd_j", "ngrdsch_i", "ngrdsch_j", "ngrdext_i", "ngrdext_j")}
-    o["grdspc_i"], o["grdspc_j"] = np.zeros(max(nc, 1)), np.zeros(max(nc, 1))
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib().letkf_obs_mesh_dims(C.c_int32(nc), p(ty), p(hl), C.c_int32(len(sp)), p(sp), p(mx), p(ms), C.c_double(dx),
-                                   C.c_double(dy), C.c_int32(nlon), C.c_int32(nlat), p(o["ngrd_i"]), p(o["ngrd_j"]),
-                                   p(o["grdspc_i"]), p(o["grdspc_j"]), p(o["ngrdsch_i"]), p(o["ngrdsch_j"]),
-                                   p(o["ngrdext_i"]), p(o["ngrdext_j"]))
+    outs = ("ngrd_i", "ngrd_j", "grdspc_i", "grdspc_j", "ngrdsch_i", "ngrdsch_j", "ngrdext_i", "ngrdext_j")   # the entry's order
+    o = {n: np.zeros(max(nc, 1), dtype=np.float64 if n.startswith("grdspc") else np.int32) for n in outs}
+    p = _hptr
+    rc = lib().letkf_obs_mesh_dims(nc, p(ty), p(hl), len(sp), p(sp), p(mx), p(ms), dx, dy, nlon, nlat, *[p(v) for v in o.values()])
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_obs_mesh_dims: {rc}: {lib().letkf_amd_last_error().decode()}")
     return {k: v[:nc].copy() for k, v in o.items()}
@@ -253,20 +250,17 @@ class ObsTable:
     def set_varloc(self, varloc):
         import numpy as np
         v = np.ascontiguousarray(varloc, dtype=np.float64)
-        self._ctx._check(self._ctx._l.letkf_obs_table_set_varloc(self._ctx._c, self._h, v.ctypes.data_as(C.c_void_p)))
+        self._ctx._check(self._ctx._l.letkf_obs_table_set_varloc(self._ctx._c, self._h, _hptr(v)))
 
     def download(self):
         """obsda_sort and the metadata as numpy arrays (letkf_obs_table_download)."""
         import numpy as np
         i = self.info()
-        nt, kld = i.nobstotal, i.kld
-        o = dict(ensval=np.zeros((max(nt, 1), kld)), val=np.zeros(max(nt, 1)), qc=np.zeros(max(nt, 1), np.int32),
-                 ob_ri=np.zeros(max(nt, 1)), ob_rj=np.zeros(max(nt, 1)), ob_lev=np.zeros(max(nt, 1)),
-                 ob_dat=np.zeros(max(nt, 1)), ob_err=np.zeros(max(nt, 1)), ac_ext=np.zeros(max(i.nacx, 1), np.int32))
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._ctx._check(self._ctx._l.letkf_obs_table_download(
-            self._ctx._c, self._h, p(o["ensval"]), p(o["val"]), p(o["qc"]), p(o["ob_ri"]), p(o["ob_rj"]), p(o["ob_lev"]),
-            p(o["ob_dat"]), p(o["ob_err"]), p(o["ac_ext"])))
+        nt, n1 = i.nobstotal, max(i.nobstotal, 1)
+        o = dict(ensval=np.zeros((n1, i.kld)), val=np.zeros(n1), qc=np.zeros(n1, np.int32), ob_ri=np.zeros(n1), ob_rj=np.zeros(n1),
+                 ob_lev=np.zeros(n1), ob_dat=np.zeros(n1), ob_err=np.zeros(n1), ac_ext=np.zeros(max(i.nacx, 1), np.int32))
+        ptrs = [_hptr(v) for v in o.values()]      # (o is in the entry's argument order)
+        self._ctx._check(self._ctx._l.letkf_obs_table_download(self._ctx._c, self._h, *ptrs))
         return {k: (v[:i.nacx] if k == "ac_ext" else v[:nt]) for k, v in o.items()}
 
 
@@ -304,32 +298,74 @@ class BetaParams(C.Structure):
                 ("dy", C.c_double)]
 
 
-EXPORTS = ["letkf_amd_abi_version", "letkf_amd_last_error", "letkf_ctx_create", "letkf_ctx_destroy",
-           "letkf_ctx_set_stream", "letkf_ctx_set_option", "letkf_ctx_synchronize", "letkf_core_c", "letkf_core_batch_dev",
-           "letkf_das_points_dev", "letkf_das_points_fused_dev", "letkf_das_columns_dev", "letkf_obs_search_dev", "letkf_obs_search_columns_dev", "letkf_ens_to_perturbations_dev", "letkf_ens_mean_dev",
-           "letkf_state_trans_dev", "letkf_member_points_dev", "letkf_ens_spread_dev",
-           "letkf_obs_departure_dev", "letkf_obs_mesh_sort_dev", "letkf_obs_halo_plan_dev",
-           "letkf_obs_gather_rows_dev", "letkf_obs_gather_i32_dev", "letkf_monit_dep_dev",
-           "letkf_additive_inflation_dev", "letkf_addinfl_weight_dev",
-           "letkf_var_local_classes", "letkf_ctype_merge_groups", "letkf_radar_only", "letkf_relax_beta_dev",
-           "letkf_infl_init_dev", "letkf_obs_allgatherv_dev", "letkf_alltoallv_dev", "letkf_allreduce_sum_i32_dev",
-           "letkf_members_alltoall_dev",
-           "letkf_obs_mesh_dims", "letkf_set_obs_local_dev", "letkf_set_obs_finish_dev", "letkf_set_obs_dev",
-           "letkf_obs_table_info_get", "letkf_obs_table_search", "letkf_obs_table_set_varloc", "letkf_obs_table_download",
-           "letkf_obs_table_destroy", "letkf_efso_points_dev", "letkf_efso_columns_dev", "letkf_efso_obsense_dev",
-           "letkf_das_obs_dev", "letkf_obs_target_var", "letkf_efso_locadv_dev", "letkf_efso_search_dev",
-           "letkf_efso_norm_dev", "letkf_efso_summary_dev",
-           "letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path", "letkf_sched_plan_check", "letkf_sched_plan_check_units"]
-
-# ctypes signatures of the entries that are called with them (include/letkf_amd.h; pointers as void *)
-_VP, _I32, _I64, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+# ctypes signature of every entry include/letkf_amd.h declares, in its order (pointers of any kind as void *): ctypes converts or
+# refuses a bare Python number at the call.  Written out by hand, the header is not read here; tests/test_abi.py keeps them in step.
+_VP, _I32, _I64, _F64, _INT = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 ARGTYPES = {
+    "letkf_amd_abi_version": [],
+    "letkf_amd_last_error": [],
+    "letkf_ctx_create": [_INT, _VP],
+    "letkf_ctx_destroy": [_VP],
+    "letkf_ctx_set_stream": [_VP, _VP],
+    "letkf_ctx_synchronize": [_VP],
+    "letkf_ctx_set_option": [_VP, _INT, _INT],
+    "letkf_core_c": [_INT, _INT, _INT, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_core_batch_dev": [_VP, _VP],
+    "letkf_das_points_dev": [_VP, _VP],
+    "letkf_ens_to_perturbations_dev": [_VP, _I32, _I32, _I64, _VP, _I64, _I64, _I64],
+    "letkf_ens_mean_dev": [_VP, _I32, _I32, _I64, _VP, _I64, _I64, _I64],
+    "letkf_obs_search_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP],
+    "letkf_obs_search_columns_dev": [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_das_points_fused_dev": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_das_columns_dev": [_VP, _VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _I64, _VP],
+    "letkf_state_trans_dev": [_VP, _VP, _I32, _I32, _I32, _I32, _VP, _I32],
+    "letkf_member_points_dev": [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I64, _I64, _I64, _I64],
+    "letkf_ens_spread_dev": [_VP, _I32, _I32, _I64, _VP, _I64, _I64, _I64, _VP],
+    "letkf_obs_departure_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _VP],
+    "letkf_obs_mesh_sort_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_obs_halo_plan_dev": [_VP, _VP, _VP, _VP, _VP, _I64, _VP],
+    "letkf_obs_gather_rows_dev": [_VP, _I64, _VP, _I32, _VP, _I64, _VP, _I64],
+    "letkf_obs_gather_i32_dev": [_VP, _I64, _VP, _VP, _VP],
+    "letkf_monit_dep_dev": [_VP, _I32, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_additive_inflation_dev": [_VP, _I32, _I32, _I64, _I64, _VP, _VP, _I64, _I64, _I64, _F64, _VP, _VP, _I64, _I64, _I32,
+                                     _I32, _VP],
+    "letkf_addinfl_weight_dev": [_VP, _I64, _VP, _VP, _I64, _VP, _VP, _F64, _F64, _F64, _VP],
+    "letkf_var_local_classes": [_I32, _I32, _VP, _VP, _VP, _VP],
+    "letkf_ctype_merge_groups": [_I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP],
+    "letkf_radar_only": [_I32, _VP, _I32],
+    "letkf_relax_beta_dev": [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP],
+    "letkf_infl_init_dev": [_VP, _I64, _VP, _F64, _F64],
+    "letkf_obs_allgatherv_dev": [_VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP],
+    "letkf_alltoallv_dev": [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _VP],
+    "letkf_allreduce_sum_i32_dev": [_VP, _VP, _I32, _I64, _VP],
+    "letkf_members_alltoall_dev": [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _I64, _I64, _I64],
+    "letkf_obs_mesh_dims": [_I32, _VP, _VP, _I32, _VP, _VP, _VP, _F64, _F64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_set_obs_local_dev": [_VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP],
+    "letkf_set_obs_finish_dev": [_VP, _VP, _VP, _VP, _I64, _VP],
+    "letkf_set_obs_dev": [_VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP],
+    "letkf_obs_table_info_get": [_VP, _VP],
+    "letkf_obs_table_search": [_VP, _VP],
+    "letkf_obs_table_set_varloc": [_VP, _VP, _VP],
+    "letkf_obs_table_download": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_obs_table_destroy": [_VP],
+    "letkf_efso_points_dev": [_VP, _VP],
+    "letkf_efso_columns_dev": [_VP, _VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _I64],
+    "letkf_efso_obsense_dev": [_VP, _I32, _I64, _VP, _VP, _VP],
+    "letkf_das_obs_dev": [_VP, _VP, _VP],
+    "letkf_obs_target_var": [_I32],
     "letkf_efso_locadv_dev": [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _F64, _F64, _F64, _F64, _VP, _VP],
     "letkf_efso_search_dev": [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64],
     "letkf_efso_norm_dev": [_VP, _VP, _I64, _I32, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP,
                             _VP],
     "letkf_efso_summary_dev": [_VP, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _I32, _F64, _VP, _VP, _VP],
+    "letkf_ctx_last_path": [_VP, _VP, _I32],
+    "letkf_ctx_timing_enable": [_VP, _INT],
+    "letkf_ctx_timing_read": [_VP, _VP, _VP, _INT],
+    "letkf_sched_plan_check": [_I64, _I64, _I32, _I32, _I32, _I32],
+    "letkf_sched_plan_check_units": [_I64, _I64, _I32, _I32, _I32, _I32, _I32],
 }
+RESTYPES = {"letkf_amd_last_error": C.c_char_p, "letkf_core_c": None}     # every other entry returns int
+EXPORTS = list(ARGTYPES)
 
 _lib = None
 
@@ -346,19 +382,20 @@ def lib():
         except ImportError:
             pass
         _lib = C.CDLL(LIB_PATH)
-        _lib.letkf_amd_last_error.restype = C.c_char_p
-        for name in EXPORTS:
-            getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
         for name, at in ARGTYPES.items():
-            f = getattr(_lib, name)
-            f.argtypes, f.restype = at, C.c_int
+            f = getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
+            f.argtypes, f.restype = at, RESTYPES.get(name, _INT)
     return _lib
 
 
 def _ptr(t):
-    if t is None:
-        return None
-    return C.c_void_p(t.data_ptr())
+    """device tensor -> void * (None: NULL)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _hptr(a):
+    """host numpy array -> void * (None: NULL)"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class Context:
@@ -367,8 +404,7 @@ class Context:
     def __init__(self, device=-1, stream=None):
         self._l = lib()
         self._c = C.c_void_p()
-        rc = self._l.letkf_ctx_create(C.c_int(device), C.byref(self._c))
-        self._check(rc)
+        self._check(self._l.letkf_ctx_create(device, C.byref(self._c)))
         if stream is not None:
             self.set_stream(stream)
 
@@ -398,23 +434,23 @@ class Context:
     OPT_SMALL_K_TRIO = 6       # LETKF_OPT_SMALL_K_TRIO
 
     def set_option(self, option, value):
-        self._check(self._l.letkf_ctx_set_option(self._c, C.c_int(option), C.c_int(value)))
+        self._check(self._l.letkf_ctx_set_option(self._c, option, value))
 
     def synchronize(self):
         self._check(self._l.letkf_ctx_synchronize(self._c))
 
     def timing_enable(self, on=True):
-        self._check(self._l.letkf_ctx_timing_enable(self._c, C.c_int(1 if on else 0)))
+        self._check(self._l.letkf_ctx_timing_enable(self._c, 1 if on else 0))
 
     def last_path(self):
         buf = C.create_string_buffer(256)
-        self._check(self._l.letkf_ctx_last_path(self._c, buf, C.c_int32(256)))
+        self._check(self._l.letkf_ctx_last_path(self._c, buf, 256))
         return buf.value.decode()
 
     def timing_read(self, reset=True):
         avg = C.c_double(0.0)
         n = C.c_int64(0)
-        self._check(self._l.letkf_ctx_timing_read(self._c, C.byref(avg), C.byref(n), C.c_int(1 if reset else 0)))
+        self._check(self._l.letkf_ctx_timing_read(self._c, C.byref(avg), C.byref(n), 1 if reset else 0))
         return avg.value, n.value
 
     # ---- (1b) batched letkf_core on device tensors
@@ -430,29 +466,34 @@ class Context:
         self._check(self._l.letkf_core_batch_dev(self._c, C.byref(a)))
 
     # ---- (2) das_letkf point update on device tensors
+    def _das_args(self, k, nv, npts, ensval, kld, dep, infl, gues, anal, sp, sm, sv, beta, det_run, infl_adaptive,
+                  relax_to_inflated_prior, relax_alpha, relax_alpha_spread, q_update_top, q_sprd_max, iv_p, iv_q_first,
+                  iv_q_last, status, nsweep, rtps_infl_out, warm_run, var_mask, infl_sv):
+        """the letkf_das_args both loop-body entries share; the lists, the k x k outputs and warm_stride stay NULL / 0"""
+        a = DasArgs()
+        a.k, a.nv, a.det_run, a.infl_adaptive = k, nv, int(bool(det_run)), int(bool(infl_adaptive))
+        a.relax_to_inflated_prior = int(bool(relax_to_inflated_prior))
+        a.iv_p, a.iv_q_first, a.iv_q_last = iv_p, iv_q_first, iv_q_last
+        a.relax_alpha, a.relax_alpha_spread = relax_alpha, relax_alpha_spread
+        a.q_update_top, a.q_sprd_max, a.npts = q_update_top, q_sprd_max, npts
+        a.ensval, a.kld, a.dep, a.beta, a.infl = _ptr(ensval), kld, _ptr(dep), _ptr(beta), _ptr(infl)
+        a.gues, a.anal, a.sp, a.sm, a.sv = _ptr(gues), _ptr(anal), sp, sm, sv
+        a.status, a.nsweep, a.rtps_infl_out = _ptr(status), _ptr(nsweep), _ptr(rtps_infl_out)
+        a.warm_run, a.var_mask, a.infl_sv = int(warm_run), int(var_mask), int(infl_sv)
+        return a
+
     def das_points(self, k, nv, obs_off, obs_idx, rdiag_l, rloc_l, ensval, kld, dep, infl, gues, anal, sp, sm, sv,
                    beta=None, det_run=False, infl_adaptive=False, relax_to_inflated_prior=False, relax_alpha=0.0,
                    relax_alpha_spread=0.0, q_update_top=0.0, q_sprd_max=0.0, iv_p=4, iv_q_first=5, iv_q_last=10,
                    trans_out=None, transm_out=None, pa_out=None, status=None, nsweep=None, rtps_infl_out=None,
                    warm_run=0, var_mask=0, fused=None, nobs_out=None, warm_stride=0, infl_sv=0):
         """fused = (tables, ri, rj, rlev, rz): obs_local fused into the kernel (obs_off .. rloc_l may be None)"""
-        a = DasArgs()
-        a.k, a.nv, a.det_run, a.infl_adaptive = k, nv, int(bool(det_run)), int(bool(infl_adaptive))
-        a.relax_to_inflated_prior = int(bool(relax_to_inflated_prior))
-        a.iv_p, a.iv_q_first, a.iv_q_last = iv_p, iv_q_first, iv_q_last
-        a.relax_alpha, a.relax_alpha_spread = relax_alpha, relax_alpha_spread
-        a.q_update_top, a.q_sprd_max = q_update_top, q_sprd_max
-        a.npts = (obs_off.numel() - 1) if fused is None else fused[1].numel()
+        a = self._das_args(k, nv, (obs_off.numel() - 1) if fused is None else fused[1].numel(), ensval, kld, dep, infl, gues,
+                           anal, sp, sm, sv, beta, det_run, infl_adaptive, relax_to_inflated_prior, relax_alpha,
+                           relax_alpha_spread, q_update_top, q_sprd_max, iv_p, iv_q_first, iv_q_last, status, nsweep,
+                           rtps_infl_out, warm_run, var_mask, infl_sv)
         a.obs_off, a.obs_idx, a.rdiag_l, a.rloc_l = _ptr(obs_off), _ptr(obs_idx), _ptr(rdiag_l), _ptr(rloc_l)
-        a.ensval, a.kld, a.dep, a.beta, a.infl = _ptr(ensval), kld, _ptr(dep), _ptr(beta), _ptr(infl)
-        a.gues, a.anal, a.sp, a.sm, a.sv = _ptr(gues), _ptr(anal), sp, sm, sv
-        a.trans_out, a.transm_out, a.pa_out = _ptr(trans_out), _ptr(transm_out), _ptr(pa_out)
-        a.status, a.nsweep = _ptr(status), _ptr(nsweep)
-        a.rtps_infl_out = _ptr(rtps_infl_out)
-        a.warm_run = int(warm_run)
-        a.warm_stride = int(warm_stride)
-        a.var_mask = int(var_mask)
-        a.infl_sv = int(infl_sv)
+        a.trans_out, a.transm_out, a.pa_out, a.warm_stride = _ptr(trans_out), _ptr(transm_out), _ptr(pa_out), int(warm_stride)
         if fused is None:
             self._check(self._l.letkf_das_points_dev(self._c, C.byref(a)))
         else:
@@ -467,59 +508,43 @@ class Context:
         """letkf_das_columns_dev: obs_local + loop body for the points p = ij + nij1*lev -- list-free where the one-wave kernel
         serves the call (horizontal survivors per column, batches of columns that fit list_bytes), else by slabs of levels whose
         lists fit list_bytes of library workspace."""
-        a = DasArgs()
-        a.k, a.nv, a.det_run, a.infl_adaptive = k, nv, int(bool(det_run)), int(bool(infl_adaptive))
-        a.relax_to_inflated_prior = int(bool(relax_to_inflated_prior))
-        a.iv_p, a.iv_q_first, a.iv_q_last = iv_p, iv_q_first, iv_q_last
-        a.relax_alpha, a.relax_alpha_spread = relax_alpha, relax_alpha_spread
-        a.q_update_top, a.q_sprd_max = q_update_top, q_sprd_max
-        a.npts = nij1 * nlev
-        a.ensval, a.kld, a.dep, a.beta, a.infl = _ptr(ensval), kld, _ptr(dep), _ptr(beta), _ptr(infl)
-        a.gues, a.anal, a.sp, a.sm, a.sv = _ptr(gues), _ptr(anal), sp, sm, sv
-        a.status, a.nsweep, a.rtps_infl_out = _ptr(status), _ptr(nsweep), _ptr(rtps_infl_out)
-        a.warm_run, a.var_mask, a.infl_sv = int(warm_run), int(var_mask), int(infl_sv)
-        self._check(self._l.letkf_das_columns_dev(self._c, C.byref(a), C.byref(tables), C.c_int64(nij1), C.c_int32(nlev),
-                                                  _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), C.c_int64(list_bytes),
-                                                  _ptr(nobs_out)))
+        a = self._das_args(k, nv, nij1 * nlev, ensval, kld, dep, infl, gues, anal, sp, sm, sv, beta, det_run, infl_adaptive,
+                           relax_to_inflated_prior, relax_alpha, relax_alpha_spread, q_update_top, q_sprd_max, iv_p, iv_q_first,
+                           iv_q_last, status, nsweep, rtps_infl_out, warm_run, var_mask, infl_sv)
+        self._check(self._l.letkf_das_columns_dev(self._c, C.byref(a), C.byref(tables), nij1, nlev, _ptr(rig), _ptr(rjg),
+                                                  _ptr(rlev), _ptr(rz), list_bytes, _ptr(nobs_out)))
 
     # ---- (3) obs_local on the device: two-phase CSR build (count, scan, fill)
-    def obs_search(self, tables, ri, rj, rlev, rz):
-        """Returns (obs_off, obs_idx, rdiag_l, rloc_l) device tensors for the points (ri, rj, rlev, rz)."""
+    def _csr_lists(self, npts, device, search):
+        """Count pass, counts -> offsets, the three list tensors, fill pass.  search(fill, counts, obs_off, obs_idx, rdiag_l,
+        rloc_l) makes one call of a search entry; returns (obs_off, obs_idx, rdiag_l, rloc_l)."""
         import torch
-        npts = ri.numel()
-        counts = torch.zeros(npts, dtype=torch.int32, device=ri.device)
-        self._check(self._l.letkf_obs_search_dev(self._c, C.byref(tables), C.c_int64(npts), _ptr(ri), _ptr(rj),
-                                                 _ptr(rlev), _ptr(rz), C.c_int32(0), _ptr(counts), None, None, None,
-                                                 None))
-        obs_off = torch.zeros(npts + 1, dtype=torch.int64, device=ri.device)
+        counts = torch.zeros(npts, dtype=torch.int32, device=device)
+        search(0, counts, None, None, None, None)
+        obs_off = torch.zeros(npts + 1, dtype=torch.int64, device=device)
         obs_off[1:] = torch.cumsum(counts.to(torch.int64), 0)
         nnz = int(obs_off[-1].item())
-        obs_idx = torch.empty(max(nnz, 1), dtype=torch.int32, device=ri.device)
-        rdiag = torch.empty(max(nnz, 1), dtype=torch.float64, device=ri.device)
-        rloc = torch.empty(max(nnz, 1), dtype=torch.float64, device=ri.device)
-        self._check(self._l.letkf_obs_search_dev(self._c, C.byref(tables), C.c_int64(npts), _ptr(ri), _ptr(rj),
-                                                 _ptr(rlev), _ptr(rz), C.c_int32(1), None, _ptr(obs_off),
-                                                 _ptr(obs_idx), _ptr(rdiag), _ptr(rloc)))
+        obs_idx, rdiag, rloc = (torch.empty(max(nnz, 1), dtype=t, device=device)
+                                for t in (torch.int32, torch.float64, torch.float64))
+        search(1, None, obs_off, obs_idx, rdiag, rloc)
         return obs_off, obs_idx[:nnz], rdiag[:nnz], rloc[:nnz]
+
+    def obs_search(self, tables, ri, rj, rlev, rz):
+        """Returns (obs_off, obs_idx, rdiag_l, rloc_l) device tensors for the points (ri, rj, rlev, rz)."""
+        def search(fill, counts, obs_off, obs_idx, rdiag, rloc):
+            self._check(self._l.letkf_obs_search_dev(self._c, C.byref(tables), ri.numel(), _ptr(ri), _ptr(rj), _ptr(rlev),
+                                                     _ptr(rz), fill, _ptr(counts), _ptr(obs_off), _ptr(obs_idx), _ptr(rdiag),
+                                                     _ptr(rloc)))
+        return self._csr_lists(ri.numel(), ri.device, search)
 
     def obs_search_columns(self, tables, nij1, nlev, rig, rjg, rlev, rz, nobs_ctype=None, cutd_ctype=None):
         """Column-cooperative obs_local for points p = ij + nij1*lev; same return as obs_search."""
-        import torch
-        npts = nij1 * nlev
-        counts = torch.zeros(npts, dtype=torch.int32, device=rig.device)
-        f = self._l.letkf_obs_search_columns_dev
-        self._check(f(self._c, C.byref(tables), C.c_int64(nij1), C.c_int32(nlev), _ptr(rig), _ptr(rjg), _ptr(rlev),
-                      _ptr(rz), C.c_int32(0), _ptr(counts), None, None, None, None, None, None))
-        obs_off = torch.zeros(npts + 1, dtype=torch.int64, device=rig.device)
-        obs_off[1:] = torch.cumsum(counts.to(torch.int64), 0)
-        nnz = int(obs_off[-1].item())
-        obs_idx = torch.empty(max(nnz, 1), dtype=torch.int32, device=rig.device)
-        rdiag = torch.empty(max(nnz, 1), dtype=torch.float64, device=rig.device)
-        rloc = torch.empty(max(nnz, 1), dtype=torch.float64, device=rig.device)
-        self._check(f(self._c, C.byref(tables), C.c_int64(nij1), C.c_int32(nlev), _ptr(rig), _ptr(rjg), _ptr(rlev),
-                      _ptr(rz), C.c_int32(1), None, _ptr(obs_off), _ptr(obs_idx), _ptr(rdiag), _ptr(rloc), _ptr(nobs_ctype),
-                      _ptr(cutd_ctype)))    # (diagnostics with the fill pass: the count pass then needs no selection)
-        return obs_off, obs_idx[:nnz], rdiag[:nnz], rloc[:nnz]
+        def search(fill, counts, obs_off, obs_idx, rdiag, rloc):
+            nobs_c, cutd_c = (nobs_ctype, cutd_ctype) if fill else (None, None)   # (diagnostics with the fill pass: the count
+            self._check(self._l.letkf_obs_search_columns_dev(                       # pass then needs no selection)
+                self._c, C.byref(tables), nij1, nlev, _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), fill, _ptr(counts),
+                _ptr(obs_off), _ptr(obs_idx), _ptr(rdiag), _ptr(rloc), _ptr(nobs_c), _ptr(cutd_c)))
+        return self._csr_lists(nij1 * nlev, rig.device, search)
 
     # ---- (10) EFSO: das_efso's loop on device tensors
     def _efso_args(self, k, nv, term_of_var, nterm, npts, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp, fsv, djdy,
@@ -549,13 +574,12 @@ class Context:
         """letkf_efso_columns_dev: the column search and EFSO for the points p = ij + nij1*lev, by slabs of levels."""
         a, keep = self._efso_args(k, nv, term_of_var, nterm, nij1 * nlev, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp, fsv,
                                   djdy, var_mask)
-        self._check(self._l.letkf_efso_columns_dev(self._c, C.byref(a), C.byref(tables), C.c_int64(nij1), C.c_int32(nlev),
-                                                   _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), C.c_int64(list_bytes)))
+        self._check(self._l.letkf_efso_columns_dev(self._c, C.byref(a), C.byref(tables), nij1, nlev, _ptr(rig), _ptr(rjg),
+                                                   _ptr(rlev), _ptr(rz), list_bytes))
 
     def efso_obsense(self, nterm, djdy, dep, obsense):
         """letkf_efso_obsense_dev: obsense[j*nterm + t] = djdy[j*nterm + t] * dep[j]."""
-        self._check(self._l.letkf_efso_obsense_dev(self._c, C.c_int32(nterm), C.c_int64(dep.numel()), _ptr(djdy), _ptr(dep),
-                                                   _ptr(obsense)))
+        self._check(self._l.letkf_efso_obsense_dev(self._c, nterm, dep.numel(), _ptr(djdy), _ptr(dep), _ptr(obsense)))
 
     # ---- (12) EFSO with localisation advection
     def efso_locadv(self, rig, rjg, nlev, u0, v0, u1, v1, locadv_rate, eft, dx, dy, ri=None, rj=None):
@@ -568,8 +592,7 @@ class Context:
         if rj is None:
             rj = torch.empty(nij1 * nlev, dtype=torch.float64, device=rig.device)
         self._check(self._l.letkf_efso_locadv_dev(self._c, nij1, nlev, _ptr(rig), _ptr(rjg), _ptr(u0), _ptr(v0), _ptr(u1),
-                                                  _ptr(v1), float(locadv_rate), float(eft), float(dx), float(dy), _ptr(ri),
-                                                  _ptr(rj)))
+                                                  _ptr(v1), locadv_rate, eft, dx, dy, _ptr(ri), _ptr(rj)))
         return ri, rj
 
     def efso_search(self, k, nv, term_of_var, nterm, tables, ri, rj, rlev, rz, ensval, kld, nobs, fcst, sp, sm, sv, fcer, fsp,
@@ -606,8 +629,8 @@ class Context:
                     torch.empty((nterm,) + shape, dtype=torch.int32, device=d))
         count, ssum, nneg = outs
         self._check(self._l.letkf_efso_summary_dev(self._c, nterm, n, _ptr(obsense), _ptr(elm), _ptr(typ), _ptr(lat), _ptr(qc),
-                                                   nid, ids.ctypes.data_as(C.c_void_p) if nid else None, nobtype,
-                                                   float(latbound), _ptr(count), _ptr(ssum), _ptr(nneg)))
+                                                   nid, _hptr(ids) if nid else None, nobtype, latbound, _ptr(count), _ptr(ssum),
+                                                   _ptr(nneg)))
         return count, ssum, nneg
 
     # ---- (11) das_letkf_obs: the analysis ensemble in observation space
@@ -632,9 +655,8 @@ class Context:
 
     # ---- (5) set_letkf_obs on the device
     def obs_departure(self, params, elm, dat, err, ensval, kld, val, qc):
-        self._check(self._l.letkf_obs_departure_dev(self._c, C.byref(params), C.c_int64(elm.numel()), _ptr(elm),
-                                                    _ptr(dat), _ptr(err), _ptr(ensval), C.c_int64(kld), _ptr(val),
-                                                    _ptr(qc)))
+        self._check(self._l.letkf_obs_departure_dev(self._c, C.byref(params), elm.numel(), _ptr(elm), _ptr(dat), _ptr(err),
+                                                    _ptr(ensval), kld, _ptr(val), _ptr(qc)))
 
     def obs_mesh_sort(self, mesh, ncell, ctype, ri, rj, qc):
         """Returns (n_cell [ncell] int32, key [nsorted] int32) device tensors."""
@@ -643,8 +665,8 @@ class Context:
         n_cell = torch.zeros(max(ncell, 1), dtype=torch.int32, device=ctype.device)
         key = torch.empty(max(nobs, 1), dtype=torch.int32, device=ctype.device)
         ns = C.c_int64(0)
-        self._check(self._l.letkf_obs_mesh_sort_dev(self._c, C.byref(mesh), C.c_int64(nobs), _ptr(ctype), _ptr(ri),
-                                                    _ptr(rj), _ptr(qc), _ptr(n_cell), _ptr(key), C.byref(ns)))
+        self._check(self._l.letkf_obs_mesh_sort_dev(self._c, C.byref(mesh), nobs, _ptr(ctype), _ptr(ri), _ptr(rj), _ptr(qc),
+                                                    _ptr(n_cell), _ptr(key), C.byref(ns)))
         return n_cell[:ncell], key[:ns.value]
 
     def obs_halo_plan(self, layout, n_all, nacx, cap):
@@ -653,39 +675,34 @@ class Context:
         ac_ext = torch.zeros(max(nacx, 1), dtype=torch.int32, device=n_all.device)
         src_row = torch.empty(max(cap, 1), dtype=torch.int32, device=n_all.device)
         nt = C.c_int64(0)
-        self._check(self._l.letkf_obs_halo_plan_dev(self._c, C.byref(layout), _ptr(n_all), _ptr(ac_ext),
-                                                    _ptr(src_row), C.c_int64(cap), C.byref(nt)))
+        self._check(self._l.letkf_obs_halo_plan_dev(self._c, C.byref(layout), _ptr(n_all), _ptr(ac_ext), _ptr(src_row), cap,
+                                                    C.byref(nt)))
         return ac_ext[:nacx], src_row[:nt.value]
 
     def obs_gather_rows(self, src_row, ncols, src, ld_src, dst, ld_dst):
-        self._check(self._l.letkf_obs_gather_rows_dev(self._c, C.c_int64(src_row.numel()), _ptr(src_row),
-                                                      C.c_int32(ncols), _ptr(src), C.c_int64(ld_src), _ptr(dst),
-                                                      C.c_int64(ld_dst)))
+        self._check(self._l.letkf_obs_gather_rows_dev(self._c, src_row.numel(), _ptr(src_row), ncols, _ptr(src), ld_src,
+                                                      _ptr(dst), ld_dst))
 
     def obs_gather_i32(self, src_row, src, dst):
-        self._check(self._l.letkf_obs_gather_i32_dev(self._c, C.c_int64(src_row.numel()), _ptr(src_row), _ptr(src),
-                                                     _ptr(dst)))
+        self._check(self._l.letkf_obs_gather_i32_dev(self._c, src_row.numel(), _ptr(src_row), _ptr(src), _ptr(dst)))
 
     # ---- (9) set_letkf_obs behind one call
-    def _setobs_args(self, params, qcp, files, set_, idx, qc, ensval, kld):
-        return (self._c, C.byref(params), C.byref(qcp), C.byref(files), C.c_int64(set_.numel()), _ptr(set_), _ptr(idx), _ptr(qc),
-                _ptr(ensval), C.c_int64(kld))
+    def _set_obs(self, entry, params, qcp, files, set_, idx, qc, ensval, kld, keep):
+        h = C.c_void_p()
+        self._check(entry(self._c, C.byref(params), C.byref(qcp), C.byref(files), set_.numel(), _ptr(set_), _ptr(idx), _ptr(qc),
+                          _ptr(ensval), kld, C.byref(h)))
+        return ObsTable(self, h, keep)
 
     def set_obs(self, params, qcp, files, set_, idx, qc, ensval, kld, keep=()):
         """letkf_set_obs_dev (one rank).  `keep`: objects the table's file rows / params depend on."""
-        h = C.c_void_p()
-        self._check(self._l.letkf_set_obs_dev(*self._setobs_args(params, qcp, files, set_, idx, qc, ensval, kld), C.byref(h)))
-        return ObsTable(self, h, keep)
+        return self._set_obs(self._l.letkf_set_obs_dev, params, qcp, files, set_, idx, qc, ensval, kld, keep)
 
     def set_obs_local(self, params, qcp, files, set_, idx, qc, ensval, kld, keep=()):
-        h = C.c_void_p()
-        self._check(self._l.letkf_set_obs_local_dev(*self._setobs_args(params, qcp, files, set_, idx, qc, ensval, kld), C.byref(h)))
-        return ObsTable(self, h, keep)
+        return self._set_obs(self._l.letkf_set_obs_local_dev, params, qcp, files, set_, idx, qc, ensval, kld, keep)
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
-        nrecv = recv.shape[0] if recv is not None else 0
-        self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g), C.c_int64(nrecv),
-                                                     _ptr(recv)))
+        self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),
+                                                     recv.shape[0] if recv is not None else 0, _ptr(recv)))
 
     # ---- (6) after the loop
     def monit_dep(self, elem_uid, elm, dep, qc):
@@ -697,86 +714,72 @@ class Context:
         nobs = torch.zeros(nid, dtype=torch.int32, device=dep.device)
         bias = torch.zeros(nid, dtype=torch.float64, device=dep.device)
         rmse = torch.zeros(nid, dtype=torch.float64, device=dep.device)
-        self._check(self._l.letkf_monit_dep_dev(self._c, C.c_int32(nid), ids.ctypes.data_as(C.c_void_p),
-                                                C.c_int64(dep.numel()), _ptr(elm), _ptr(dep), _ptr(qc), _ptr(nobs),
-                                                _ptr(bias), _ptr(rmse)))
+        self._check(self._l.letkf_monit_dep_dev(self._c, nid, _hptr(ids), dep.numel(), _ptr(elm), _ptr(dep), _ptr(qc),
+                                                _ptr(nobs), _ptr(bias), _ptr(rmse)))
         return nobs, bias, rmse
 
     def additive_inflation(self, k, nv, npts, nij1, anal, add, sp, sm, sv, infl_add, weight=None, qmean=None, q_sp=0,
                            q_sv=0, iv_q_first=5, iv_q_last=10, ishuf=None):
-        self._check(self._l.letkf_additive_inflation_dev(
-            self._c, C.c_int32(k), C.c_int32(nv), C.c_int64(npts), C.c_int64(nij1), _ptr(anal), _ptr(add),
-            C.c_int64(sp), C.c_int64(sm), C.c_int64(sv), C.c_double(infl_add), _ptr(weight), _ptr(qmean),
-            C.c_int64(q_sp), C.c_int64(q_sv), C.c_int32(iv_q_first), C.c_int32(iv_q_last), _ptr(ishuf)))
+        self._check(self._l.letkf_additive_inflation_dev(self._c, k, nv, npts, nij1, _ptr(anal), _ptr(add), sp, sm, sv, infl_add,
+                                                         _ptr(weight), _ptr(qmean), q_sp, q_sv, iv_q_first, iv_q_last,
+                                                         _ptr(ishuf)))
 
     def addinfl_weight(self, rig, rjg, ob_ri, ob_rj, dx, dy, hori_loc):
         import torch
         w = torch.zeros(rig.numel(), dtype=torch.float64, device=rig.device)
-        self._check(self._l.letkf_addinfl_weight_dev(self._c, C.c_int64(rig.numel()), _ptr(rig), _ptr(rjg),
-                                                     C.c_int64(ob_ri.numel()), _ptr(ob_ri), _ptr(ob_rj),
-                                                     C.c_double(dx), C.c_double(dy), C.c_double(hori_loc), _ptr(w)))
+        self._check(self._l.letkf_addinfl_weight_dev(self._c, rig.numel(), _ptr(rig), _ptr(rjg), ob_ri.numel(), _ptr(ob_ri),
+                                                     _ptr(ob_rj), dx, dy, hori_loc, _ptr(w)))
         return w
 
     # ---- (8) the exchange, on an RCCL communicator the caller owns (an integer / c_void_p ncclComm_t)
     def obs_allgatherv(self, nccl_comm, myrank, counts, send, recv):
         """counts: python ints per rank (rows); send / recv: device tensors whose rows are contiguous."""
-        n = len(counts)
-        cnt = (C.c_int64 * n)(*[int(x) for x in counts])
+        import numpy as np
+        cnt = np.array([int(x) for x in counts], dtype=np.int64)
         row_bytes = send.element_size() * (send[0].numel() if send.dim() > 1 and send.shape[0] > 0 else
                                            (recv[0].numel() if recv.dim() > 1 else 1))
-        self._check(self._l.letkf_obs_allgatherv_dev(self._c, C.c_void_p(nccl_comm), C.c_int32(n), C.c_int32(myrank),
-                                                     cnt, C.c_int64(row_bytes), _ptr(send), _ptr(recv)))
+        self._check(self._l.letkf_obs_allgatherv_dev(self._c, C.c_void_p(nccl_comm), len(cnt), myrank, _hptr(cnt), row_bytes,
+                                                     _ptr(send), _ptr(recv)))
 
     # ---- (7) das_letkf set-up
     def alltoallv(self, nccl_comm, myrank, send_counts, send_offs, recv_counts, recv_offs, row_bytes, send, recv):
         """letkf_alltoallv_dev: counts / offsets are host lists in rows of row_bytes bytes"""
-        n = len(send_counts)
-        arr = lambda v: (C.c_int64 * n)(*[int(a) for a in v])
-        self._check(self._l.letkf_alltoallv_dev(self._c, C.c_void_p(nccl_comm), C.c_int32(n), C.c_int32(myrank), arr(send_counts),
-                                                arr(send_offs), arr(recv_counts), arr(recv_offs), C.c_int64(row_bytes), _ptr(send),
-                                                _ptr(recv)))
+        import numpy as np
+        arr = lambda v: _hptr(np.array([int(a) for a in v], dtype=np.int64))
+        self._check(self._l.letkf_alltoallv_dev(self._c, C.c_void_p(nccl_comm), len(send_counts), myrank, arr(send_counts),
+                                                arr(send_offs), arr(recv_counts), arr(recv_offs), row_bytes, _ptr(send), _ptr(recv)))
 
     def allreduce_sum_i32(self, nccl_comm, nranks, buf):
-        self._check(self._l.letkf_allreduce_sum_i32_dev(self._c, C.c_void_p(nccl_comm), C.c_int32(nranks), C.c_int64(buf.numel()),
-                                                        _ptr(buf)))
+        self._check(self._l.letkf_allreduce_sum_i32_dev(self._c, C.c_void_p(nccl_comm), nranks, buf.numel(), _ptr(buf)))
 
     def members_alltoall(self, nccl_comm, nranks, myrank, direction, nlev, nlon, nlat, nv3d, mstart, mcount, v3dg, x, sp, sm, sv):
-        self._check(self._l.letkf_members_alltoall_dev(self._c, C.c_void_p(nccl_comm), C.c_int32(nranks), C.c_int32(myrank),
-                                                       C.c_int32(direction), C.c_int32(nlev), C.c_int32(nlon), C.c_int32(nlat),
-                                                       C.c_int32(nv3d), C.c_int32(mstart), C.c_int32(mcount), _ptr(v3dg), _ptr(x),
-                                                       C.c_int64(sp), C.c_int64(sm), C.c_int64(sv)))
+        self._check(self._l.letkf_members_alltoall_dev(self._c, C.c_void_p(nccl_comm), nranks, myrank, direction, nlev, nlon,
+                                                       nlat, nv3d, mstart, mcount, _ptr(v3dg), _ptr(x), sp, sm, sv))
 
     def relax_beta(self, params, nij1, nlev, rig, rjg, hgt, beta):
-        self._check(self._l.letkf_relax_beta_dev(self._c, C.byref(params), C.c_int64(nij1), C.c_int32(nlev), _ptr(rig),
-                                                 _ptr(rjg), _ptr(hgt), _ptr(beta)))
+        self._check(self._l.letkf_relax_beta_dev(self._c, C.byref(params), nij1, nlev, _ptr(rig), _ptr(rjg), _ptr(hgt),
+                                                 _ptr(beta)))
 
     def infl_init(self, work3d, infl_mul, infl_mul_min):
-        self._check(self._l.letkf_infl_init_dev(self._c, C.c_int64(work3d.numel()), _ptr(work3d),
-                                                C.c_double(infl_mul), C.c_double(infl_mul_min)))
+        self._check(self._l.letkf_infl_init_dev(self._c, work3d.numel(), _ptr(work3d), infl_mul, infl_mul_min))
 
     # ---- (4) the steps either side of the loop
     def state_trans(self, consts, nlev, nlon, nlat, nv3d, v3dg, inverse=False):
-        self._check(self._l.letkf_state_trans_dev(self._c, C.byref(consts), C.c_int32(nlev), C.c_int32(nlon),
-                                                  C.c_int32(nlat), C.c_int32(nv3d), _ptr(v3dg),
-                                                  C.c_int32(1 if inverse else 0)))
+        self._check(self._l.letkf_state_trans_dev(self._c, C.byref(consts), nlev, nlon, nlat, nv3d, _ptr(v3dg),
+                                                  1 if inverse else 0))
 
     def member_points(self, direction, nlev, nlon, nlat, nv3d, np_, rank, m, v3dg, x, nij1, sp, sm, sv):
-        self._check(self._l.letkf_member_points_dev(self._c, C.c_int32(direction), C.c_int32(nlev), C.c_int32(nlon),
-                                                    C.c_int32(nlat), C.c_int32(nv3d), C.c_int32(np_), C.c_int32(rank),
-                                                    C.c_int32(m), _ptr(v3dg), _ptr(x), C.c_int64(nij1), C.c_int64(sp),
-                                                    C.c_int64(sm), C.c_int64(sv)))
+        self._check(self._l.letkf_member_points_dev(self._c, direction, nlev, nlon, nlat, nv3d, np_, rank, m, _ptr(v3dg),
+                                                    _ptr(x), nij1, sp, sm, sv))
 
     def ens_spread(self, k, nv, npts, x, sp, sm, sv, sprd):
-        self._check(self._l.letkf_ens_spread_dev(self._c, C.c_int32(k), C.c_int32(nv), C.c_int64(npts), _ptr(x),
-                                                 C.c_int64(sp), C.c_int64(sm), C.c_int64(sv), _ptr(sprd)))
+        self._check(self._l.letkf_ens_spread_dev(self._c, k, nv, npts, _ptr(x), sp, sm, sv, _ptr(sprd)))
 
     def to_perturbations(self, k, nv, npts, x, sp, sm, sv):
-        self._check(self._l.letkf_ens_to_perturbations_dev(self._c, C.c_int32(k), C.c_int32(nv), C.c_int64(npts),
-                                                           _ptr(x), C.c_int64(sp), C.c_int64(sm), C.c_int64(sv)))
+        self._check(self._l.letkf_ens_to_perturbations_dev(self._c, k, nv, npts, _ptr(x), sp, sm, sv))
 
     def ens_mean(self, k, nv, npts, x, sp, sm, sv):
-        self._check(self._l.letkf_ens_mean_dev(self._c, C.c_int32(k), C.c_int32(nv), C.c_int64(npts), _ptr(x),
-                                               C.c_int64(sp), C.c_int64(sm), C.c_int64(sv)))
+        self._check(self._l.letkf_ens_mean_dev(self._c, k, nv, npts, _ptr(x), sp, sm, sv))
 
 
 def letkf_core_host(ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_transm=True, want_pao=True,
@@ -785,9 +788,7 @@ def letkf_core_host(ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_tra
     """The host-pointer drop-in letkf_core_c (what the Fortran shim calls), on numpy arrays.  The outputs start as
     `fill`; transmd is returned only with depd unless transmd_without_depd."""
     import numpy as np
-    l = lib()
-    dp = C.POINTER(C.c_double)
-    f = lambda a: None if a is None else a.ctypes.data_as(dp)
+    f = _hptr
     hdxb = np.asfortranarray(hdxb, dtype=np.float64)
     trans = np.full((ne, ne), fill, order="F")
     transm = np.full(ne, fill) if want_transm else None
@@ -797,9 +798,9 @@ def letkf_core_host(ne, nobs, nobsl, hdxb, rdiag, rloc, dep, parm_infl, want_tra
     wl = C.c_int(1 if rdiag_wloc else 0)
     iu = C.c_int(1 if infl_update else 0)
     st = C.c_int(-99)
-    l.letkf_core_c(C.c_int(ne), C.c_int(nobs), C.c_int(nobsl), f(hdxb), f(rdiag), f(rloc), f(dep), C.byref(infl),
-                   f(trans), f(transm), f(pao), C.byref(wl) if rdiag_wloc is not None else None,
-                   C.byref(iu) if infl_update is not None else None, f(depd), f(transmd), C.byref(st))
+    lib().letkf_core_c(ne, nobs, nobsl, f(hdxb), f(rdiag), f(rloc), f(dep), C.byref(infl), f(trans), f(transm), f(pao),
+                       C.byref(wl) if rdiag_wloc is not None else None, C.byref(iu) if infl_update is not None else None,
+                       f(depd), f(transmd), C.byref(st))
     return dict(trans=trans, transm=transm, pao=pao,
                 transmd=transmd if (depd is not None or transmd_without_depd) else None,
                 parm_infl=infl.value, status=st.value)
@@ -814,8 +815,7 @@ def var_local_classes(var_local):
     n2nc = np.zeros(nvar, dtype=np.int32)
     n2n = np.zeros(nvar, dtype=np.int32)
     nc = C.c_int32(0)
-    rc = lib().letkf_var_local_classes(C.c_int32(nvar), C.c_int32(nlt), v.ctypes.data_as(C.c_void_p),
-                                       n2nc.ctypes.data_as(C.c_void_p), n2n.ctypes.data_as(C.c_void_p), C.byref(nc))
+    rc = lib().letkf_var_local_classes(nvar, nlt, _hptr(v), _hptr(n2nc), _hptr(n2n), C.byref(nc))
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_var_local_classes: {rc}")
     return n2nc, n2n, nc.value
@@ -831,9 +831,8 @@ def ctype_merge_groups(elm_u_ctype, typ_ctype, ctype_merge):
     gs = np.zeros(nct + 1, dtype=np.int32)
     gm = np.zeros(max(nct, 1), dtype=np.int32)
     ng = C.c_int32(0)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib().letkf_ctype_merge_groups(C.c_int32(nct), p(eu), p(ty), C.c_int32(cm.shape[0]), C.c_int32(cm.shape[1]),
-                                        p(cm), p(gs), p(gm), C.byref(ng))
+    p = _hptr
+    rc = lib().letkf_ctype_merge_groups(nct, p(eu), p(ty), cm.shape[0], cm.shape[1], p(cm), p(gs), p(gm), C.byref(ng))
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_ctype_merge_groups: {rc}")
     return gs[:ng.value + 1].copy(), gm[:nct].copy()
@@ -841,10 +840,10 @@ def ctype_merge_groups(elm_u_ctype, typ_ctype, ctype_merge):
 
 def obs_target_var(elm):
     """letkf_obs_target_var (host only): the 0-based grid variable das_letkf_obs regards an observation element as, -1 none."""
-    return int(lib().letkf_obs_target_var(C.c_int32(int(elm))))
+    return int(lib().letkf_obs_target_var(int(elm)))
 
 
 def radar_only(typ_ctype, typ_radar=22):
     import numpy as np
     ty = np.ascontiguousarray(typ_ctype, dtype=np.int32)
-    return int(lib().letkf_radar_only(C.c_int32(len(ty)), ty.ctypes.data_as(C.c_void_p), C.c_int32(typ_radar)))
+    return int(lib().letkf_radar_only(len(ty), _hptr(ty), typ_radar))

@@ -2,14 +2,13 @@
 ABI 11, the library exports them, the Python binding's ctypes signatures are the header's, and the numpy restatement
 tests/_efso_locadv.py has the properties of the reference's loc_advection."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import _efso_locadv as la
-from __graft_entry__ import ROOT, load_package
+from __graft_entry__ import load_package
+from _header import argtypes_of, declared_params, defines
 
 ENTRIES = ("letkf_efso_locadv_dev", "letkf_efso_search_dev")
 
@@ -21,28 +20,8 @@ def pkg():
     return p
 
 
-def header():
-    src = open(os.path.join(ROOT, "include", "letkf_amd.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def declared_params(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header())
-    assert m, f"{name} not declared"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
-def ctype_of(param):
-    """the ctypes type of one C parameter declaration (pointers of any kind as void *)"""
-    if "*" in param:
-        return C.c_void_p
-    base = param.replace("const ", "").split()[0]
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "double": C.c_double}[base]
-
-
 def test_header_declares_both_entries_at_abi_11():
-    src = open(os.path.join(ROOT, "include", "letkf_amd.h")).read()
-    assert int(re.search(r"#define LETKF_AMD_ABI_VERSION (\d+)", src).group(1)) == 11
+    assert defines()["LETKF_AMD_ABI_VERSION"] == 11
     for name in ENTRIES:
         declared_params(name)
     assert declared_params("letkf_efso_search_dev")[1] == "const letkf_efso_args *args"
@@ -59,7 +38,7 @@ def test_library_exports_both(pkg):
 def test_ctypes_signatures_match_the_header(pkg):
     lib = pkg.lib()
     for name in ENTRIES:
-        want = [ctype_of(p) for p in declared_params(name)]
+        want = argtypes_of(name)
         assert pkg.ARGTYPES[name] == want, name
         assert getattr(lib, name).argtypes == want
         assert getattr(lib, name).restype is C.c_int

@@ -2,16 +2,13 @@
 both entries and letkf_efso_norm_params, the library exports them, the Python binding's ctypes signatures and struct are
 the header's, and the numpy restatement tests/_efso_norm.py is the reference's lnorm / print_obsense loops."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import _efso_norm as en
-from __graft_entry__ import ROOT, load_package
+from __graft_entry__ import load_package
+from _header import argtypes_of, declared_params, defines, offsetof, sizeof, structs
 
 ENTRIES = ("letkf_efso_norm_dev", "letkf_efso_summary_dev")
 
@@ -23,31 +20,11 @@ def pkg():
     return p
 
 
-def header():
-    src = open(os.path.join(ROOT, "include", "letkf_amd.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def declared_params(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header())
-    assert m, f"{name} not declared"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
-def ctype_of(param):
-    if "*" in param:
-        return C.c_void_p
-    base = param.replace("const ", "").split()[0]
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "double": C.c_double}[base]
-
-
 def test_header_declares_both_entries_and_the_struct():
-    h = header()
-    assert re.search(r"typedef struct \{[^}]*\}\s*letkf_efso_norm_params;", h)
+    assert "letkf_efso_norm_params" in structs()
     assert declared_params("letkf_efso_norm_dev")[1] == "const letkf_efso_norm_params *prm"
     assert declared_params("letkf_efso_summary_dev")[0] == "letkf_ctx *ctx"
-    src = open(os.path.join(ROOT, "include", "letkf_amd.h")).read()
-    assert int(re.search(r"#define LETKF_AMD_ABI_VERSION (\d+)", src).group(1)) == 11
+    assert defines()["LETKF_AMD_ABI_VERSION"] == 11
 
 
 def test_library_exports_both(pkg):
@@ -61,7 +38,7 @@ def test_library_exports_both(pkg):
 def test_ctypes_signatures_match_the_header(pkg):
     lib = pkg.lib()
     for name in ENTRIES:
-        want = [ctype_of(p) for p in declared_params(name)]
+        want = argtypes_of(name)
         assert pkg.ARGTYPES[name] == want, name
         assert getattr(lib, name).argtypes == want
         assert getattr(lib, name).restype is C.c_int
@@ -69,16 +46,8 @@ def test_ctypes_signatures_match_the_header(pkg):
 
 def test_struct_matches_the_compiled_c_layout(pkg):
     fields = [f for f, _ in pkg.EfsoNormParams._fields_]
-    offs = "".join(f'printf("%zu\\n", offsetof(letkf_efso_norm_params, {f}));' for f in fields)
-    code = ('#include <stdio.h>\n#include <stddef.h>\n#include "letkf_amd.h"\nint main(){printf("%zu\\n", '
-            f'sizeof(letkf_efso_norm_params));{offs}return 0;}}\n')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(code)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        out = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert out[0] == C.sizeof(pkg.EfsoNormParams)
-    assert out[1:] == [getattr(pkg.EfsoNormParams, f).offset for f in fields]
+    assert sizeof("letkf_efso_norm_params") == C.sizeof(pkg.EfsoNormParams)
+    assert [offsetof("letkf_efso_norm_params", f) for f in fields] == [getattr(pkg.EfsoNormParams, f).offset for f in fields]
 
 
 def pressure_columns(rng, nij1, nlev, k):

@@ -17,6 +17,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import _header
 import _oracle
 from __graft_entry__ import PKG_DIR, load_package
 from _search import build_case, host_struct
@@ -29,29 +30,6 @@ HAVE_FC = os.path.exists("/opt/rocm/bin/amdflang")
 def build_fortran():
     load_package().build()
     subprocess.check_call(["make", "-C", FDIR], stdout=subprocess.DEVNULL)
-
-
-def c_structs(hdr):
-    """{name: [(kind, field), ...]} for every `typedef struct { ... } name;` of the header; kind in i32 / i64 / f64 / ptr"""
-    out = {}
-    for m in re.finditer(r"typedef struct \{(.*?)\}\s*(\w+);", hdr, flags=re.S):
-        body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-        fields = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            base = "i32" if "int32_t" in decl else "i64" if "int64_t" in decl else "f64" if "double" in decl else None   # (uint32_t: a 32-bit mask)
-            assert base, decl
-            decl = re.sub(r"\b(const|u?int32_t|int64_t|double)\b", "", decl)
-            for part in decl.split(","):
-                part = part.strip()
-                ptr = "*" in part
-                name = part.replace("*", "").strip()
-                name = re.sub(r"\[\d+\]", "", name)
-                fields.append(("ptr" if ptr else base, name))
-        out[m.group(2)] = fields
-    return out
 
 
 def f_types(src):
@@ -75,15 +53,15 @@ def f_types(src):
 
 @pytest.mark.skipif(not HAVE_FC, reason="amdflang not present")
 def test_every_bind_c_type_mirrors_its_c_struct():
-    hdr = open(os.path.join(PKG_DIR, "..", "include", "letkf_amd.h")).read()
     src = open(os.path.join(FDIR, "letkf_amd_api.f90")).read()
-    cs, fs = c_structs(hdr), f_types(src)
+    cs, fs = _header.c_structs(), f_types(src)
     # every struct of the C ABI has its Fortran mirror ...
     assert set(cs) == set(fs), (sorted(set(cs) - set(fs)), sorted(set(fs) - set(cs)))
     for name in cs:                 # ... field by field, in the C order, with the C kinds
         assert fs[name] == cs[name], (name, fs[name], cs[name])
     # and every device / host entry point of the header is bound by name
-    entries = set(re.findall(r"\n(?:int|void)\s+(letkf_\w+)\(", hdr)) - {"letkf_core_c", "letkf_sched_plan_check", "letkf_sched_plan_check_units"}
+    entries = {n for n, (ret, _) in _header.entries().items() if ret in ("int", "void")} - {
+        "letkf_core_c", "letkf_sched_plan_check", "letkf_sched_plan_check_units"}
     bound = set(re.findall(r"BIND\(C, name='(letkf_\w+)'\)", src))
     harness_only = {"letkf_ctx_timing_enable", "letkf_ctx_timing_read", "letkf_ctx_last_path"}
     assert entries - bound <= harness_only, sorted(entries - bound - harness_only)

@@ -80,21 +80,10 @@ DAS_DRIVER = os.path.join(FDIR, "build", "das_driver")
 @pytest.mark.skipif(not HAVE_FC, reason="amdflang not present")
 def test_fortran_api_module_mirrors_the_c_struct():
     """letkf_amd_api.f90: TYPE(letkf_das_args), BIND(C) must list the C struct's fields in the C order"""
-    import re
+    from _header import structs
     build_shim()
     assert os.path.exists(DAS_DRIVER)
-    hdr = open(os.path.join(PKG_DIR, "..", "include", "letkf_amd.h")).read()
-    body = hdr[:hdr.index("} letkf_das_args;")]
-    body = body[body.rindex("typedef struct {") + len("typedef struct {"):]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    c_fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl or decl.startswith("typedef"):
-            continue
-        names = decl.replace("*", " ").split(",")
-        c_fields.append(names[0].split()[-1])
-        c_fields += [n.strip() for n in names[1:]]
+    c_fields = [name for _, name, _ in structs()["letkf_das_args"]]
     src = open(os.path.join(FDIR, "letkf_amd_api.f90")).read()
     t = src[src.index("TYPE, BIND(C) :: letkf_das_args"):src.index("END TYPE letkf_das_args")]
     f_fields = []

@@ -2,16 +2,14 @@
 loop body on the pseudo-state; a lone observation gives the scalar Kalman filter; letkf_obs_target_var restates the
 reference's SELECT CASE; the ctypes mirror of letkf_das_obs_args has the header's size."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import _header
 import _obsanal
 from _search import build_case
-from __graft_entry__ import ROOT, load_package
+from __graft_entry__ import load_package
 
 
 @pytest.fixture(scope="module")
@@ -103,15 +101,6 @@ def test_obs_target_var_over_every_id(pkg):
 
 
 def test_das_obs_args_layout_matches_header(pkg):
-    code = ('#include <stdio.h>\n#include <stddef.h>\n#include "letkf_amd.h"\n'
-            'int main(){printf("%zu %zu %zu\\n", sizeof(letkf_das_obs_args), offsetof(letkf_das_obs_args, ntgt), '
-            'offsetof(letkf_das_obs_args, list_bytes));return 0;}\n')
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, "s.c")
-        open(src, "w").write(code)
-        exe = os.path.join(d, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        size, o_ntgt, o_lb = map(int, subprocess.check_output([exe]).split())
-    assert size == C.sizeof(pkg.DasObsArgs)
-    assert o_ntgt == pkg.DasObsArgs.ntgt.offset
-    assert o_lb == pkg.DasObsArgs.list_bytes.offset
+    assert _header.sizeof("letkf_das_obs_args") == C.sizeof(pkg.DasObsArgs)
+    assert _header.offsetof("letkf_das_obs_args", "ntgt") == pkg.DasObsArgs.ntgt.offset
+    assert _header.offsetof("letkf_das_obs_args", "list_bytes") == pkg.DasObsArgs.list_bytes.offset

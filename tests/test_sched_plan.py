@@ -4,8 +4,6 @@ problem size, run direction, run length and grid.  letkf_sched_plan_check builds
 every hand-out position of every XCD range through the very function the kernel runs (it is compiled for both sides);
 no device is needed.  The GPU tests check the other half: that the counters are drawn atomically, i.e. that no point of
 an analysis is left unwritten (tests/test_gpu_trivial.py, test_gpu_fullsize.py)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -16,10 +14,7 @@ from __graft_entry__ import load_package
 def check():
     p = load_package()
     p.build()
-    f = C.CDLL(p.LIB_PATH).letkf_sched_plan_check
-    f.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    f.restype = C.c_int
-    return f
+    return p.lib().letkf_sched_plan_check
 
 
 def test_baseline_shapes(check):
@@ -62,9 +57,7 @@ def test_units_of_three_runs():
     """csrc/letkf_trio.hip (k <= 20) walks three neighbouring runs in step: its plan hands out units that are whole multiples of
     three runs, every run exactly once, no quartered runs."""
     p = load_package()
-    f = C.CDLL(p.LIB_PATH).letkf_sched_plan_check_units
-    f.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    f.restype = C.c_int
+    f = p.lib().letkf_sched_plan_check_units
     shapes = [(240 * 240 * 60, 240 * 240, 60, 512, 4, 256), (40 * 40 * 30, 1600, 4, 512, 4, 256), (40 * 40 * 30, 1600, 30, 134, 4, 256),
               (48 * 48 * 12, 1, 6, 512, 4, 256), (150, 1, 1, 13, 4, 256), (1, 1, 1, 1, 4, 256), (0, 1, 1, 1, 4, 256), (100_000_000, 1, 16, 512, 4, 256)]
     for s in shapes:
