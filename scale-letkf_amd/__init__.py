@@ -27,6 +27,7 @@ def build(force=False):
     """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
     stale = force or not os.path.exists(LIB_PATH) or any(
@@ -367,6 +368,21 @@ ARGTYPES = {
 RESTYPES = {"letkf_amd_last_error": C.c_char_p, "letkf_core_c": None}     # every other entry returns int
 EXPORTS = list(ARGTYPES)
 
+
+class InterpArgs(C.Structure):
+    """letkf_interp_args (include/letkf_amd_interp.h)"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nlev", C.c_int32), ("stride_x", C.c_int32),
+                ("stride_y", C.c_int32), ("reserved0", C.c_int32), ("ws_bytes", C.c_int64), ("rig", C.c_void_p),
+                ("rjg", C.c_void_p), ("rlev", C.c_void_p), ("rz", C.c_void_p), ("nobs_coarse", C.c_void_p)]
+
+
+# ... and of the entries of the companion header include/letkf_amd_interp.h, a table of their own
+INTERP_VERSION = 1
+INTERP_ARGTYPES = {
+    "letkf_interp_coarse_axis": [_I32, _I32, _VP, _VP],
+    "letkf_das_interp_dev": [_VP, _VP, _VP, _VP],
+}
+
 _lib = None
 
 
@@ -382,10 +398,21 @@ def lib():
         except ImportError:
             pass
         _lib = C.CDLL(LIB_PATH)
-        for name, at in ARGTYPES.items():
+        for name, at in list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()):
             f = getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
             f.argtypes, f.restype = at, RESTYPES.get(name, _INT)
     return _lib
+
+
+def interp_coarse_axis(n, stride):
+    """letkf_interp_coarse_axis (host only): the coarse indices of an axis of n points, as an int32 numpy array."""
+    import numpy as np
+    idx = np.zeros(max(int(n), 1), dtype=np.int32)
+    cnt = C.c_int32(0)
+    rc = lib().letkf_interp_coarse_axis(n, stride, idx.ctypes.data_as(C.c_void_p), C.byref(cnt))
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_interp_coarse_axis: {rc}")
+    return idx[:cnt.value].copy()
 
 
 def _ptr(t):
@@ -513,6 +540,23 @@ class Context:
                            iv_q_last, status, nsweep, rtps_infl_out, warm_run, var_mask, infl_sv)
         self._check(self._l.letkf_das_columns_dev(self._c, C.byref(a), C.byref(tables), nij1, nlev, _ptr(rig), _ptr(rjg),
                                                   _ptr(rlev), _ptr(rz), list_bytes, _ptr(nobs_out)))
+
+    def das_interp(self, k, nv, tables, nx, ny, nlev, stride_x, stride_y, rig, rjg, rlev, rz, ensval, kld, dep, infl, gues,
+                   anal, sp, sm, sv, ws_bytes=0, nobs_coarse=None, npts=None, beta=None, det_run=False, infl_adaptive=False,
+                   relax_to_inflated_prior=False, relax_alpha=0.0, relax_alpha_spread=0.0, q_update_top=0.0, q_sprd_max=0.0,
+                   iv_p=4, iv_q_first=5, iv_q_last=10, status=None, nsweep=None, rtps_infl_out=None, var_mask=0, infl_sv=0,
+                   trans_out=None, transm_out=None, pa_out=None):
+        """letkf_das_interp_dev (include/letkf_amd_interp.h): letkf_core on every stride-th column of the nx x ny x nlev tile
+        (point p = i + nx*j + nx*ny*lev), T and w-bar interpolated bilinearly, the loop body's rules at every point.  npts,
+        infl_adaptive, nsweep and the k x k outputs only reach the entry's argument checks, which refuse them."""
+        a = self._das_args(k, nv, nx * ny * nlev if npts is None else npts, ensval, kld, dep, infl, gues, anal, sp, sm, sv,
+                           beta, det_run, infl_adaptive, relax_to_inflated_prior, relax_alpha, relax_alpha_spread, q_update_top,
+                           q_sprd_max, iv_p, iv_q_first, iv_q_last, status, nsweep, rtps_infl_out, 0, var_mask, infl_sv)
+        a.trans_out, a.transm_out, a.pa_out = _ptr(trans_out), _ptr(transm_out), _ptr(pa_out)
+        i = InterpArgs()
+        i.nx, i.ny, i.nlev, i.stride_x, i.stride_y, i.ws_bytes = nx, ny, nlev, stride_x, stride_y, int(ws_bytes)
+        i.rig, i.rjg, i.rlev, i.rz, i.nobs_coarse = _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), _ptr(nobs_coarse)
+        self._check(self._l.letkf_das_interp_dev(self._c, C.byref(a), C.byref(tables), C.byref(i)))
 
     # ---- (3) obs_local on the device: two-phase CSR build (count, scan, fill)
     def _csr_lists(self, npts, device, search):

@@ -20,7 +20,9 @@
 #include <vector>
 
 #include "../../include/letkf_amd.h"
+#include "../../include/letkf_amd_interp.h"
 #include "letkf_device.h"
+#include "letkf_interp_dev.h"
 
 namespace letkf {
 
@@ -95,6 +97,8 @@ struct letkf_ctx {
   DevBuf efso_ws;             // EFSO: the pair contributions of a slab, their sort by observation row and the row offsets
   DevBuf obsanal_ws;          // das_letkf_obs: the targets' coordinates, pseudo-state, inflation and flag word
   DevBuf staged_ws;           // staged path: per-point slabs of a batch + meta / info words
+  DevBuf interp_fix;          // letkf_das_interp_dev: the coarse indices and the coarse points' coordinates
+  DevBuf interp_ws;           // ... the kept T / w-bar and the gathered observation rows of a slab of levels
   std::string last_path;      // kernels the last loop-body / letkf_core launch went through (bench.py reports it)
   bool timing = false;
   bool staged_poly = true;    // LETKF_OPT_STAGED_POLY
@@ -1014,6 +1018,195 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     if (int rc = das_points_impl(c, &a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
     l0 = l1;
   }
+  return LETKF_OK;
+}
+
+// (3d) weight interpolation (include/letkf_amd_interp.h): letkf_core at the coarse points of a tile by slabs of levels -- the
+// column search on the coarse columns, the lists gathered into the batch form of letkf_core_batch_dev, every solver route with
+// T, w-bar (and w-bar_det) kept -- then the blend and the apply at every fine point of the slab (letkf_interp.hip)
+int letkf_das_interp_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const letkf_interp_args* ia) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!g || !t || !ia) return fail(LETKF_E_INVALID, "args / tables / interp is NULL");
+  if (ia->nx < 1 || ia->ny < 1 || ia->nlev < 1 || g->npts != (int64_t)ia->nx * ia->ny * ia->nlev)
+    return fail(LETKF_E_INVALID, "npts must be nx * ny * nlev");
+  if (ia->stride_x < 1 || ia->stride_x > 8 || ia->stride_y < 1 || ia->stride_y > 8) return fail(LETKF_E_INVALID, "strides must be 1..8");
+  if (g->k > 128) return fail(LETKF_E_INVALID, "weight interpolation serves k <= 128");
+  if (g->infl_adaptive) return fail(LETKF_E_INVALID, "adaptive inflation belongs to solved points: not on the interpolation route");
+  if (g->trans_out || g->transm_out || g->pa_out || g->nsweep)
+    return fail(LETKF_E_INVALID, "trans_out / transm_out / pa_out / nsweep must be NULL on the interpolation route");
+  if (!ia->rig || !ia->rjg || !ia->rlev || !ia->rz) return fail(LETKF_E_INVALID, "a point coordinate array is NULL");
+  if (t->nctype < 1 || t->ngroup < 1) return fail(LETKF_E_INVALID, "bad nctype / ngroup");
+  if (int rc = das_args_check(g, false)) return rc;
+  if (g->nv > 32) return fail(LETKF_E_INVALID, "nv must be <= 32");
+  const int k = g->k, nlev = ia->nlev;
+  const int64_t npts = g->npts;
+  const int64_t budget = ia->ws_bytes > 0 ? ia->ws_bytes : ((int64_t)8 << 30);
+
+  // ---- the coarse set (letkf_interp_coarse_axis and nothing else), its indices and coordinates on the device
+  std::vector<int32_t> hx((size_t)ia->nx), hy((size_t)ia->ny);
+  int32_t ncx = 0, ncy = 0;
+  if (letkf_interp_coarse_axis(ia->nx, ia->stride_x, hx.data(), &ncx) || letkf_interp_coarse_axis(ia->ny, ia->stride_y, hy.data(), &ncy))
+    return fail(LETKF_E_INVALID, "bad extent / stride");
+  const int64_t ncc = (int64_t)ncx * ncy, npc = ncc * nlev;
+  const size_t o_iy = align256((size_t)ncx * 4), o_rig = o_iy + align256((size_t)ncy * 4), o_rjg = o_rig + align256((size_t)ncc * 8);
+  const size_t o_rlev = o_rjg + align256((size_t)ncc * 8), o_rz = o_rlev + align256((size_t)npc * 8);
+  if (int rc = grow(c, &c->interp_fix, o_rz + (size_t)npc * 8 + 256)) return rc;
+  letkf::InterpGrid G;
+  G.nx = ia->nx;
+  G.ny = ia->ny;
+  G.nlev = nlev;
+  G.ncx = ncx;
+  G.ncy = ncy;
+  G.ix = reinterpret_cast<const int*>(c->interp_fix.p);
+  G.iy = reinterpret_cast<const int*>(c->interp_fix.p + o_iy);
+  HIP_TRY(hipMemcpyAsync(c->interp_fix.p, hx.data(), (size_t)ncx * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->interp_fix.p + o_iy, hy.data(), (size_t)ncy * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (hx, hy are this call's own)
+  letkf::InterpCoordArgs ca;
+  ca.G = G;
+  ca.rig = ia->rig;
+  ca.rjg = ia->rjg;
+  ca.rlev = ia->rlev;
+  ca.rz = ia->rz;
+  ca.crig = reinterpret_cast<double*>(c->interp_fix.p + o_rig);
+  ca.crjg = reinterpret_cast<double*>(c->interp_fix.p + o_rjg);
+  ca.crlev = reinterpret_cast<double*>(c->interp_fix.p + o_rlev);
+  ca.crz = reinterpret_cast<double*>(c->interp_fix.p + o_rz);
+  HIP_TRY(letkf::launch_interp_coords(ca, c->num_cu, c->stream));
+
+  // ---- count pass over the coarse points of all levels, prefix sum; level boundaries and the counts back to the host
+  RingKeep ring_keep_guard(c);
+  ScanWs sw;
+  if (int rc = scan_ws(c, &c->scratch, (size_t)npc, 0, &sw)) return rc;
+  HIP_TRY(zero_total(c, sw));
+  if (int rc = letkf_obs_search_columns_dev(c, t, ncc, nlev, ca.crig, ca.crjg, ca.crlev, ca.crz, 0, sw.counts, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr))
+    return rc;
+  HIP_TRY(scan_offsets(c, sw));
+  if (ia->nobs_coarse) HIP_TRY(hipMemcpyAsync(ia->nobs_coarse, sw.counts, (size_t)npc * 4, hipMemcpyDeviceToDevice, c->stream));
+  std::vector<int32_t> hcount((size_t)npc);
+  if (int rc = offsets_to_host(c, sw, (size_t)ncc, hcount.data(), sw.counts, (size_t)npc * 4)) return rc;
+  const std::vector<int64_t>& lev_off = sw.hoff;
+  std::vector<int32_t> lev_max((size_t)nlev, 0);
+  for (int l = 0; l < nlev; ++l)
+    for (int64_t cc = 0; cc < ncc; ++cc) lev_max[(size_t)l] = std::max(lev_max[(size_t)l], hcount[(size_t)(l * ncc + cc)]);
+
+  // the rules' switches and the state of the call, as the kernels of this route read them
+  letkf::PointArgs P;
+  std::memset(&P, 0, sizeof(P));
+  P.k = k;
+  P.nv = g->nv;
+  P.npts = npts;
+  P.ensval = g->ensval;
+  P.kld = g->kld;
+  P.dep = g->dep;
+  P.det_run = g->det_run;
+  P.relax_to_inflated_prior = g->relax_to_inflated_prior;
+  P.iv_p = g->iv_p;
+  P.iv_q_first = g->iv_q_first;
+  P.iv_q_last = g->iv_q_last;
+  P.relax_alpha = g->relax_alpha;
+  P.relax_alpha_spread = g->relax_alpha_spread;
+  P.q_update_top = g->q_update_top;
+  P.q_sprd_max = g->q_sprd_max;
+  P.beta = g->beta;
+  P.infl = g->infl;
+  P.infl_sv = g->infl_sv > 0 ? g->infl_sv : npts;
+  P.gues = g->gues;
+  P.anal = g->anal;
+  P.sp = g->sp;
+  P.sm = g->sm;
+  P.sv = g->sv;
+  P.status = g->status;
+  P.rtps_out = g->rtps_infl_out;
+  P.var_mask = g->var_mask ? g->var_mask : ~0u;
+
+  // ---- slabs of levels: the lists (20 B per entry), per coarse point the kept k * k + 2 k doubles, rho, count and status, and the
+  // gathered rows of the slab's longest list (k + 4 doubles each)
+  const int64_t kept = ((int64_t)k * k + 2 * (int64_t)k + 2) * 8;
+  auto slab_bytes = [&](int l0, int l1, int nmax) {
+    return 20 * (lev_off[(size_t)l1] - lev_off[(size_t)l0]) + (int64_t)(l1 - l0) * ncc * (kept + (int64_t)nmax * (k + 4) * 8);
+  };
+  std::string solve_path;
+  int l0 = 0;
+  while (l0 < nlev) {
+    int l1 = l0 + 1, nmax = std::max(1, lev_max[(size_t)l0]);
+    while (l1 < nlev) {
+      const int nm = std::max(nmax, lev_max[(size_t)l1]);
+      if (slab_bytes(l0, l1 + 1, nm) > budget) break;
+      nmax = nm;
+      ++l1;
+    }
+    const int nl = l1 - l0;
+    const int64_t p0c = (int64_t)l0 * ncc, nb = (int64_t)nl * ncc;
+    ListSlab ls;
+    if (int rc = list_slab(c, lev_off[(size_t)l0], lev_off[(size_t)l1], &ls)) return rc;
+    if (int rc = letkf_obs_search_columns_dev(c, t, ncc, nl, ca.crig, ca.crjg, ca.crlev + p0c, ca.crz + p0c, 1, nullptr, sw.off + p0c, ls.idx,
+                                              ls.rd, ls.rl, nullptr, nullptr))
+      return rc;
+    // T | w-bar | w-bar_det | rho | rdiag | rloc | dep | depd | hdxb | nobsl | status
+    const size_t s_T = align256((size_t)nb * k * k * 8), s_w = align256((size_t)nb * k * 8), s_r = align256((size_t)nb * 8);
+    const size_t s_o = align256((size_t)nb * nmax * 8), s_h = align256((size_t)nb * nmax * k * 8), s_i = align256((size_t)nb * 4);
+    const size_t o_w = s_T, o_wd = o_w + s_w, o_rho = o_wd + s_w, o_rd = o_rho + s_r, o_rl = o_rd + s_o, o_dep = o_rl + s_o;
+    const size_t o_depd = o_dep + s_o, o_h = o_depd + s_o, o_n = o_h + s_h, o_st = o_n + s_i;
+    if (int rc = grow(c, &c->interp_ws, o_st + s_i + 256)) return rc;
+    char* w = c->interp_ws.p;
+    letkf::InterpGatherArgs ga;
+    ga.G = G;
+    ga.A = P;
+    ga.l0 = l0;
+    ga.nl = nl;
+    ga.nobs = nmax;
+    ga.obs_off = reinterpret_cast<const long*>(sw.off);
+    ga.obs_idx = ls.idx;
+    ga.rdiag_l = ls.rd;
+    ga.rloc_l = ls.rl;
+    ga.nobsl = reinterpret_cast<int*>(w + o_n);
+    ga.hdxb = reinterpret_cast<double*>(w + o_h);
+    ga.rdiag = reinterpret_cast<double*>(w + o_rd);
+    ga.rloc = reinterpret_cast<double*>(w + o_rl);
+    ga.dep = reinterpret_cast<double*>(w + o_dep);
+    ga.depd = g->det_run ? reinterpret_cast<double*>(w + o_depd) : nullptr;
+    ga.rho = reinterpret_cast<double*>(w + o_rho);
+    HIP_TRY(letkf::launch_interp_gather(ga, c->num_cu, c->stream));
+    // letkf_core at the slab's coarse points, as letkf_core_batch_dev runs it (letkf_tools.f90:420-447: rdiag carries the
+    // localisation, transm and transmd are asked for).  Every solve is cold: a warm-start run would tie a point's rounding
+    // to the slab it falls in.
+    letkf::PointArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.k = k;
+    a.nv = 0;
+    a.var_mask = ~0u;
+    a.mode = 1;
+    a.npts = nb;
+    a.nobsl = ga.nobsl;
+    a.hdxb = ga.hdxb;
+    a.rdiag = ga.rdiag;
+    a.rloc = ga.rloc;
+    a.depv = ga.dep;
+    a.depd = ga.depd;
+    a.nobs = nmax;
+    a.rdiag_wloc = 1;
+    a.infl = ga.rho;
+    a.trans_out = reinterpret_cast<double*>(w);
+    a.transm_out = reinterpret_cast<double*>(w + o_w);
+    a.transmd_out = g->det_run ? reinterpret_cast<double*>(w + o_wd) : nullptr;
+    a.status = reinterpret_cast<int*>(w + o_st);
+    if (int rc = launch(c, a, 1, 1)) return rc;
+    solve_path = c->last_path;
+    letkf::InterpApplyArgs aa;
+    aa.G = G;
+    aa.A = P;
+    aa.l0 = l0;
+    aa.nl = nl;
+    aa.T = a.trans_out;
+    aa.wbar = a.transm_out;
+    aa.wbard = a.transmd_out;
+    aa.cstatus = a.status;
+    HIP_TRY(letkf::launch_interp_apply(aa, c->stream));
+    l0 = l1;
+  }
+  c->last_path = "interp: search_columns + " + solve_path + " + " + letkf::interp_apply_kernel_name(k);
   return LETKF_OK;
 }
 
