@@ -6,7 +6,10 @@ solves, the run-to-run spread, and per variable RMS(interpolated - full) / RMS(f
 where neighbouring points see similar observations).  Not the contract bench (bench.py).
 
   bench_interp.py [WORKLOAD] [--strides 2 3 4] [--reps 3] [--out FILE]
-  bench_interp.py [WORKLOAD] --full-only     the full analysis alone (with LETKF_AMD_LIB: another build of the library)"""
+  bench_interp.py [WORKLOAD] --full-only     the full analysis alone (with LETKF_AMD_LIB: another build of the library)
+
+A/B against another build: LETKF_AMD_LIB=/path/to/its/libletkf_amd.so bench_interp.py ..., then the same line without it.  A
+library that lacks the window entries (letkf_amd_interp_window.h; this script does not call them) is loaded without them."""
 import argparse
 import json
 import os
@@ -51,6 +54,9 @@ def main():
     pkg = load_package()
     if args.full_only:
         pkg.INTERP_ARGTYPES.clear()      # (another build of the library may not have the entries)
+    import ctypes
+    if os.path.exists(pkg.LIB_PATH) and not hasattr(ctypes.CDLL(pkg.LIB_PATH), "letkf_das_interp_window_dev"):
+        pkg.INTERP_WINDOW_ARGTYPES.clear()      # (a build from before include/letkf_amd_interp_window.h: not called here)
     pkg.build()
     dev = torch.device("cuda:0")
     ctx = pkg.Context(0, torch.cuda.current_stream().cuda_stream)

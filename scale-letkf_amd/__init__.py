@@ -28,6 +28,7 @@ def build(force=False):
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp_window.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
     stale = force or not os.path.exists(LIB_PATH) or any(
@@ -383,6 +384,20 @@ INTERP_ARGTYPES = {
     "letkf_das_interp_dev": [_VP, _VP, _VP, _VP],
 }
 
+
+class InterpWindow(C.Structure):
+    """letkf_interp_window (include/letkf_amd_interp_window.h)"""
+    _fields_ = [("gnx", C.c_int32), ("gny", C.c_int32), ("gi0", C.c_int32), ("gj0", C.c_int32), ("oi0", C.c_int32),
+                ("oj0", C.c_int32), ("onx", C.c_int32), ("ony", C.c_int32)]
+
+
+# ... and of the second companion header include/letkf_amd_interp_window.h, again a table of its own
+INTERP_WINDOW_VERSION = 1
+INTERP_WINDOW_ARGTYPES = {
+    "letkf_interp_window_axis": [_I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP],
+    "letkf_das_interp_window_dev": [_VP, _VP, _VP, _VP, _VP],
+}
+
 _lib = None
 
 
@@ -398,7 +413,7 @@ def lib():
         except ImportError:
             pass
         _lib = C.CDLL(LIB_PATH)
-        for name, at in list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()):
+        for name, at in list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()) + list(INTERP_WINDOW_ARGTYPES.items()):
             f = getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
             f.argtypes, f.restype = at, RESTYPES.get(name, _INT)
     return _lib
@@ -412,6 +427,19 @@ def interp_coarse_axis(n, stride):
     rc = lib().letkf_interp_coarse_axis(n, stride, idx.ctypes.data_as(C.c_void_p), C.byref(cnt))
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_interp_coarse_axis: {rc}")
+    return idx[:cnt.value].copy()
+
+
+def interp_window_axis(gn, stride, g0, n, o0, on):
+    """letkf_interp_window_axis (host only): the coarse lines of one axis that the owned range [o0, o0 + on) of arrays of n
+    points at global index g0 needs, of a domain of gn points -- ascending array indices as an int32 numpy array.  Raises
+    LetkfError where the entry refuses (a needed line outside the arrays among the reasons)."""
+    import numpy as np
+    idx = np.zeros(max(int(on), 0) + 2, dtype=np.int32)
+    cnt = C.c_int32(0)
+    rc = lib().letkf_interp_window_axis(gn, stride, g0, n, o0, on, idx.ctypes.data_as(C.c_void_p), C.byref(cnt))
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_interp_window_axis: {rc}")
     return idx[:cnt.value].copy()
 
 
@@ -557,6 +585,27 @@ class Context:
         i.nx, i.ny, i.nlev, i.stride_x, i.stride_y, i.ws_bytes = nx, ny, nlev, stride_x, stride_y, int(ws_bytes)
         i.rig, i.rjg, i.rlev, i.rz, i.nobs_coarse = _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), _ptr(nobs_coarse)
         self._check(self._l.letkf_das_interp_dev(self._c, C.byref(a), C.byref(tables), C.byref(i)))
+
+    def das_interp_window(self, k, nv, tables, nx, ny, nlev, stride_x, stride_y, rig, rjg, rlev, rz, ensval, kld, dep,
+                          infl, gues, anal, sp, sm, sv, window=None, ws_bytes=0, nobs_coarse=None, npts=None, beta=None, det_run=False,
+                          infl_adaptive=False, relax_to_inflated_prior=False, relax_alpha=0.0, relax_alpha_spread=0.0,
+                          q_update_top=0.0, q_sprd_max=0.0, iv_p=4, iv_q_first=5, iv_q_last=10, status=None, nsweep=None,
+                          rtps_infl_out=None, var_mask=0, infl_sv=0, trans_out=None, transm_out=None, pa_out=None):
+        """letkf_das_interp_window_dev (include/letkf_amd_interp_window.h): das_interp's arguments, with nx, ny, nlev the
+        extents of the arrays handed in, and the window (an InterpWindow, a tuple (gnx, gny, gi0, gj0, oi0, oj0, onx, ony), or
+        None for the whole arrays as the whole domain): the coarse lattice is the domain's, the owned rectangle is analysed,
+        and of the halo only the coarse columns interp_window_axis names are read."""
+        a = self._das_args(k, nv, nx * ny * nlev if npts is None else npts, ensval, kld, dep, infl, gues, anal, sp, sm, sv,
+                           beta, det_run, infl_adaptive, relax_to_inflated_prior, relax_alpha, relax_alpha_spread, q_update_top,
+                           q_sprd_max, iv_p, iv_q_first, iv_q_last, status, nsweep, rtps_infl_out, 0, var_mask, infl_sv)
+        a.trans_out, a.transm_out, a.pa_out = _ptr(trans_out), _ptr(transm_out), _ptr(pa_out)
+        i = InterpArgs()
+        i.nx, i.ny, i.nlev, i.stride_x, i.stride_y, i.ws_bytes = nx, ny, nlev, stride_x, stride_y, int(ws_bytes)
+        i.rig, i.rjg, i.rlev, i.rz, i.nobs_coarse = _ptr(rig), _ptr(rjg), _ptr(rlev), _ptr(rz), _ptr(nobs_coarse)
+        if window is not None and not isinstance(window, InterpWindow):
+            window = InterpWindow(*[int(v) for v in window])
+        self._check(self._l.letkf_das_interp_window_dev(self._c, C.byref(a), C.byref(tables), C.byref(i),
+                                                        None if window is None else C.byref(window)))
 
     # ---- (3) obs_local on the device: two-phase CSR build (count, scan, fill)
     def _csr_lists(self, npts, device, search):

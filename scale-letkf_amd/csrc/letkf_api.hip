@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "../../include/letkf_amd.h"
-#include "../../include/letkf_amd_interp.h"
+#include "../../include/letkf_amd_interp_window.h"
 #include "letkf_device.h"
 #include "letkf_interp_dev.h"
 
@@ -1025,6 +1025,13 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
 // column search on the coarse columns, the lists gathered into the batch form of letkf_core_batch_dev, every solver route with
 // T, w-bar (and w-bar_det) kept -- then the blend and the apply at every fine point of the slab (letkf_interp.hip)
 int letkf_das_interp_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const letkf_interp_args* ia) {
+  return letkf_das_interp_window_dev(c, g, t, ia, nullptr);
+}
+
+// ... on the coarse lattice of a whole domain, for the window of it that the call owns (include/letkf_amd_interp_window.h);
+// without a window the arrays are the domain
+int letkf_das_interp_window_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const letkf_interp_args* ia,
+                                const letkf_interp_window* win) {
   if (int rc = check_ctx(c)) return rc;
   if (!g || !t || !ia) return fail(LETKF_E_INVALID, "args / tables / interp is NULL");
   if (ia->nx < 1 || ia->ny < 1 || ia->nlev < 1 || g->npts != (int64_t)ia->nx * ia->ny * ia->nlev)
@@ -1042,11 +1049,35 @@ int letkf_das_interp_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sear
   const int64_t npts = g->npts;
   const int64_t budget = ia->ws_bytes > 0 ? ia->ws_bytes : ((int64_t)8 << 30);
 
-  // ---- the coarse set (letkf_interp_coarse_axis and nothing else), its indices and coordinates on the device
-  std::vector<int32_t> hx((size_t)ia->nx), hy((size_t)ia->ny);
-  int32_t ncx = 0, ncy = 0;
-  if (letkf_interp_coarse_axis(ia->nx, ia->stride_x, hx.data(), &ncx) || letkf_interp_coarse_axis(ia->ny, ia->stride_y, hy.data(), &ncy))
+  // ---- the coarse set (letkf_interp_coarse_axis / letkf_interp_window_axis and nothing else), its indices and coordinates on
+  // the device
+  letkf_interp_window whole = {ia->nx, ia->ny, 0, 0, 0, 0, ia->nx, ia->ny};
+  const letkf_interp_window& W = win ? *win : whole;
+  if (W.gnx < 1 || W.gny < 1 || W.onx < 1 || W.ony < 1) return fail(LETKF_E_INVALID, "window: extents must be >= 1");
+  if (W.gi0 < 0 || (int64_t)W.gi0 + ia->nx > W.gnx || W.gj0 < 0 || (int64_t)W.gj0 + ia->ny > W.gny)
+    return fail(LETKF_E_INVALID, "window: the array rectangle is not inside the domain");
+  if (W.oi0 < 0 || (int64_t)W.oi0 + W.onx > ia->nx || W.oj0 < 0 || (int64_t)W.oj0 + W.ony > ia->ny)
+    return fail(LETKF_E_INVALID, "window: the owned rectangle is not inside the arrays");
+  std::vector<int32_t> hx((size_t)ia->nx + 2), hy((size_t)ia->ny + 2);
+  int32_t ncx = 0, ncy = 0, bad = -1;
+  if (win) {
+    if (letkf::interp_window_axis(W.gnx, ia->stride_x, W.gi0, ia->nx, W.oi0, W.onx, hx.data(), &ncx, &bad))
+      return fail(LETKF_E_INVALID, "window: the needed coarse line x = " + std::to_string(bad) + " (global) lies outside the arrays");
+    if (letkf::interp_window_axis(W.gny, ia->stride_y, W.gj0, ia->ny, W.oj0, W.ony, hy.data(), &ncy, &bad))
+      return fail(LETKF_E_INVALID, "window: the needed coarse line y = " + std::to_string(bad) + " (global) lies outside the arrays");
+  } else if (letkf_interp_coarse_axis(ia->nx, ia->stride_x, hx.data(), &ncx) || letkf_interp_coarse_axis(ia->ny, ia->stride_y, hy.data(), &ncy)) {
     return fail(LETKF_E_INVALID, "bad extent / stride");
+  }
+  // every cell of the run holds an owned point (the run is the lines that weigh at one): the apply kernel's grid relies on it
+  for (int d = 0; d < 2; ++d) {
+    const std::vector<int32_t>& h = d ? hy : hx;
+    const int nc = d ? ncy : ncx, o0 = d ? W.oj0 : W.oi0, o1 = o0 + (d ? W.ony : W.onx);
+    for (int cl = 0; cl < (nc > 1 ? nc - 1 : 1); ++cl) {
+      int lo, hi;
+      letkf::interp_cell_lines(cl, nc, h[(size_t)cl], h[(size_t)std::min(cl + 1, nc - 1)], o0, o1, &lo, &hi);
+      if (hi < lo) return fail(LETKF_E_INVALID, "window: a cell of the coarse run owns no point (internal)");
+    }
+  }
   const int64_t ncc = (int64_t)ncx * ncy, npc = ncc * nlev;
   const size_t o_iy = align256((size_t)ncx * 4), o_rig = o_iy + align256((size_t)ncy * 4), o_rjg = o_rig + align256((size_t)ncc * 8);
   const size_t o_rlev = o_rjg + align256((size_t)ncc * 8), o_rz = o_rlev + align256((size_t)npc * 8);
@@ -1057,6 +1088,10 @@ int letkf_das_interp_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sear
   G.nlev = nlev;
   G.ncx = ncx;
   G.ncy = ncy;
+  G.ox0 = W.oi0;
+  G.ox1 = W.oi0 + W.onx;
+  G.oy0 = W.oj0;
+  G.oy1 = W.oj0 + W.ony;
   G.ix = reinterpret_cast<const int*>(c->interp_fix.p);
   G.iy = reinterpret_cast<const int*>(c->interp_fix.p + o_iy);
   HIP_TRY(hipMemcpyAsync(c->interp_fix.p, hx.data(), (size_t)ncx * 4, hipMemcpyHostToDevice, c->stream));

@@ -5,7 +5,7 @@
 
 #include <algorithm>
 
-#include "../../include/letkf_amd_interp.h"
+#include "../../include/letkf_amd_interp_window.h"
 #include "letkf_interp_dev.h"
 #include "letkf_rules_dev.h"
 
@@ -25,7 +25,36 @@ extern "C" int letkf_interp_coarse_axis(int32_t n, int32_t stride, int32_t* idx,
   return LETKF_OK;
 }
 
+extern "C" int letkf_interp_window_axis(int32_t gn, int32_t stride, int32_t g0, int32_t n, int32_t o0, int32_t on, int32_t* idx,
+                                        int32_t* count) {
+  return letkf::interp_window_axis(gn, stride, g0, n, o0, on, idx, count, nullptr);
+}
+
 namespace letkf {
+
+int interp_window_axis(int32_t gn, int32_t stride, int32_t g0, int32_t n, int32_t o0, int32_t on, int32_t* idx, int32_t* count,
+                       int32_t* bad) {
+  if (gn < 1 || stride < 1 || n < 1 || on < 1 || !count) return LETKF_E_INVALID;
+  if (g0 < 0 || (int64_t)g0 + n > gn || o0 < 0 || (int64_t)o0 + on > n) return LETKF_E_INVALID;
+  // the global lines: multiples of the stride below gn, and gn - 1 (letkf_interp_coarse_axis)
+  const int64_t p = (int64_t)g0 + o0, q = p + on - 1;
+  const bool p_on = p % stride == 0 || p == gn - 1;
+  int64_t l = p_on ? p : p / stride * stride;   // (p itself, or its predecessor)
+  int32_t m = 0;
+  for (;;) {
+    if (l < g0 || l >= (int64_t)g0 + n) {
+      if (bad) *bad = (int32_t)l;
+      return LETKF_E_INVALID;
+    }
+    if (idx) idx[m] = (int32_t)(l - g0);
+    ++m;
+    if (l >= q) break;                          // (q itself, or its successor)
+    l = std::min<int64_t>(l + stride, gn - 1);
+  }
+  *count = m;
+  return LETKF_OK;
+}
+
 namespace {
 
 using namespace rules_dev;
@@ -116,10 +145,18 @@ __global__ __launch_bounds__(64 * NW) void letkf_interp_apply_kernel(const Inter
   const long lev = S.l0 + ll;
   const int cxb = cx + 1 < G.ncx ? cx + 1 : G.ncx - 1, cyb = cy + 1 < G.ncy ? cy + 1 : G.ncy - 1;
   const int ia = G.ix[cx], ib = G.ix[cxb], jc = G.iy[cy], jd = G.iy[cyb];
-  // the cell owns i in [ia, ib) and j in [jc, jd); the last cell of a direction also its far line
-  const int nox = (cx == ncelx - 1) ? ib - ia + 1 : ib - ia;
-  const int noy = (cy == ncely - 1) ? jd - jc + 1 : jd - jc;
+  // the cell owns i in [ia, ib) and j in [jc, jd), the last cell of a direction also its far line; of these the call's own:
+  // the first cell of a direction may start above its near line, the last stop below its far line
+  int ilo, ihi, jlo, jhi;
+  interp_cell_lines(cx, G.ncx, ia, ib, G.ox0, G.ox1, &ilo, &ihi);
+  interp_cell_lines(cy, G.ncy, jc, jd, G.oy0, G.oy1, &jlo, &jhi);
+  const int nox = ihi - ilo + 1, noy = jhi - jlo + 1;
+  if (nox < 1 || noy < 1) return;   // (no cell of a call is without an owned point: the host has checked)
   const int npo = nox * noy, nrows = npo * nv;
+  // A corner that weighs 0 at every owned row of the cell is not staged: the far one where the cell's own lines are the
+  // near line alone, the near one where they are the far line alone (the last cell of a window that begins on it).
+  const bool far_x_unused = ihi == ia, near_x_unused = ilo == ib && ib > ia;
+  const bool far_y_unused = jhi == jc, near_y_unused = jlo == jd && jd > jc;
   const long ncc = (long)G.ncx * G.ncy, nij1 = (long)G.nx * G.ny;
   const double km1 = (double)(k - 1);
   const bool det = A.det_run && S.wbard;
@@ -150,9 +187,9 @@ __global__ __launch_bounds__(64 * NW) void letkf_interp_apply_kernel(const Inter
       const int v = valid[r] ? row / npo : 0, q = valid[r] ? row - v * npo : 0;
       const int qj = q / nox, qi = q - qj * nox;
       vv[r] = v;
-      pt[r] = (ia + qi) + (long)G.nx * (jc + qj) + nij1 * lev;
-      wx[r] = ib > ia ? (double)qi / (double)(ib - ia) : 0.0;
-      wy[r] = jd > jc ? (double)qj / (double)(jd - jc) : 0.0;
+      pt[r] = (ilo + qi) + (long)G.nx * (jlo + qj) + nij1 * lev;
+      wx[r] = ib > ia ? (double)(ilo + qi - ia) / (double)(ib - ia) : 0.0;
+      wy[r] = jd > jc ? (double)(jlo + qj - jc) / (double)(jd - jc) : 0.0;
     }
     // ---- and its row as the A operand: X' of the row, k-tail masked
     double ax[NSTEP];
@@ -161,7 +198,7 @@ __global__ __launch_bounds__(64 * NW) void letkf_interp_apply_kernel(const Inter
       const bool va = row < nrows;
       const int v = va ? row / npo : 0, q = va ? row - v * npo : 0;
       const int qj = q / nox, qi = q - qj * nox;
-      const double* g0 = A.gues + ((ia + qi) + (long)G.nx * (jc + qj) + nij1 * lev) * A.sp + (long)v * A.sv;
+      const double* g0 = A.gues + ((ilo + qi) + (long)G.nx * (jlo + qj) + nij1 * lev) * A.sp + (long)v * A.sv;
 #pragma unroll
       for (int s = 0; s < NSTEP; ++s) {
         const int i = 4 * s + lrow;
@@ -174,8 +211,7 @@ __global__ __launch_bounds__(64 * NW) void letkf_interp_apply_kernel(const Inter
 
 #pragma unroll 1
     for (int c = 0; c < 4; ++c) {
-      // (a corner on the far side weighs 0 at every owned point of a cell that owns one line of that direction)
-      if (((c & 1) && nox == 1) || ((c & 2) && noy == 1)) continue;
+      if (((c & 1) ? far_x_unused : near_x_unused) || ((c & 2) ? far_y_unused : near_y_unused)) continue;
       const double* Tc = S.T + (size_t)corner(c) * (size_t)k * (size_t)k;
       __syncthreads();
       for (int e = tid; e < KP * KC; e += 64 * NW) {

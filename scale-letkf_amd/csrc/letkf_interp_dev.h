@@ -10,13 +10,29 @@
 
 namespace letkf {
 
-// The tile and its coarse set: point p = i + nx * j + nx * ny * lev; coarse column cc = cx + ncx * cy is fine column
-// ix[cx] + nx * iy[cy]; coarse point cc + ncx * ncy * lev.
+// The arrays of the call and its coarse set: point p = i + nx * j + nx * ny * lev; coarse column cc = cx + ncx * cy is fine
+// column ix[cx] + nx * iy[cy]; coarse point cc + ncx * ncy * lev.  ix / iy are the call's run of the domain's coarse lines
+// (include/letkf_amd_interp_window.h) in array indices; the owned points are [ox0, ox1) x [oy0, oy1), the whole arrays where
+// the call has no window.
 struct InterpGrid {
   int nx, ny, nlev, ncx, ncy;
+  int ox0, ox1, oy0, oy1;
   const int* ix;   // dev [ncx]
   const int* iy;   // dev [ncy]
 };
+
+// The fine lines of one direction that cell c of a run of nc coarse lines owns, clipped to the owned range [o0, o1): the
+// cell [a, b] owns [a, b), its far line too where it is the last of the run.  Host and device share this one statement.
+__host__ __device__ inline void interp_cell_lines(int c, int nc, int a, int b, int o0, int o1, int* lo, int* hi) {
+  const int ncel = nc > 1 ? nc - 1 : 1;
+  const int end = (c == ncel - 1) ? b : b - 1;
+  *lo = a > o0 ? a : o0;
+  *hi = end < o1 - 1 ? end : o1 - 1;
+}
+
+// letkf_interp_window_axis with the global line that fell outside the arrays handed back (*bad; untouched otherwise)
+int interp_window_axis(int32_t gn, int32_t stride, int32_t g0, int32_t n, int32_t o0, int32_t on, int32_t* idx, int32_t* count,
+                       int32_t* bad);
 
 // the coordinates of the coarse columns and points, gathered for the column search
 struct InterpCoordArgs {

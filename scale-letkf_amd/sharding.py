@@ -30,6 +30,36 @@ def tile_partition(nx, ny, world):
     return [(xs[r % px], xs[r % px + 1], ys[r // px], ys[r // px + 1]) for r in range(world)]
 
 
+def interp_window_lines(gn, stride, p, q):
+    """The global coarse lines of one axis that the owned range [p, q] needs (include/letkf_amd_interp_window.h): the lines
+    of {0, stride, 2 stride, ...} | {gn - 1} within [p, q], the predecessor of p and the successor of q where these are no
+    lines themselves."""
+    line = lambda i: i % stride == 0 or i == gn - 1
+    lo = p if line(p) else p // stride * stride
+    hi = q if line(q) else min((q // stride + 1) * stride, gn - 1)
+    return [i for i in range(lo, hi + 1) if line(i)]
+
+
+def interp_window_rect(nx_g, ny_g, sx, sy, i0, i1, j0, j1):
+    """Weight interpolation on the owned global rectangle [i0, i1) x [j0, j1) of an nx_g x ny_g domain: the smallest array
+    rectangle the call needs and its window.  Returns dict(gi0, gj0, nx, ny: the rectangle in the domain; window: (gnx, gny,
+    gi0, gj0, oi0, oj0, onx, ony) for Context.das_interp_window; lines_x, lines_y: the call's coarse lines as array indices;
+    halo: the global (i, j) of the coarse columns outside the owned rectangle, which are all the call must be handed of it)."""
+    lx, ly = interp_window_lines(nx_g, sx, i0, i1 - 1), interp_window_lines(ny_g, sy, j0, j1 - 1)
+    gi0, gj0 = min(lx[0], i0), min(ly[0], j0)
+    nx, ny = max(lx[-1], i1 - 1) - gi0 + 1, max(ly[-1], j1 - 1) - gj0 + 1
+    halo = [(i, j) for j in ly for i in lx if not (i0 <= i < i1 and j0 <= j < j1)]
+    return dict(gi0=gi0, gj0=gj0, nx=nx, ny=ny, window=(nx_g, ny_g, gi0, gj0, i0 - gi0, j0 - gj0, i1 - i0, j1 - j0),
+                lines_x=[i - gi0 for i in lx], lines_y=[j - gj0 for j in ly], halo=halo)
+
+
+def interp_tile_window(nx_g, ny_g, px, py, pi, pj, sx, sy):
+    """interp_window_rect for tile (pi, pj) of the px x py tiles of tile_partition: the halo columns are what the tile must
+    fetch from its neighbours."""
+    assert tile_grid(px * py) == (px, py), "px x py must be the lattice tile_partition makes of px * py ranks"
+    return interp_window_rect(nx_g, ny_g, sx, sy, *tile_partition(nx_g, ny_g, px * py)[pi + px * pj])
+
+
 def cyclic_points(nij, rank, world):
     """The reference's cyclic dealing: local point i of ensemble-rank m is subdomain point m + world*i
     (scale/common/common_mpi_scale.f90:1428-1455, grd_to_buf)."""
