@@ -21,16 +21,18 @@ def coarse_axis(n, s):
 
 
 @functools.lru_cache(maxsize=None)
-def tile_case(k, nv=11, nx=7, ny=5, nlev=3, seed=5):
+def tile_case(k, nv=11, nx=7, ny=5, nlev=3, seed=5, dxs=5.5, dys=6.0):
+    """columns dxs x dys grid lengths apart (build_case's domain is 40 x 32: a larger tile needs smaller spacings); with
+    nv < 5 there is no pressure slot to fill, and no q_update_top for such a case"""
     rng = np.random.default_rng(seed + 1000 * k + nx)
     tc = build_case(seed, nlon=40, nlat=32, dx=1000.0, nobs_per_ctype=(180, 0, 120, 0), max_nobs=LIMITS, npts=1, obs_east_of=24.0)
     i_org, j_org = tc["scal"]["i_org"], tc["scal"]["j_org"]
     ii, jj = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")          # column i + nx*j
     if nx > 1:
-        rig = (i_org + 1.0 + 5.5 * ii).ravel() + rng.uniform(-0.2, 0.2, nx * ny)
+        rig = (i_org + 1.0 + dxs * ii).ravel() + rng.uniform(-0.2, 0.2, nx * ny)
     else:
         rig = np.full(nx * ny, i_org + 30.0) + rng.uniform(-0.2, 0.2, nx * ny)
-    rjg = (j_org + 4.0 + 6.0 * jj).ravel() + rng.uniform(-0.2, 0.2, nx * ny)
+    rjg = (j_org + 4.0 + dys * jj).ravel() + rng.uniform(-0.2, 0.2, nx * ny)
     nij1, npts = nx * ny, nx * ny * nlev
     zlev = np.linspace(500.0, 7000.0, nlev) if nlev > 1 else np.array([3000.0])
     rz = (zlev[:, None] + rng.uniform(-100.0, 100.0, (nlev, nij1))).ravel()
@@ -45,7 +47,8 @@ def tile_case(k, nv=11, nx=7, ny=5, nlev=3, seed=5):
     mean = rng.standard_normal((nv, npts)) * 5.0 + 50.0
     if nv > 5:
         mean[5:] = np.abs(mean[5:]) * 1e-3 + 1e-3
-    mean[4] = rlev
+    if nv > 4:
+        mean[4] = rlev
     x[:, k] = mean
     x[:, k + 1] = mean + rng.standard_normal((nv, npts)) * np.abs(x[:, 0]).max(axis=1, keepdims=True)
     infl = 1.07 * (1.0 + 0.05 * rng.uniform(size=npts * nv))
