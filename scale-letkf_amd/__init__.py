@@ -29,6 +29,7 @@ def build(force=False):
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp_window.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsope.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
     stale = force or not os.path.exists(LIB_PATH) or any(
@@ -398,6 +399,29 @@ INTERP_WINDOW_ARGTYPES = {
     "letkf_das_interp_window_dev": [_VP, _VP, _VP, _VP, _VP],
 }
 
+
+
+class ObsopeFields(C.Structure):
+    """letkf_obsope_fields (include/letkf_amd_obsope.h)"""
+    _fields_ = ([(n, C.c_int32) for n in ("nlev", "nlon", "nlat", "khalo", "ihalo", "jhalo", "nv3dd", "nv2dd", "nmem", "m0")] +
+                [("v3d", C.c_void_p)] + [(n, C.c_int64) for n in ("s3k", "s3i", "s3j", "s3v", "s3m")] +
+                [("v2d", C.c_void_p)] + [(n, C.c_int64) for n in ("s2i", "s2j", "s2v", "s2m")])
+
+
+class ObsopeParams(C.Structure):
+    """letkf_obsope_params (include/letkf_amd_obsope.h): file_radar, radar_meta and use_obs are HOST arrays"""
+    _fields_ = ([(n, C.c_void_p) for n in ("lon", "lat", "file_radar", "radar_meta", "rotc", "use_obs")] +
+                [(n, C.c_int32) for n in ("nobtype", "method_ref_calc", "use_terminal_velocity", "stggrd")] +
+                [(n, C.c_double) for n in ("min_radar_ref_dbz", "low_ref_shift", "radar_zmax", "ps_adjust_thres", "ri_off",
+                                           "rj_off")])
+
+
+# ... and of the third companion header include/letkf_amd_obsope.h, once more a table of its own
+OBSOPE_VERSION = 1
+OBSOPE_ARGTYPES = {
+    "letkf_obsope_dev": [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _I64],
+}
+
 _lib = None
 
 
@@ -413,7 +437,8 @@ def lib():
         except ImportError:
             pass
         _lib = C.CDLL(LIB_PATH)
-        for name, at in list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()) + list(INTERP_WINDOW_ARGTYPES.items()):
+        for name, at in (list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()) + list(INTERP_WINDOW_ARGTYPES.items()) +
+                         list(OBSOPE_ARGTYPES.items())):
             f = getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
             f.argtypes, f.restype = at, RESTYPES.get(name, _INT)
     return _lib
@@ -792,6 +817,14 @@ class Context:
 
     def set_obs_local(self, params, qcp, files, set_, idx, qc, ensval, kld, keep=()):
         return self._set_obs(self._l.letkf_set_obs_local_dev, params, qcp, files, set_, idx, qc, ensval, kld, keep)
+
+    def obsope(self, params, files, fields, set_, idx, qc, ensval, kld, row0=0, nrows=None):
+        """letkf_obsope_dev (include/letkf_amd_obsope.h): H(x) of fields.nmem members for the obsda rows row0 .. row0 + nrows - 1
+        (default: all of set_) into ensval[row, m0 .. m0 + nmem - 1], qc merged by maximum.  Call it before set_obs, which
+        pre-processes `files` in place."""
+        n = set_.numel() - row0 if nrows is None else nrows
+        self._check(self._l.letkf_obsope_dev(self._c, C.byref(params), C.byref(files), C.byref(fields), row0, n, _ptr(set_),
+                                             _ptr(idx), _ptr(qc), _ptr(ensval), kld))
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),

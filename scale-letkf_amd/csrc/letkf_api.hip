@@ -23,6 +23,7 @@
 #include "../../include/letkf_amd_interp_window.h"
 #include "letkf_device.h"
 #include "letkf_interp_dev.h"
+#include "letkf_obsope_dev.h"
 
 namespace letkf {
 
@@ -2312,6 +2313,24 @@ void letkf_core_c(int ne, int nobs, int nobsl, const double* hdxb, const double*
     st = rc;
   }
   if (status) *status = st;
+}
+
+// The observation operator (include/letkf_amd_obsope.h, letkf_obsope.hip): argument checks, the row flag's word, the launch.
+int letkf_obsope_dev(letkf_ctx* c, const letkf_obsope_params* p, const letkf_obs_file_rows* files, const letkf_obsope_fields* f,
+                     int64_t row0, int64_t nrows, const int32_t* set, const int32_t* idx, int32_t* qc, double* ensval,
+                     int64_t kld) try {
+  if (int rc = check_ctx(c)) return rc;
+  std::string msg;
+  if (int rc = letkf::obsope_check(p, files, f, row0, nrows, set, idx, qc, ensval, kld, &msg)) return fail(rc, msg);
+  if (int rc = grow(c, &c->scratch, 256)) return rc;
+  if (int rc = letkf::obsope_run(c->stream, p, files, f, row0, nrows, set, idx, qc, ensval, kld,
+                                 reinterpret_cast<int32_t*>(c->scratch.p), &msg))
+    return fail(rc, msg);
+  return LETKF_OK;
+} catch (const std::exception& e) {
+  return fail(LETKF_E_INVALID, std::string("letkf_obsope_dev: ") + e.what());
+} catch (...) {
+  return fail(LETKF_E_INVALID, "letkf_obsope_dev: unknown exception");
 }
 
 }  // extern "C"
