@@ -18,6 +18,8 @@
  * keeps no pointer past a call (except the context's own workspace).
  * Every function returns LETKF_OK (0) or a negative LETKF_E_* host-side error;
  * per-problem numerical status codes (>0) are written to the status arrays.
+ * No C++ exception leaves an entry: one raised inside (an allocation that
+ * fails, say) arrives as LETKF_E_INVALID with its text in letkf_amd_last_error().
  * There is NO CPU fallback: without a usable gfx950 device every compute entry
  * fails with LETKF_E_NO_DEVICE.
  */

@@ -1,4 +1,4 @@
-// letkf_device.h -- POD argument block shared by the host API (letkf_api.hip) and the device code
+// letkf_device.h -- POD argument block shared by the host API (letkf_api*.hip) and the device code
 // (letkf_kernels.hip).  Internal: the public C ABI is include/letkf_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -248,6 +248,9 @@ int trio_points_per_wave(int k);
 int sched_plan_check(long npts, long stride, int run_len, int grid, int ppw, int resident_per_xcd, int ub_of);
 bool trivial_pass_supports(const PointArgs& a);
 hipError_t launch_trivial_points(const PointArgs& a, hipStream_t st);
+// (letkf_trivial.hip) transmd[nbatch][ne] zeroed where nobsl == 0; counts zeroed where beta == 0
+hipError_t launch_zero_transmd_unobserved(int64_t nbatch, int ne, const int32_t* nobsl, double* transmd, hipStream_t st);
+hipError_t launch_zero_counts_where_beta_is_zero(int64_t n, const double* beta, int32_t* cnt, hipStream_t st);
 hipError_t launch_obs_departure(const letkf_qc_params& p, long nobs, const int* elm, const double* dat, const double* err,
                                 double* ensval, long kld, double* val, int* qc, int num_cu, hipStream_t st);
 hipError_t obs_mesh_sort(const letkf_mesh& m, long nobs, const int* ctype, const double* ri, const double* rj,

@@ -1,5 +1,5 @@
 // letkf_interp_dev.h -- argument blocks and launchers of the weight-interpolation route (letkf_interp.hip), shared with the
-// host entry letkf_das_interp_dev (letkf_api.hip).  Internal: the public interface is include/letkf_amd_interp.h.
+// host entry letkf_das_interp_dev (letkf_api_das.hip).  Internal: the public interface is include/letkf_amd_interp.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

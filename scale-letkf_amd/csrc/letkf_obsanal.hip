@@ -7,7 +7,7 @@
 //   variable 0  the target itself:  members ensval[j*kld + m] (perturbations), mean ob_dat[j] - dep[j] (H xbar^b),
 //               deterministic member ob_dat[j] - ensval[j*kld + k]
 //   variable 1  the target's pressure rlev in the mean and det slots (perturbations 0): what Q_UPDATE_TOP compares
-// and coordinates (ob_ri, ob_rj, and the vertical one by the target ctype's vmode).  The entry (letkf_api.hip) runs the
+// and coordinates (ob_ri, ob_rj, and the vertical one by the target ctype's vmode).  The entry (letkf_api_das.hip) runs the
 // search on those coordinates, the loop body with var_mask = 1 (variable 1 is never written), then the finish kernel.
 //   obsanal_targets_kernel  one thread per target: ctype (the ctype block of ac_ext that holds the row), coordinates,
 //                           pseudo-state, inflation; argument faults (a row outside [0, nobs) or outside every ctype

@@ -1,4 +1,4 @@
-// letkf_obsope_dev.h -- the observation operator's unit (letkf_obsope.hip) as the host entry letkf_obsope_dev (letkf_api.hip)
+// letkf_obsope_dev.h -- the observation operator's unit (letkf_obsope.hip) as the host entry letkf_obsope_dev (letkf_api_obs.hip)
 // calls it.  Internal: the public interface is include/letkf_amd_obsope.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -19,6 +19,25 @@
 #include "letkf_device.h"
 #include "letkf_rules_dev.h"
 
+// Two passes of the same kind for the host API: a thread per element, zero where the point has nothing to solve.
+// (extern "C": a profile lists them under these plain names)
+extern "C" {
+namespace {
+// transmd of letkf_core without depd (common/common_letkf.f90:97-99: zeroed at nobsl == 0 whatever depd is)
+__global__ void zero_transmd_where_nobsl_is_zero(int64_t nbatch, int ne, const int32_t* __restrict__ nobsl,
+                                                 double* __restrict__ transmd) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nbatch * ne && nobsl[i / ne] == 0) transmd[i] = 0.0;
+}
+
+// reported observation counts: the reference does not run obs_local at beta = 0 (letkf_tools.f90:333-359)
+__global__ void zero_where_beta_is_zero(int64_t n, const double* __restrict__ beta, int32_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && beta[i] == 0.0) cnt[i] = 0;
+}
+}  // namespace
+}  // extern "C"
+
 namespace letkf {
 
 using namespace rules_dev;
@@ -152,6 +171,17 @@ hipError_t launch_trivial_points(const PointArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)((a.npts * a.nv + 255) / 256);
   if (grid == 0) return hipSuccess;
   hipLaunchKernelGGL(letkf_trivial_points_kernel, dim3(grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_zero_transmd_unobserved(int64_t nbatch, int ne, const int32_t* nobsl, double* transmd, hipStream_t st) {
+  const int64_t n = nbatch * (int64_t)ne;
+  hipLaunchKernelGGL(zero_transmd_where_nobsl_is_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, nbatch, ne, nobsl, transmd);
+  return hipGetLastError();
+}
+
+hipError_t launch_zero_counts_where_beta_is_zero(int64_t n, const double* beta, int32_t* cnt, hipStream_t st) {
+  hipLaunchKernelGGL(zero_where_beta_is_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, beta, cnt);
   return hipGetLastError();
 }
 
