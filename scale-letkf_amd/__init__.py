@@ -30,6 +30,7 @@ def build(force=False):
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp_window.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsope.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_monit.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
     stale = force or not os.path.exists(LIB_PATH) or any(
@@ -422,6 +423,33 @@ OBSOPE_ARGTYPES = {
     "letkf_obsope_dev": [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _I64],
 }
 
+
+
+class HistState(C.Structure):
+    """letkf_hist_state (include/letkf_amd_monit.h): cz is a HOST array"""
+    _fields_ = ([("nv3d", C.c_int32), ("edge_fill", C.c_int32), ("x", C.c_void_p)] +
+                [(n, C.c_int64) for n in ("si", "sj", "sl", "sv")] + [("topo", C.c_void_p), ("cz", C.c_void_p), ("ztop", C.c_double)])
+
+
+class MonitParams(C.Structure):
+    """letkf_monit_params (include/letkf_amd_monit.h): elem_uid is a HOST array"""
+    _fields_ = ([(n, C.c_int32) for n in ("step", "departure_stat_radar", "nid", "reserved0")] +
+                [("elem_uid", C.c_void_p), ("t_range", C.c_double), ("dif", C.c_void_p)])
+
+
+class Obsdep(C.Structure):
+    """letkf_obsdep (include/letkf_amd_monit.h): the obsdep records, device arrays [nn]"""
+    _fields_ = [(n, C.c_void_p) for n in ("set", "idx", "qc", "omb", "oma")]
+
+
+# ... and of the fourth companion header include/letkf_amd_monit.h, a fifth table
+MONIT_VERSION = 1
+MONIT_ARGTYPES = {
+    "letkf_state_to_history_dev": [_VP, _VP, _VP, _VP, _VP],
+    "letkf_monit_obs_dev": [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_monit_type": [_I32, _VP, _I32, _I32, _VP],
+}
+
 _lib = None
 
 
@@ -438,7 +466,7 @@ def lib():
             pass
         _lib = C.CDLL(LIB_PATH)
         for name, at in (list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()) + list(INTERP_WINDOW_ARGTYPES.items()) +
-                         list(OBSOPE_ARGTYPES.items())):
+                         list(OBSOPE_ARGTYPES.items()) + list(MONIT_ARGTYPES.items())):
             f = getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
             f.argtypes, f.restype = at, RESTYPES.get(name, _INT)
     return _lib
@@ -466,6 +494,18 @@ def interp_window_axis(gn, stride, g0, n, o0, on):
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_interp_window_axis: {rc}")
     return idx[:cnt.value].copy()
+
+
+def monit_type(elem_uid, departure_stat_radar=False, departure_stat_h08=False):
+    """letkf_monit_type (host only): which elements of elem_uid monit_obs reports, as an int32 numpy array of 0 / 1."""
+    import numpy as np
+    ids = np.ascontiguousarray(elem_uid, dtype=np.int32)
+    out = np.zeros(len(ids), dtype=np.int32)
+    rc = lib().letkf_monit_type(len(ids), ids.ctypes.data_as(C.c_void_p), int(bool(departure_stat_radar)),
+                                int(bool(departure_stat_h08)), out.ctypes.data_as(C.c_void_p))
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_monit_type: {rc}: {lib().letkf_amd_last_error().decode()}")
+    return out
 
 
 def _ptr(t):
@@ -825,6 +865,29 @@ class Context:
         n = set_.numel() - row0 if nrows is None else nrows
         self._check(self._l.letkf_obsope_dev(self._c, C.byref(params), C.byref(files), C.byref(fields), row0, n, _ptr(set_),
                                              _ptr(idx), _ptr(qc), _ptr(ensval), kld))
+
+    def state_to_history(self, state, layout, v3d, v2d):
+        """letkf_state_to_history_dev (include/letkf_amd_monit.h): the state `state` (HistState) into member slot 0 of the
+        history fields v3d / v2d laid out as `layout` (ObsopeFields) says."""
+        self._check(self._l.letkf_state_to_history_dev(self._c, C.byref(state), C.byref(layout), _ptr(v3d), _ptr(v2d)))
+
+    def monit_obs(self, mparams, params, files, fields, set_, idx, rec, key=None, nn=None, outs=None):
+        """letkf_monit_obs_dev (include/letkf_amd_monit.h): monit_obs of step mparams.step over the rows key[0 .. nn - 1] of
+        set_ / idx (key None: the first nn, default all; a device int32 tensor, or a raw device address such as
+        ObsTableInfo.key together with nn); `rec` (Obsdep) is updated in place.  Returns (nobs int32 [nid], bias, rmse) device
+        tensors (`outs`: the three to write into)."""
+        import torch
+        raw = isinstance(key, int)
+        n = (key.numel() if key is not None else set_.numel()) if nn is None else nn
+        if outs is None:
+            outs = (torch.zeros(mparams.nid, dtype=torch.int32, device=set_.device),
+                    torch.zeros(mparams.nid, dtype=torch.float64, device=set_.device),
+                    torch.zeros(mparams.nid, dtype=torch.float64, device=set_.device))
+        self._check(self._l.letkf_monit_obs_dev(self._c, C.byref(mparams), C.byref(params), C.byref(files), C.byref(fields), n,
+                                                C.c_void_p(key) if raw else _ptr(key), _ptr(set_), _ptr(idx), C.byref(rec),
+                                                _ptr(outs[0]), _ptr(outs[1]),
+                                                _ptr(outs[2])))
+        return outs
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),

@@ -1,6 +1,6 @@
 // letkf_api_internal.h -- what the units of the C ABI (letkf_api*.hip) share: the context, the error barrier, the device
-// buffers, the plumbing of the list-driven entries and the launch of the loop body.  Host side, not installed; no other
-// unit includes it.  Every function is defined in the one unit named above its declaration.
+// buffers, the plumbing of the list-driven entries and the launch of the loop body.  Host side, not installed; beside them only
+// letkf_monit_entry.hip (the entries of include/letkf_amd_monit.h) includes it.  Every function is defined in the one unit named above its declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 
