@@ -14,6 +14,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LETKF_AMD_LIB") or os.path.join(HERE, "lib", "libletkf_amd.so")   # override: profiling twin (make PROF=1)
+OSSE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_osse.so")   # the OSSE tools (include/letkf_amd_obsmake.h); links against the production library
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -31,10 +32,12 @@ def build(force=False):
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp_window.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsope.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_monit.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsmake.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    stale = force or not os.path.exists(LIB_PATH) or any(
-        os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    libs = [LIB_PATH, OSSE_LIB_PATH]
+    stale = force or not all(os.path.exists(l) for l in libs) or any(
+        os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
         subprocess.check_call(["make", "-j4", "-C", HERE] + (["-B"] if force else []), stdout=2)
     return LIB_PATH
@@ -450,7 +453,84 @@ MONIT_ARGTYPES = {
     "letkf_monit_type": [_I32, _VP, _I32, _I32, _VP],
 }
 
+
+
+class ObsmakeSlot(C.Structure):
+    """letkf_obsmake_slot (include/letkf_amd_obsmake.h): dif and own are device arrays per file row"""
+    _fields_ = [("slot_lb", C.c_double), ("slot_ub", C.c_double), ("dif", C.c_void_p), ("own", C.c_void_p),
+                ("outside_undef", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class ObsmakeErr(C.Structure):
+    """letkf_obsmake_err (include/letkf_amd_obsmake.h): the OBSERR_* of the namelist"""
+    _fields_ = [(n, C.c_double) for n in ("obserr_u", "obserr_v", "obserr_t", "obserr_q", "obserr_rh", "obserr_ps",
+                                          "obserr_radar_ref", "obserr_radar_vr")]
+
+
+# ... and of the fifth companion header include/letkf_amd_obsmake.h, a sixth table: these entries are exported by the library
+# of the OSSE tools (OSSE_LIB_PATH, osse_lib()), not by the main one
+OBSMAKE_VERSION = 1
+OBSMAKE_ARGTYPES = {
+    "letkf_rand_create": [_I32, _VP],
+    "letkf_rand_destroy": [_VP],
+    "letkf_rand_set_chunk": [_VP, _I64],
+    "letkf_rand_res53": [_VP, _I64, _VP],
+    "letkf_randn_dev": [_VP, _VP, _I64, _VP],
+    "letkf_obsmake_slot_dev": [_VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_obsmake_noise_dev": [_VP, _VP, _VP, _VP],
+}
+
 _lib = None
+_osse_lib = None
+
+
+def osse_lib():
+    """dlopen the library of the OSSE tools, after the main one whose context and operator it uses."""
+    global _osse_lib
+    if _osse_lib is None:
+        lib()
+        if not os.path.exists(OSSE_LIB_PATH):
+            raise LetkfError(f"{OSSE_LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
+        _osse_lib = C.CDLL(OSSE_LIB_PATH)
+        for name, at in OBSMAKE_ARGTYPES.items():
+            f = getattr(_osse_lib, name)
+            f.argtypes, f.restype = at, _INT
+    return _osse_lib
+
+
+class Rand:
+    """letkf_rand (include/letkf_amd_obsmake.h): the SFMT19937 stream of a process's first init_gen_rand(seed), host state."""
+
+    def __init__(self, seed):
+        self._l = osse_lib()
+        self._r = C.c_void_p()
+        self._check(self._l.letkf_rand_create(int(seed), C.byref(self._r)))
+
+    def _check(self, rc):
+        if rc != LETKF_OK:
+            raise LetkfError(f"letkf_amd error {rc}: {lib().letkf_amd_last_error().decode()}")
+
+    def close(self):
+        if self._r:
+            self._l.letkf_rand_destroy(self._r)
+            self._r = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_chunk(self, pairs):
+        """pairs of uniforms per staging buffer of randn (the results do not depend on it)"""
+        self._check(self._l.letkf_rand_set_chunk(self._r, pairs))
+
+    def res53(self, n):
+        """the next n values of genrand_res53 as a float64 numpy array (com_rand without its clock seeding)"""
+        import numpy as np
+        out = np.zeros(max(int(n), 0), dtype=np.float64)
+        self._check(self._l.letkf_rand_res53(self._r, n, out.ctypes.data_as(C.c_void_p)))
+        return out
 
 
 def lib():
@@ -888,6 +968,20 @@ class Context:
                                                 _ptr(outs[0]), _ptr(outs[1]),
                                                 _ptr(outs[2])))
         return outs
+
+    def randn(self, rand, n, out):
+        """letkf_randn_dev (include/letkf_amd_obsmake.h): com_randn(n) from the stream `rand` (Rand) into the device tensor out."""
+        self._check(osse_lib().letkf_randn_dev(self._c, rand._r, n, _ptr(out)))
+
+    def obsmake_slot(self, slot, params, files, fields, counts=None):
+        """letkf_obsmake_slot_dev: one time slot of obsmake_cal -- files.dat of the slot's rows becomes H(x) of the one state in
+        `fields`, or undef; counts (device int64 [2], or None) = rows in the slot, rows processed."""
+        self._check(osse_lib().letkf_obsmake_slot_dev(self._c, C.byref(slot), C.byref(params), C.byref(files), C.byref(fields),
+                                                      _ptr(counts)))
+
+    def obsmake_noise(self, err, files, rand):
+        """letkf_obsmake_noise_dev: files.err by element, files.dat += err * com_randn over all rows in file order."""
+        self._check(osse_lib().letkf_obsmake_noise_dev(self._c, C.byref(err), C.byref(files), rand._r))
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),

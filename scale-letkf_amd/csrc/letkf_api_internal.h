@@ -1,6 +1,7 @@
 // letkf_api_internal.h -- what the units of the C ABI (letkf_api*.hip) share: the context, the error barrier, the device
 // buffers, the plumbing of the list-driven entries and the launch of the loop body.  Host side, not installed; beside them only
-// letkf_monit_entry.hip (the entries of include/letkf_amd_monit.h) includes it.  Every function is defined in the one unit named above its declaration.
+// letkf_monit_entry.hip (the entries of include/letkf_amd_monit.h) and, from the library of the OSSE tools, letkf_obsmake_entry.hip
+// (include/letkf_amd_obsmake.h) include it.  Every function is defined in the one unit named above its declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -44,6 +44,7 @@ struct ObsopeArgs {
   const int *set, *idx;
   unsigned use_mask;                              // bit typ-1 = USE_OBS(typ)
   int nobtype, method, use_tv, stggrd;
+  int keep_ref_low;                               // obsmake_cal's mode: qc 11 stays (obsope_tools.f90:864-884 has no :488)
   double min_ref, low_dbz, radar_zmax, ps_thres, ri_off, rj_off;
   // fields
   int nlev, khalo, nlevh, nlonh, nlath, nmem, m0;
@@ -53,13 +54,18 @@ struct ObsopeArgs {
   long s2i, s2j, s2v, s2m;
   // outputs
   long row0, nrows, kld;
+  const long* nrows_dev;                          // NULL, or the device's own row count (<= nrows, which then bounds the grid)
   int* qc;
   double* ensval;
 };
 
+// the rows of this call: nrows, or where the caller compacted them on the device the count it left there (wave-uniform)
+__device__ inline long rows_of(const ObsopeArgs& A) { return A.nrows_dev ? min(A.nrows, *A.nrows_dev) : A.nrows; }
+
 // set / idx outside the files, or a report type outside 1..nobtype
 __global__ void __launch_bounds__(256) obsope_rows_check_kernel(const ObsopeArgs A, int* __restrict__ bad) {
-  for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < A.nrows; n += (long)gridDim.x * blockDim.x) {
+  const long nrows = rows_of(A);
+  for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < nrows; n += (long)gridDim.x * blockDim.x) {
     const int f = A.set[A.row0 + n] - 1;
     const long i = (long)A.idx[A.row0 + n] - 1;
     bool ok = f >= 0 && f < A.nfile;
@@ -451,7 +457,7 @@ __device__ inline void stage_3(const ObsopeArgs& A, const long task, int qc, con
         } else {
           qc = kQcOtype;
         }
-        if (qc == kQcRefLow) qc = 0;                                 // obsope_tools.f90:488
+        if (qc == kQcRefLow && !A.keep_ref_low) qc = 0;              // obsope_tools.f90:488
       }
     }
   }
@@ -464,7 +470,7 @@ __device__ inline void stage_3(const ObsopeArgs& A, const long task, int qc, con
 __global__ void __launch_bounds__(256) letkf_obsope_kernel(const ObsopeArgs A) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long base = ((long)blockIdx.x * 4 + wave) * 64, ntask = A.nrows * A.nmem;
+  const long base = ((long)blockIdx.x * 4 + wave) * 64, ntask = rows_of(A) * A.nmem;
   if (base >= ntask) return;
   const int cnt = (int)(ntask - base < 64 ? ntask - base : 64);
   int my_qc = 0;
@@ -518,7 +524,7 @@ int obsope_check(const letkf_obsope_params* p, const letkf_obs_file_rows* files,
 
 int obsope_run(hipStream_t st, const letkf_obsope_params* p, const letkf_obs_file_rows* files, const letkf_obsope_fields* f,
                int64_t row0, int64_t nrows, const int32_t* set, const int32_t* idx, int32_t* qc, double* ensval, int64_t kld,
-               int32_t* flag, std::string* msg) {
+               int32_t* flag, std::string* msg, bool keep_ref_low, const int64_t* nrows_dev) {
   if (nrows == 0) return LETKF_OK;
   ObsopeArgs A = {};
   A.nfile = files->nfile;
@@ -541,6 +547,13 @@ int obsope_run(hipStream_t st, const letkf_obsope_params* p, const letkf_obs_fil
   A.v3d = f->v3d, A.s3k = f->s3k, A.s3i = f->s3i, A.s3j = f->s3j, A.s3v = f->s3v, A.s3m = f->s3m;
   A.v2d = f->v2d, A.s2i = f->s2i, A.s2j = f->s2j, A.s2v = f->s2v, A.s2m = f->s2m;
   A.row0 = row0, A.nrows = nrows, A.kld = kld, A.qc = qc, A.ensval = ensval;
+  static_assert(sizeof(long) == sizeof(int64_t), "the device count is read as long");
+  A.nrows_dev = reinterpret_cast<const long*>(nrows_dev);
+  if (keep_ref_low) {                                                // obsmake_cal: no USE_OBS test, no RADAR_ZMAX test
+    A.keep_ref_low = 1;
+    A.use_mask = 0xffffffffu;
+    A.radar_zmax = INFINITY;
+  }
   const int64_t ntask = nrows * (int64_t)f->nmem;
   if ((ntask + 255) / 256 > 0x7fffffff) return *msg = "more than 2^39 (row, member) pairs in one call", LETKF_E_INVALID;
 
