@@ -15,6 +15,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LETKF_AMD_LIB") or os.path.join(HERE, "lib", "libletkf_amd.so")   # override: profiling twin (make PROF=1)
 OSSE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_osse.so")   # the OSSE tools (include/letkf_amd_obsmake.h); links against the production library
+OBSSIM_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obssim.so")   # the model-to-observation simulator (include/letkf_amd_obssim.h); links against the production library too
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -33,9 +34,10 @@ def build(force=False):
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsope.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_monit.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsmake.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obssim.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = [LIB_PATH, OSSE_LIB_PATH]
+    libs = [LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH]
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
@@ -480,8 +482,46 @@ OBSMAKE_ARGTYPES = {
     "letkf_obsmake_noise_dev": [_VP, _VP, _VP, _VP],
 }
 
+
+
+class ObssimParams(C.Structure):
+    """letkf_obssim_params (include/letkf_amd_obssim.h): the lists and the radar are values, lon / lat / rotc device arrays"""
+    _fields_ = ([("nvar3", C.c_int32), ("vars3", C.c_int32 * 16), ("nvar2", C.c_int32), ("vars2", C.c_int32 * 16)] +
+                [(n, C.c_double) for n in ("radar_lon", "radar_lat", "radar_z")] +
+                [(n, C.c_void_p) for n in ("lon", "lat", "rotc")] +
+                [(n, C.c_int32) for n in ("method_ref_calc", "use_terminal_velocity", "stggrd", "round_single")] +
+                [(n, C.c_double) for n in ("min_radar_ref_dbz", "low_ref_shift", "ps_adjust_thres")])
+
+
+class ObssimOut(C.Structure):
+    """letkf_obssim_out (include/letkf_amd_obssim.h): v3 / v2 double, rec float device arrays (any may be NULL, not all)"""
+    _fields_ = [("v3", C.c_void_p), ("v2", C.c_void_p), ("rec", C.c_void_p), ("sm3", C.c_int64), ("sm2", C.c_int64)]
+
+
+# ... and of the sixth companion header include/letkf_amd_obssim.h, a seventh table: the entry is exported by the library of the
+# simulator (OBSSIM_LIB_PATH, obssim_lib()), not by the other two
+OBSSIM_VERSION = 1
+OBSSIM_ARGTYPES = {
+    "letkf_obssim_dev": [_VP, _VP, _VP, _VP],
+}
+
 _lib = None
 _osse_lib = None
+_obssim_lib = None
+
+
+def obssim_lib():
+    """dlopen the library of the simulator, after the main one whose context it uses."""
+    global _obssim_lib
+    if _obssim_lib is None:
+        lib()
+        if not os.path.exists(OBSSIM_LIB_PATH):
+            raise LetkfError(f"{OBSSIM_LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
+        _obssim_lib = C.CDLL(OBSSIM_LIB_PATH)
+        for name, at in OBSSIM_ARGTYPES.items():
+            f = getattr(_obssim_lib, name)
+            f.argtypes, f.restype = at, _INT
+    return _obssim_lib
 
 
 def osse_lib():
@@ -982,6 +1022,18 @@ class Context:
     def obsmake_noise(self, err, files, rand):
         """letkf_obsmake_noise_dev: files.err by element, files.dat += err * com_randn over all rows in file order."""
         self._check(osse_lib().letkf_obsmake_noise_dev(self._c, C.byref(err), C.byref(files), rand._r))
+
+    def obssim(self, params, fields, v3=None, v2=None, rec=None, sm3=None, sm2=None):
+        """letkf_obssim_dev (include/letkf_amd_obssim.h): obssim_cal for the fields.nmem states of `fields` (ObsopeFields) with the
+        lists and the radar of `params` (ObssimParams) into the device tensors v3 (float64, per state (nvar3, nlat, nlon, nlev)),
+        v2 (float64, (nvar2, nlat, nlon)) and rec (float32, (nrec, nlat, nlon)); any may be None, not all.  sm3 / sm2: elements
+        between two states (default: dense)."""
+        out = ObssimOut()
+        out.v3, out.v2, out.rec = _ptr(v3), _ptr(v2), _ptr(rec)
+        npl = fields.nlon * fields.nlat
+        out.sm3 = params.nvar3 * fields.nlev * npl if sm3 is None else sm3
+        out.sm2 = params.nvar2 * npl if sm2 is None else sm2
+        self._check(obssim_lib().letkf_obssim_dev(self._c, C.byref(params), C.byref(fields), C.byref(out)))
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),
