@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LETKF_AMD_LIB") or os.path.join(HERE, "lib", "libletkf_amd.so")   # override: profiling twin (make PROF=1)
 OSSE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_osse.so")   # the OSSE tools (include/letkf_amd_obsmake.h); links against the production library
 OBSSIM_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obssim.so")   # the model-to-observation simulator (include/letkf_amd_obssim.h); links against the production library too
+SUPEROB_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_superob.so")   # superob (include/letkf_amd_superob.h); links against the production library too
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -35,9 +36,10 @@ def build(force=False):
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_monit.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsmake.h"))
     srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obssim.h"))
+    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_superob.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = [LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH]
+    libs = [LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH]
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
@@ -505,9 +507,72 @@ OBSSIM_ARGTYPES = {
     "letkf_obssim_dev": [_VP, _VP, _VP, _VP],
 }
 
+
+
+class SuperobParams(C.Structure):
+    """letkf_superob_params (include/letkf_amd_superob.h): slot_off, elem_uid and the method tables are HOST arrays, the rows
+    device arrays"""
+    _fields_ = ([("nobs", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("elm", "typ", "lon", "lat", "lev", "dat", "err", "ri", "rj", "rk", "slot_off")] +
+                [(n, C.c_int32) for n in ("nlon", "nlat", "nlevx", "nslots", "nbslot", "nobtype", "nid", "surface_typ_mask")] +
+                [(n, C.c_void_p) for n in ("elem_uid", "method_g", "method_v", "method_t", "method_h")])
+
+
+class SuperobOut(C.Structure):
+    """letkf_superob_out (include/letkf_amd_superob.h): device arrays; slot_off_out, qc1, counts and obsnum may be NULL"""
+    _fields_ = [(n, C.c_void_p) for n in ("elm", "typ", "slot", "lon", "lat", "lev", "dat", "err", "ri", "rj", "rk", "i", "j", "k",
+                                          "nout", "slot_off_out", "qc1", "counts", "obsnum")]
+
+
+# ... and of the seventh companion header include/letkf_amd_superob.h, an eighth table: the entries are exported by the library
+# of superob (SUPEROB_LIB_PATH, superob_lib()), not by the other three
+SUPEROB_VERSION = 1
+SUPEROB_ARGTYPES = {
+    "letkf_superob_dev": [_VP, _VP, _VP],
+    "letkf_superob_default_methods": [_I32, _I32, _VP, _VP, _VP, _VP],
+    "letkf_superob_slot_priority": [_I32, _I32, _VP],
+}
+SUPEROB_SURFACE_TYPES = 0x4780   # report types 8, 9, 10, 11, 15 (scale/obs/superob.f90:289-291)
+
 _lib = None
 _osse_lib = None
 _obssim_lib = None
+_superob_lib = None
+
+
+def superob_lib():
+    """dlopen the library of superob, after the main one whose context it uses."""
+    global _superob_lib
+    if _superob_lib is None:
+        lib()
+        if not os.path.exists(SUPEROB_LIB_PATH):
+            raise LetkfError(f"{SUPEROB_LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
+        _superob_lib = C.CDLL(SUPEROB_LIB_PATH)
+        for name, at in SUPEROB_ARGTYPES.items():
+            f = getattr(_superob_lib, name)
+            f.argtypes, f.restype = at, _INT
+    return _superob_lib
+
+
+def superob_default_methods(nobtype, nid):
+    """letkf_superob_default_methods: the reference's hard-coded tables as four int32 arrays (nid, nobtype): g, v, t, h"""
+    import numpy as np
+    tabs = [np.zeros((nid, nobtype), dtype=np.int32) for _ in range(4)]
+    rc = superob_lib().letkf_superob_default_methods(nobtype, nid, *[t.ctypes.data for t in tabs])
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_superob_default_methods: {lib().letkf_amd_last_error().decode()}")
+    return tabs
+
+
+def superob_slot_priority(nslots, nbslot):
+    """letkf_superob_slot_priority: the 1-based slots, the nearest to nbslot first, the lower on ties"""
+    import numpy as np
+    out = np.zeros(max(nslots, 0), dtype=np.int32)
+    rc = superob_lib().letkf_superob_slot_priority(nslots, nbslot, out.ctypes.data)
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_superob_slot_priority: {lib().letkf_amd_last_error().decode()}")
+    return out
+
 
 
 def obssim_lib():
@@ -1034,6 +1099,46 @@ class Context:
         out.sm3 = params.nvar3 * fields.nlev * npl if sm3 is None else sm3
         out.sm2 = params.nvar2 * npl if sm2 is None else sm2
         self._check(obssim_lib().letkf_obssim_dev(self._c, C.byref(params), C.byref(fields), C.byref(out)))
+
+    def superob(self, rows, slot_off, grid, nbslot, elem_uid, methods, surface_typ_mask=SUPEROB_SURFACE_TYPES, obsnum=True,
+                out=None):
+        """letkf_superob_dev (include/letkf_amd_superob.h): superob's four stages over `rows`, a dict of device tensors elm, typ
+        (int32) and lon, lat, lev, dat, err, ri, rj, rk (float64).  slot_off: host int64 [nslots + 1]; grid = (nlon, nlat, nlevx);
+        elem_uid: host int32 [nid]; methods = (g, v, t, h), host int32 arrays (nid, nobtype).  Returns a dict of device tensors:
+        the output rows at capacity nobs, nout [1], slot_off_out, qc1, counts [7] and obsnum (4, nid, nobtype) (None with
+        obsnum=False).  Nothing is read back: slice by nout after a synchronisation of your own.  `out`: the dict to write into
+        (an entry that is None stays NULL where the header allows it)."""
+        import numpy as np
+        import torch
+        so = np.ascontiguousarray(slot_off, dtype=np.int64)
+        ids = np.ascontiguousarray(elem_uid, dtype=np.int32)
+        m = [np.ascontiguousarray(t, dtype=np.int32) for t in methods]
+        nid, nobtype = m[0].shape
+        n = rows["elm"].numel()
+        dev = rows["elm"].device
+        p = SuperobParams()
+        p.nobs = n
+        for name in ("elm", "typ", "lon", "lat", "lev", "dat", "err", "ri", "rj", "rk"):
+            setattr(p, name, _ptr(rows[name]))
+        p.slot_off = so.ctypes.data
+        p.nlon, p.nlat, p.nlevx = grid
+        p.nslots, p.nbslot, p.nobtype, p.nid = len(so) - 1, nbslot, nobtype, nid
+        p.surface_typ_mask = surface_typ_mask - (1 << 32) if surface_typ_mask >= 1 << 31 else surface_typ_mask
+        p.elem_uid = ids.ctypes.data
+        p.method_g, p.method_v, p.method_t, p.method_h = (t.ctypes.data for t in m)
+        if out is None:
+            out = {name: torch.zeros(n, dtype=torch.int32, device=dev) for name in ("elm", "typ", "slot", "i", "j", "k", "qc1")}
+            out.update({name: torch.zeros(n, dtype=torch.float64, device=dev)
+                        for name in ("lon", "lat", "lev", "dat", "err", "ri", "rj", "rk")})
+            out["nout"] = torch.zeros(1, dtype=torch.int64, device=dev)
+            out["slot_off_out"] = torch.zeros(len(so), dtype=torch.int64, device=dev)
+            out["counts"] = torch.zeros(7, dtype=torch.int64, device=dev)
+            out["obsnum"] = torch.zeros((4, nid, nobtype), dtype=torch.int64, device=dev) if obsnum else None
+        o = SuperobOut()
+        for name, _ in SuperobOut._fields_:
+            setattr(o, name, _ptr(out.get(name)))
+        self._check(superob_lib().letkf_superob_dev(self._c, C.byref(p), C.byref(o)))
+        return out
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),
