@@ -371,7 +371,8 @@ int letkf_das_columns_dev(letkf_ctx *ctx, const letkf_das_args *args, const letk
  *       v3dg(nlev,nlon,nlat,nv3d) (level-fastest).  The SCALE-RM constants are not in the reference tree
  *       (scale_const / scale_tracer): the caller passes them.  Variable order as common_scale.f90:36-51:
  *       0 rho/u, 1 rhou... : see letkf_state_consts.  state_trans_inv applies the positive-definite clamps of
- *       :1243-1250 first when requested.
+ *       :1243-1250 first when requested.  Every iv_* slot must lie in [0, nv3d); a call that breaks this, or has a
+ *       dimension below 1, is LETKF_E_INVALID and touches nothing.
  *     member field <-> point-major ensemble   grd_to_buf / buf_to_grd + the ALLTOALL of read_ens_mpi / write_ens_mpi
  *       (scale/common/common_mpi_scale.f90:1099-1274, :1428-1480): the horizontal points of a subdomain are dealt
  *       cyclically over np ranks (local point i of rank r is subdomain point r + np*i, ilon = mod(j,nlon)); this
@@ -385,7 +386,9 @@ typedef struct {
   int32_t iv_rho, iv_rhou, iv_rhov, iv_rhow, iv_rhot;   /* 0-based slots of the prognostic variables ...        */
   int32_t iv_u, iv_v, iv_w, iv_t, iv_p;                 /* ... and of the analysis variables that replace them */
   int32_t iv_q;                      /* first moisture variable; moisture = iv_q .. nv3d-1 */
-  int32_t positive_definite_q, positive_definite_qhyd;  /* POSITIVE_DEFINITE_Q / _QHYD (inverse only) */
+  int32_t positive_definite_q, positive_definite_qhyd;  /* POSITIVE_DEFINITE_Q / _QHYD (inverse only): _q clamps slot iv_q;
+                                        * _qhyd clamps the five slots iv_q+1 .. iv_q+5 (qc qr qi qs qg, common_scale.f90:1246-1248)
+                                        * and no other: a 7th or 8th species enters the thermodynamics as it is */
   int32_t reserved0;
 } letkf_state_consts;
 

@@ -1004,8 +1004,8 @@ int orc_obs_local_tied(const orc_search_tables *t, double ri, double rj, double 
 /* scale/common/common_scale.f90:1181-1224 and :1229-1280 */
 void orc_state_trans(const orc_state_consts *c, int nlev, int nlon, int nlat, int nv3d, double *v, int inverse) {
   const int64_t nxy = (int64_t)nlon * nlat, st = (int64_t)nlev * nxy;
-  if (inverse) {                                             /* :1243-1250 */
-    for (int n = c->iv_q; n < nv3d; ++n) {
+  if (inverse) {                                             /* :1243-1250: q, then qc qr qi qs qg and no further */
+    for (int n = c->iv_q; n < nv3d && n < c->iv_q + 6; ++n) {
       const int clamp = (n == c->iv_q) ? c->positive_definite_q : c->positive_definite_qhyd;
       if (clamp)
         for (int64_t e = 0; e < st; ++e) v[n * st + e] = fmax(v[n * st + e], 0.0);

@@ -119,8 +119,10 @@ int letkf_infl_init_dev(letkf_ctx* c, int64_t n, double* work3d, double infl_mul
 int letkf_state_trans_dev(letkf_ctx* c, const letkf_state_consts* k, int32_t nlev, int32_t nlon, int32_t nlat,
                           int32_t nv3d, double* v3dg, int32_t inverse) try {
   if (int rc = check_ctx(c)) return rc;
-  if (!k || !v3dg || nlev < 1 || nlon < 1 || nlat < 1) return fail(LETKF_E_INVALID, "bad argument");
+  if (!k || !v3dg || nlev < 1 || nlon < 1 || nlat < 1 || nv3d < 1) return fail(LETKF_E_INVALID, "bad argument");
   if (k->iv_q < 0 || k->iv_q >= nv3d || nv3d - k->iv_q > 8) return fail(LETKF_E_INVALID, "moisture range must be 1..8 variables");
+  for (const int32_t iv : {k->iv_rho, k->iv_rhou, k->iv_rhov, k->iv_rhow, k->iv_rhot, k->iv_u, k->iv_v, k->iv_w, k->iv_t, k->iv_p})
+    if (iv < 0 || iv >= nv3d) return fail(LETKF_E_INVALID, "a variable slot lies outside [0, nv3d)");
   HIP_TRY(letkf::launch_state_trans(*k, nlev, (long)nlon * nlat, nv3d, v3dg, inverse, c->stream));
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_state_trans_dev)
@@ -130,6 +132,7 @@ int letkf_member_points_dev(letkf_ctx* c, int32_t dir, int32_t nlev, int32_t nlo
                             int64_t sm, int64_t sv) try {
   if (int rc = check_ctx(c)) return rc;
   if (!v3dg || !x || np < 1 || rank < 0 || rank >= np || m < 0 || nij1 < 0) return fail(LETKF_E_INVALID, "bad argument");
+  if (nlev < 1 || nlon < 1 || nlat < 1 || nv3d < 1) return fail(LETKF_E_INVALID, "nlev, nlon, nlat and nv3d must be at least 1");
   const long nxy = (long)nlon * nlat;
   const long expect = (nxy - rank + np - 1) / np;               // points r, r+np, ... below nlon*nlat
   if (nij1 != expect) return fail(LETKF_E_INVALID, "nij1 does not match the cyclic share of this rank");

@@ -948,8 +948,9 @@ __global__ void state_trans_kernel(const letkf_state_consts C, int nlev, long nx
   const long stride = total;                       // distance between variables
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     double* p = v + e;
-    if (inverse) {                                 // :1243-1250 positive-definite clamps
-      for (int n = C.iv_q; n < nv3d; ++n) {
+    if (inverse) {                                 // :1243-1250 positive-definite clamps: q, and the five named
+      const int nclamp = min(nv3d, C.iv_q + 6);    // hydrometeors qc qr qi qs qg that follow it (:1246-1248), no further
+      for (int n = C.iv_q; n < nclamp; ++n) {
         const bool clamp = (n == C.iv_q) ? C.positive_definite_q != 0 : C.positive_definite_qhyd != 0;
         if (clamp) p[n * stride] = fmax(p[n * stride], 0.0);
       }

@@ -107,13 +107,16 @@ __global__ void additive_kernel(const int k, const int nv, const long npts, cons
 }
 
 // addinfl_weight (:813-838): nearest reflectivity observation, brute force over the ctype's rows as in the reference;
-// one wave per horizontal point, min by wave reduction (min is order-independent: bit-identical)
+// one wave per horizontal point, min by wave reduction (min is order-independent: bit-identical).  rdx*rdx + rdy*rdy is
+// rounded term by term as the reference's expression is: fused, the scaled distance moves by up to two ulps, which is
+// 1.8e-15 of the weight near the cut-off and can put a point on the other side of it.
 __global__ void __launch_bounds__(256) addinfl_weight_kernel(const long nij1, const double* __restrict__ rig,
                                                              const double* __restrict__ rjg, const long nob,
                                                              const double* __restrict__ ob_ri,
                                                              const double* __restrict__ ob_rj, const double dx,
                                                              const double dy, const double hori_loc,
                                                              const double cut2, double* __restrict__ w) {
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const long w0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((long)gridDim.x * blockDim.x) >> 6;
   for (long ij = w0; ij < nij1; ij += nw) {
