@@ -9,6 +9,7 @@ Because the directory name carries a hyphen, load it with `load_package()` from 
 (importlib under the module name `scale_letkf_amd`).
 """
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -29,17 +30,10 @@ class LetkfError(RuntimeError):
 def build(force=False):
     """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_interp_window.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsope.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_monit.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obsmake.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_obssim.h"))
-    srcs.append(os.path.join(HERE, "..", "include", "letkf_amd_superob.h"))
+    srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = [LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH]
+    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
@@ -386,7 +380,8 @@ class InterpArgs(C.Structure):
                 ("rjg", C.c_void_p), ("rlev", C.c_void_p), ("rz", C.c_void_p), ("nobs_coarse", C.c_void_p)]
 
 
-# ... and of the entries of the companion header include/letkf_amd_interp.h, a table of their own
+# ... and of the entries of the companion header include/letkf_amd_interp.h, a table of their own, as for every companion
+# header below (DESIGN.md section 17 lists what a new one touches)
 INTERP_VERSION = 1
 INTERP_ARGTYPES = {
     "letkf_interp_coarse_axis": [_I32, _I32, _VP, _VP],
@@ -400,7 +395,7 @@ class InterpWindow(C.Structure):
                 ("oj0", C.c_int32), ("onx", C.c_int32), ("ony", C.c_int32)]
 
 
-# ... and of the second companion header include/letkf_amd_interp_window.h, again a table of its own
+# ... and of the second companion header include/letkf_amd_interp_window.h, a table of its own
 INTERP_WINDOW_VERSION = 1
 INTERP_WINDOW_ARGTYPES = {
     "letkf_interp_window_axis": [_I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP],
@@ -424,7 +419,7 @@ class ObsopeParams(C.Structure):
                                            "rj_off")])
 
 
-# ... and of the third companion header include/letkf_amd_obsope.h, once more a table of its own
+# ... and of the third companion header include/letkf_amd_obsope.h, a table of its own
 OBSOPE_VERSION = 1
 OBSOPE_ARGTYPES = {
     "letkf_obsope_dev": [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _I64],
@@ -449,7 +444,7 @@ class Obsdep(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("set", "idx", "qc", "omb", "oma")]
 
 
-# ... and of the fourth companion header include/letkf_amd_monit.h, a fifth table
+# ... and of the fourth companion header include/letkf_amd_monit.h, a table of its own
 MONIT_VERSION = 1
 MONIT_ARGTYPES = {
     "letkf_state_to_history_dev": [_VP, _VP, _VP, _VP, _VP],
@@ -471,7 +466,7 @@ class ObsmakeErr(C.Structure):
                                           "obserr_radar_ref", "obserr_radar_vr")]
 
 
-# ... and of the fifth companion header include/letkf_amd_obsmake.h, a sixth table: these entries are exported by the library
+# ... and of the fifth companion header include/letkf_amd_obsmake.h, a table of its own: these entries are exported by the library
 # of the OSSE tools (OSSE_LIB_PATH, osse_lib()), not by the main one
 OBSMAKE_VERSION = 1
 OBSMAKE_ARGTYPES = {
@@ -500,7 +495,7 @@ class ObssimOut(C.Structure):
     _fields_ = [("v3", C.c_void_p), ("v2", C.c_void_p), ("rec", C.c_void_p), ("sm3", C.c_int64), ("sm2", C.c_int64)]
 
 
-# ... and of the sixth companion header include/letkf_amd_obssim.h, a seventh table: the entry is exported by the library of the
+# ... and of the sixth companion header include/letkf_amd_obssim.h, a table of its own: the entry is exported by the library of the
 # simulator (OBSSIM_LIB_PATH, obssim_lib()), not by the other two
 OBSSIM_VERSION = 1
 OBSSIM_ARGTYPES = {
@@ -524,7 +519,7 @@ class SuperobOut(C.Structure):
                                           "nout", "slot_off_out", "qc1", "counts", "obsnum")]
 
 
-# ... and of the seventh companion header include/letkf_amd_superob.h, an eighth table: the entries are exported by the library
+# ... and of the seventh companion header include/letkf_amd_superob.h, a table of its own: the entries are exported by the library
 # of superob (SUPEROB_LIB_PATH, superob_lib()), not by the other three
 SUPEROB_VERSION = 1
 SUPEROB_ARGTYPES = {
@@ -534,24 +529,51 @@ SUPEROB_ARGTYPES = {
 }
 SUPEROB_SURFACE_TYPES = 0x4780   # report types 8, 9, 10, 11, 15 (scale/obs/superob.f90:289-291)
 
-_lib = None
-_osse_lib = None
-_obssim_lib = None
-_superob_lib = None
+_libs = {}
+
+
+def _load(path, tables, restypes={}):
+    """dlopen the library at path, once, and type every entry of the tables: a declared symbol that is missing raises
+    AttributeError, and every entry returns int but those restypes names."""
+    if path not in _libs:
+        if not os.path.exists(path):
+            raise LetkfError(f"{path} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
+        loaded = C.CDLL(path)
+        for table in tables:
+            for name, at in table.items():
+                f = getattr(loaded, name)
+                f.argtypes, f.restype = at, restypes.get(name, _INT)
+        _libs[path] = loaded
+    return _libs[path]
+
+
+def lib():
+    """dlopen the library.  `import torch` first when torch is in the process so both share one HIP runtime
+    (torch's libamdhip64.so and /opt/rocm's carry the same SONAME; the first one loaded wins)."""
+    if LIB_PATH not in _libs:
+        try:            # make torch's HIP runtime the process's one BEFORE ours binds /opt/rocm's copy: loaded the other
+            import torch  # noqa: F401  way round, the two runtimes coexist and ours sees no device
+        except ImportError:
+            pass
+    return _load(LIB_PATH, (ARGTYPES, INTERP_ARGTYPES, INTERP_WINDOW_ARGTYPES, OBSOPE_ARGTYPES, MONIT_ARGTYPES), RESTYPES)
+
+
+def osse_lib():
+    """dlopen the library of the OSSE tools, after the main one whose context and operator it uses."""
+    lib()
+    return _load(OSSE_LIB_PATH, (OBSMAKE_ARGTYPES,))
+
+
+def obssim_lib():
+    """dlopen the library of the simulator, after the main one whose context it uses."""
+    lib()
+    return _load(OBSSIM_LIB_PATH, (OBSSIM_ARGTYPES,))
 
 
 def superob_lib():
     """dlopen the library of superob, after the main one whose context it uses."""
-    global _superob_lib
-    if _superob_lib is None:
-        lib()
-        if not os.path.exists(SUPEROB_LIB_PATH):
-            raise LetkfError(f"{SUPEROB_LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
-        _superob_lib = C.CDLL(SUPEROB_LIB_PATH)
-        for name, at in SUPEROB_ARGTYPES.items():
-            f = getattr(_superob_lib, name)
-            f.argtypes, f.restype = at, _INT
-    return _superob_lib
+    lib()
+    return _load(SUPEROB_LIB_PATH, (SUPEROB_ARGTYPES,))
 
 
 def superob_default_methods(nobtype, nid):
@@ -572,35 +594,6 @@ def superob_slot_priority(nslots, nbslot):
     if rc != LETKF_OK:
         raise LetkfError(f"letkf_superob_slot_priority: {lib().letkf_amd_last_error().decode()}")
     return out
-
-
-
-def obssim_lib():
-    """dlopen the library of the simulator, after the main one whose context it uses."""
-    global _obssim_lib
-    if _obssim_lib is None:
-        lib()
-        if not os.path.exists(OBSSIM_LIB_PATH):
-            raise LetkfError(f"{OBSSIM_LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
-        _obssim_lib = C.CDLL(OBSSIM_LIB_PATH)
-        for name, at in OBSSIM_ARGTYPES.items():
-            f = getattr(_obssim_lib, name)
-            f.argtypes, f.restype = at, _INT
-    return _obssim_lib
-
-
-def osse_lib():
-    """dlopen the library of the OSSE tools, after the main one whose context and operator it uses."""
-    global _osse_lib
-    if _osse_lib is None:
-        lib()
-        if not os.path.exists(OSSE_LIB_PATH):
-            raise LetkfError(f"{OSSE_LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
-        _osse_lib = C.CDLL(OSSE_LIB_PATH)
-        for name, at in OBSMAKE_ARGTYPES.items():
-            f = getattr(_osse_lib, name)
-            f.argtypes, f.restype = at, _INT
-    return _osse_lib
 
 
 class Rand:
@@ -636,25 +629,6 @@ class Rand:
         out = np.zeros(max(int(n), 0), dtype=np.float64)
         self._check(self._l.letkf_rand_res53(self._r, n, out.ctypes.data_as(C.c_void_p)))
         return out
-
-
-def lib():
-    """dlopen the library.  `import torch` first when torch is in the process so both share one HIP runtime
-    (torch's libamdhip64.so and /opt/rocm's carry the same SONAME; the first one loaded wins)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise LetkfError(f"{LIB_PATH} not built: run `make -C scale-letkf_amd` (no CPU fallback exists)")
-        try:            # make torch's HIP runtime the process's one BEFORE ours binds /opt/rocm's copy: loaded the other
-            import torch  # noqa: F401  way round, the two runtimes coexist and ours sees no device
-        except ImportError:
-            pass
-        _lib = C.CDLL(LIB_PATH)
-        for name, at in (list(ARGTYPES.items()) + list(INTERP_ARGTYPES.items()) + list(INTERP_WINDOW_ARGTYPES.items()) +
-                         list(OBSOPE_ARGTYPES.items()) + list(MONIT_ARGTYPES.items())):
-            f = getattr(_lib, name)  # raises AttributeError when a declared symbol is missing
-            f.argtypes, f.restype = at, RESTYPES.get(name, _INT)
-    return _lib
 
 
 def interp_coarse_axis(n, stride):

@@ -1,51 +1,39 @@
-"""No C++ exception leaves a C entry: every entry the headers declare is defined once, in one of the letkf_api*.hip units, as a
-function-try-block that LETKF_ENTRY_END closes (read from the sources), and the barrier behind that macro maps what is thrown
+"""No C++ exception leaves a C entry: every entry the headers declare is defined once -- the main header's in one of the
+letkf_api*.hip units, the companions' where test_companion_bindings.py names them -- as a function-try-block that LETKF_ENTRY_END
+closes (read from the sources), and the barrier behind that macro maps what is thrown
 to LETKF_E_INVALID with its text (a stand-alone host program built from letkf_api_error.hip alone).  No GPU, no library."""
-import glob
 import os
 import re
 import subprocess
 import textwrap
 
 import _header
-from __graft_entry__ import PKG_DIR, ROOT
+from __graft_entry__ import PKG_DIR
+from test_companion_bindings import COMPANIONS
 
 CSRC = os.path.join(PKG_DIR, "csrc")
 # the two entries without a barrier: they take no context, allocate nothing and are what a caller reads after a failure
 EXEMPT = {"letkf_amd_abi_version", "letkf_amd_last_error"}
 
 
-def _units():
-    return {os.path.basename(p): open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "letkf_api*.hip")))}
-
-
-def _definitions():
-    """{entry: [(unit, head, close), ...]}: every definition of a letkf_* function at file level in the units -- what stands
-    between its parameter list and its body, and the line that closes the body"""
-    out = {}
-    for unit, src in _units().items():
-        for m in re.finditer(r"^(?:int|void|const char\*) (letkf_\w+)\(([^)]*)\)([^;{]*)\{", src, flags=re.M):
-            close = re.compile(r"^\}.*$", flags=re.M).search(src, m.end()).group(0)
-            out.setdefault(m.group(1), []).append((unit, m.group(3).strip(), close.strip()))
-    return out
-
-
 def test_every_entry_is_defined_once_behind_the_barrier():
-    units = _units()
-    assert len(units) >= 7, sorted(units)
-    assert not [u for u, src in units.items() if "__global__" in src], "a kernel in a unit of the host API"
-    defs = _definitions()
-    declared = set(_header.entries())
-    for extra in ("letkf_amd_interp.h", "letkf_amd_interp_window.h", "letkf_amd_obsope.h"):   # entries of the other headers
-        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", extra)).read(), flags=re.S)
-        declared |= {n for n in re.findall(r"^int\s+(letkf_\w+)\s*\(", text, flags=re.M) if n in defs}
-    assert len(_header.entries()) == 59 and EXEMPT <= declared
-    missing = sorted(declared - set(defs))
-    assert not missing, f"declared, but defined in no letkf_api*.hip unit: {missing}"
-    assert not sorted(set(defs) - declared), f"defined as an entry, but declared in no header: {sorted(set(defs) - declared)}"
-    for name in sorted(declared):
+    defs = _header.definitions()
+    api = {u for where in defs.values() for u, _, _ in where if u.startswith("letkf_api")}
+    assert len(api) >= 7, sorted(api)
+    for unit in api:
+        assert "__global__" not in open(os.path.join(CSRC, unit)).read(), f"{unit}: a kernel in a unit of the host API"
+    main = set(_header.entries())
+    assert len(main) == 59 and EXEMPT <= main
+    # the companions' entries, with their units, are test_companion_bindings.py's; here: they and the main header's are all there is
+    companions = set().union(*(c.entries for c in COMPANIONS.values()))
+    assert not main & companions
+    missing = sorted((main | companions) - set(defs))
+    assert not missing, f"declared, but defined in no unit: {missing}"
+    assert not sorted(set(defs) - main - companions), f"defined as an entry, but declared in no header: {sorted(set(defs) - main - companions)}"
+    for name in sorted(main):
         assert len(defs[name]) == 1, (name, [u for u, _, _ in defs[name]])
         unit, head, close = defs[name][0]
+        assert unit in api, (name, unit)
         if name in EXEMPT:
             assert head == "" and unit == "letkf_api_error.hip", (name, unit, head)
             continue

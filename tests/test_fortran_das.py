@@ -32,29 +32,10 @@ def build_fortran():
     subprocess.check_call(["make", "-C", FDIR], stdout=subprocess.DEVNULL)
 
 
-def f_types(src):
-    out = {}
-    for m in re.finditer(r"TYPE, BIND\(C\) :: (\w+)\n(.*?)END TYPE", src, flags=re.S):
-        fields = []
-        body = re.sub(r"&\s*\n", " ", m.group(2))
-        for line in body.splitlines():
-            line = line.split("!")[0]
-            if "::" not in line:
-                continue
-            decl, names = line.split("::")
-            kind = ("i32" if "c_int32_t" in decl else "i64" if "c_int64_t" in decl else "f64" if "c_double" in decl
-                    else "ptr" if "c_ptr" in decl else None)
-            assert kind, line
-            for n in names.split(","):
-                fields.append((kind, re.sub(r"\(\d+\)", "", n.strip())))
-        out[m.group(1)] = fields
-    return out
-
-
 @pytest.mark.skipif(not HAVE_FC, reason="amdflang not present")
 def test_every_bind_c_type_mirrors_its_c_struct():
     src = open(os.path.join(FDIR, "letkf_amd_api.f90")).read()
-    cs, fs = _header.c_structs(), f_types(src)
+    cs, fs = _header.c_structs(), _header.fortran_types(src)
     # every struct of the C ABI has its Fortran mirror ...
     assert set(cs) == set(fs), (sorted(set(cs) - set(fs)), sorted(set(fs) - set(cs)))
     for name in cs:                 # ... field by field, in the C order, with the C kinds

@@ -125,10 +125,9 @@ def test_mesh_dims_every_branch(nlon, nlat):
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/amdflang"), reason="amdflang not present")
 def test_setobs_structs_mirror_bind_c():
-    from _header import c_structs
-    from test_fortran_das import f_types
+    from _header import c_structs, fortran_types
     src = open(os.path.join(ROOT, "scale-letkf_amd", "fortran", "letkf_amd_api.f90")).read()
-    cs, fs = c_structs(), f_types(src)
+    cs, fs = c_structs(), fortran_types(src)
     for name in ("letkf_setobs_params", "letkf_obs_file_rows", "letkf_obs_table_info"):
         assert fs[name] == cs[name], name
     for entry in ("letkf_set_obs_local_dev", "letkf_set_obs_finish_dev", "letkf_set_obs_dev", "letkf_obs_mesh_dims",
