@@ -415,6 +415,34 @@ int letkf_ens_spread_dev(letkf_ctx *ctx, int32_t k, int32_t nv, int64_t npts, co
  *       extended-subdomain plan :922-976 and copy into obsda_sort :1036-1100
  *     Integer results (qc, counts, keys, ac_ext, row map) are identical to the reference's; the departures use the
  *     same sequential member sum and are bit-identical too.
+ *
+ *     kld: any kld >= MEMBER (+1 with DET_RUN); the columns beyond are neither read nor changed.  Up to the kld of which 64
+ *     rows fit in LDS (kld <= 319 at 160 KiB) the departure runs the kernel it always ran.  Longer rows go through tiles of 16
+ *     rows, and rows of which not even 16 fit (kld >= 1280) are walked where they lie in global memory: the same results bit
+ *     for bit, at a speed nobody has measured.
+ *
+ *     REFUSED with LETKF_E_INVALID, the message naming the argument, before anything is launched or written unless said
+ *     otherwise:
+ *       letkf_obs_departure_dev    p NULL; nobs < 0; with nobs > 0: elm, dat, err, ensval, val or qc NULL, p->member < 1,
+ *                                  kld < MEMBER (+1 with DET_RUN).  nobs = 0 returns LETKF_OK and reads no pointer.
+ *       letkf_obs_mesh_sort_dev    mesh, nsorted or n_cell NULL; nobs < 0 or >= 2^31; mesh->nctype, nlon or nlat < 1; mesh->ngrd_i
+ *                                  or ngrd_j NULL or holding a value < 1; with nobs > 0: ctype, ri, rj, qc or key NULL.
+ *                                  A row with qc = 0 whose ctype lies outside 0 .. nctype-1: found on the device and reported with
+ *                                  the count's read-back; the row touches nothing, key and *nsorted are not written, and n_cell
+ *                                  holds the counts of the OTHER accepted rows (not a result: sort again with valid types).
+ *                                  The ctype of a row with qc /= 0 is not read.
+ *       letkf_obs_halo_plan_dev    layout, nobstotal, n_all or ac_ext NULL; nctype, nprocs or prc_num_x < 1; prc_num_x not
+ *                                  dividing nprocs; myrank outside 0 .. nprocs-1; ngrd_i, ngrd_j, ngrdsch_i or ngrdsch_j NULL, an
+ *                                  ngrd value < 1, an ngrdsch value < 0; cap < 0; src_row NULL with cap > 0; after the download
+ *                                  of n_all, on the host: a negative count, a total of 2^31 rows or more.
+ *                                  cap < nobstotal: *nobstotal says what it takes and ac_ext is written; src_row is not.
+ *       letkf_obs_gather_rows_dev  nrows or ncols < 0; with rows and columns: src_row, src or dst NULL, ld_src or ld_dst < ncols.
+ *       letkf_obs_gather_i32_dev   nrows < 0; with rows: src_row, src or dst NULL.
+ *     The two gathers do NOT check the entries of src_row: a row number outside src is the caller's error and reads outside it.
+ *     They are meant for the src_row of letkf_obs_halo_plan_dev, whose entries lie in 0 .. total of n_all - 1.
+ *     Coordinates: the mesh cell is CEILING((r - halo - 0.5) * ngrd / n) clamped to 1 .. ngrd as a double, before the conversion
+ *     to an integer, so it is defined for every double and is the reference's for every coordinate the reference defines: NaN
+ *     and -inf fall in cell 1, +inf and anything beyond the subdomain in the last cell.
  *-------------------------------------------------------------------------*/
 typedef struct {
   int32_t member;                 /* MEMBER */
@@ -458,7 +486,8 @@ typedef struct {
 
 /* ctype[n]: 0-based combined type of row n (ctype_elmtyp(uid_obs(elm), typ) - 1); ri, rj: global grid coordinates.
  * n_cell (dev, OUT): per ctype [ngrd_j][ngrd_i] counts of accepted rows, ctypes concatenated (obsgrd%n(:,:,myrank));
- * key (dev, OUT, [nobs]): key[0 .. *nsorted) = 0-based row numbers in (ctype, j, i, row) order (obsda%key).
+ * key (dev, OUT, [nobs]): key[0 .. *nsorted) = 0-based row numbers in (ctype, j, i, row) order (obsda%key); the entries
+ * from *nsorted on are not written.
  * Synchronises the stream (the count goes back to the host). */
 int letkf_obs_mesh_sort_dev(letkf_ctx *ctx, const letkf_mesh *mesh, int64_t nobs, const int32_t *ctype,
                             const double *ri, const double *rj, const int32_t *qc, int32_t *n_cell, int32_t *key,
@@ -617,6 +646,25 @@ int letkf_members_alltoall_dev(letkf_ctx *ctx, void *nccl_comm, int32_t nranks, 
  *     Observation files and obsda are read by the host (read_obs_all / obsope, out of scope); the observation files
  *     are the SAME on every rank (as in the reference: every rank reads them all).  Not covered: the member-sliced
  *     ensval of nprocs_e > 1 (:994-1004), LOG_LEVEL >= 3 prints, DEPARTURE_STAT_H08, NOBS_OUT files.
+ *
+ *     kld: any kld with MEMBER (+1 with DET_RUN) <= kld < 2^20; the departure takes the routes of section 5 (beyond kld = 319
+ *     at 160 KiB of LDS: correct and unmeasured).
+ *
+ *     REFUSED with LETKF_E_INVALID, the message naming the argument:
+ *       letkf_set_obs_local_dev   before anything is launched or written but *tab = NULL: tab, p, qcp or files NULL; nobtype
+ *                                 outside 1 .. 32; one of the five per-type arrays of p NULL; nlon, nlat, nprocs or prc_num_x < 1;
+ *                                 prc_num_x not dividing nprocs; myrank outside 0 .. nprocs-1; dx or dy not positive (NaN
+ *                                 included); files->nfile < 0; files->off NULL, not starting at 0 or decreasing; nobs < 0 or
+ *                                 >= 2^31; qcp->member < 1; kld too small or >= 2^20; with nobs > 0: set, idx, qc or ensval NULL,
+ *                                 nfile = 0, h08 = 1 without qcp->h08_lev; with file rows: one of the seven arrays of files NULL.
+ *                                 After the pre-processing of the files, qc and ensval still as they came, no table: a file
+ *                                 row whose elm is none of the 16 ids or whose typ lies outside 1 .. nobtype; a sorting mesh
+ *                                 without cells; an obsda row whose set lies outside 1 .. nfile or whose idx outside its file.
+ *       letkf_set_obs_dev         the same, and p->nprocs /= 1.
+ *       letkf_set_obs_finish_dev  tab NULL or already finished; n_all NULL; nrecv < 0; recv NULL with nrecv > 0; a negative
+ *                                 count in n_all, a total of 2^31 or more, or one that differs from nrecv.  The table stays as the
+ *                                 local half left it and may be finished with the right arguments.
+ *       letkf_obs_table_*         tab (info, tables, varloc) NULL; search, set_varloc and download before the finish half.
  *-------------------------------------------------------------------------*/
 #define LETKF_NID_OBS 16   /* nid_obs, common_nml.f90:21: uid_obs() numbers the 16 element ids of common_obs_scale.f90:74-77 */
 

@@ -1158,14 +1158,13 @@ void orc_obs_departure(const orc_qc_params *p, int64_t nobs, const int32_t *elm,
 static void orc_ij_obsgrd(const orc_mesh *m, int ic, double ri, double rj, int *ogi, int *ogj) {
   const double ril = ri - (double)(m->rank_i * m->nlon);
   const double rjl = rj - (double)(m->rank_j * m->nlat);
-  int i = (int)ceil((ril - (double)m->ihalo - 0.5) * (double)m->ngrd_i[ic] / (double)m->nlon);
-  int j = (int)ceil((rjl - (double)m->jhalo - 0.5) * (double)(m->fix_ij_obsgrd ? m->ngrd_j[ic] : m->ngrd_i[ic]) / (double)m->nlat);
-  if (i < 1) i = 1;
-  if (i > m->ngrd_i[ic]) i = m->ngrd_i[ic];
-  if (j < 1) j = 1;
-  if (j > m->ngrd_j[ic]) j = m->ngrd_j[ic];
-  *ogi = i;
-  *ogj = j;
+  /* the clamps of :768-771 taken as doubles, before the conversion: CEILING of a NaN, an infinity or a magnitude beyond 2^31 is
+   * undefined there and here; so NaN and -inf go to cell 1, +inf to the last cell, and no in-range input changes */
+  const int gi = m->ngrd_i[ic], gj = m->ngrd_j[ic];
+  const double ci = ceil((ril - (double)m->ihalo - 0.5) * (double)gi / (double)m->nlon);
+  const double cj = ceil((rjl - (double)m->jhalo - 0.5) * (double)(m->fix_ij_obsgrd ? gj : gi) / (double)m->nlat);
+  *ogi = !(ci >= 1.0) ? 1 : (ci > (double)gi ? gi : (int)ci);
+  *ogj = !(cj >= 1.0) ? 1 : (cj > (double)gj ? gj : (int)cj);
 }
 
 int64_t orc_obs_mesh_sort(const orc_mesh *m, int64_t nobs, const int32_t *ctype, const double *ri, const double *rj,

@@ -5,36 +5,55 @@
 
 using namespace letkf::api;
 
+namespace {
+struct NamedPtr {
+  const void* p;
+  const char* name;
+};
+// LETKF_E_INVALID naming the first NULL pointer of the list, or 0
+int first_null(std::initializer_list<NamedPtr> l) {
+  for (const NamedPtr& a : l)
+    if (!a.p) return fail(LETKF_E_INVALID, std::string(a.name) + " is NULL");
+  return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int letkf_obs_departure_dev(letkf_ctx* c, const letkf_qc_params* p, int64_t nobs, const int32_t* elm, const double* dat,
                             const double* err, double* ensval, int64_t kld, double* val, int32_t* qc) try {
   if (int rc = check_ctx(c)) return rc;
-  if (!p || nobs < 0) return fail(LETKF_E_INVALID, "params is NULL or nobs < 0");
+  if (!p) return fail(LETKF_E_INVALID, "p is NULL");
+  if (nobs < 0) return fail(LETKF_E_INVALID, "nobs is negative");
   if (nobs == 0) return LETKF_OK;
-  if (!elm || !dat || !err || !ensval || !val || !qc) return fail(LETKF_E_INVALID, "an observation array is NULL");
-  if (p->member < 1 || kld < p->member + (p->det_run ? 1 : 0))
-    return fail(LETKF_E_INVALID, "kld must hold MEMBER (+1 with DET_RUN) columns");
-  if ((size_t)64 * (size_t)(kld | 1) * sizeof(double) > c->lds_max) return fail(LETKF_E_INVALID, "kld too large");
-  HIP_TRY(letkf::launch_obs_departure(*p, nobs, elm, dat, err, ensval, kld, val, qc, c->num_cu, c->stream));
+  if (int rc = first_null({{elm, "elm"}, {dat, "dat"}, {err, "err"}, {ensval, "ensval"}, {val, "val"}, {qc, "qc"}})) return rc;
+  if (p->member < 1) return fail(LETKF_E_INVALID, "p->member must be positive");
+  if (kld < p->member + (p->det_run ? 1 : 0)) return fail(LETKF_E_INVALID, "kld must hold MEMBER (+1 with DET_RUN) columns");
+  HIP_TRY(letkf::launch_obs_departure(*p, nobs, elm, dat, err, ensval, kld, val, qc, c->num_cu, c->lds_max, c->stream));
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_departure_dev)
 
 int letkf_obs_mesh_sort_dev(letkf_ctx* c, const letkf_mesh* m, int64_t nobs, const int32_t* ctype, const double* ri,
                             const double* rj, const int32_t* qc, int32_t* n_cell, int32_t* key, int64_t* nsorted) try {
   if (int rc = check_ctx(c)) return rc;
-  if (!m || nobs < 0 || !nsorted) return fail(LETKF_E_INVALID, "mesh / nsorted is NULL or nobs < 0");
-  if (m->nctype < 1 || !m->ngrd_i || !m->ngrd_j || m->nlon < 1 || m->nlat < 1)
-    return fail(LETKF_E_INVALID, "bad mesh description");
-  if (nobs > 0 && (!ctype || !ri || !rj || !qc || !key)) return fail(LETKF_E_INVALID, "an observation array is NULL");
-  if (!n_cell) return fail(LETKF_E_INVALID, "n_cell is NULL");
-  if (nobs >= (1LL << 31)) return fail(LETKF_E_INVALID, "more than 2^31 local observations");
+  if (int rc = first_null({{m, "mesh"}, {nsorted, "nsorted"}, {n_cell, "n_cell"}})) return rc;
+  if (nobs < 0 || nobs >= (1LL << 31)) return fail(LETKF_E_INVALID, "nobs outside 0..2^31-1");
+  if (m->nctype < 1) return fail(LETKF_E_INVALID, "mesh->nctype must be positive");
+  if (int rc = first_null({{m->ngrd_i, "mesh->ngrd_i"}, {m->ngrd_j, "mesh->ngrd_j"}})) return rc;
+  if (m->nlon < 1) return fail(LETKF_E_INVALID, "mesh->nlon must be positive");
+  if (m->nlat < 1) return fail(LETKF_E_INVALID, "mesh->nlat must be positive");
+  for (int ic = 0; ic < m->nctype; ++ic)
+    if (m->ngrd_i[ic] < 1 || m->ngrd_j[ic] < 1) return fail(LETKF_E_INVALID, "mesh->ngrd_i / ngrd_j: an empty mesh");
+  if (nobs > 0)
+    if (int rc = first_null({{ctype, "ctype"}, {ri, "ri"}, {rj, "rj"}, {qc, "qc"}, {key, "key"}})) return rc;
   size_t need = 0;
   long ns = 0;
-  HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, nullptr, &need, c->num_cu, c->stream));
+  bool bad = false;
+  HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, &bad, nullptr, &need, c->num_cu, c->stream));
   if (int rc = grow(c, &c->scratch, need)) return rc;
   size_t have = c->scratch.cap;
-  HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, c->scratch.p, &have, c->num_cu, c->stream));
+  HIP_TRY(letkf::obs_mesh_sort(*m, nobs, ctype, ri, rj, qc, n_cell, key, &ns, &bad, c->scratch.p, &have, c->num_cu, c->stream));
+  if (bad) return fail(LETKF_E_INVALID, "ctype: a row with qc = 0 has a value outside 0..nctype-1");
   *nsorted = ns;
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_mesh_sort_dev)
@@ -42,15 +61,26 @@ int letkf_obs_mesh_sort_dev(letkf_ctx* c, const letkf_mesh* m, int64_t nobs, con
 int letkf_obs_halo_plan_dev(letkf_ctx* c, const letkf_halo_layout* l, const int32_t* n_all, int32_t* ac_ext,
                             int32_t* src_row, int64_t cap, int64_t* nobstotal) try {
   if (int rc = check_ctx(c)) return rc;
-  if (!l || !nobstotal || !n_all || !ac_ext) return fail(LETKF_E_INVALID, "a required pointer is NULL");
-  if (l->nctype < 1 || l->nprocs < 1 || l->prc_num_x < 1 || l->myrank < 0 || l->myrank >= l->nprocs ||
-      l->nprocs % l->prc_num_x != 0 || !l->ngrd_i || !l->ngrd_j || !l->ngrdsch_i || !l->ngrdsch_j)
-    return fail(LETKF_E_INVALID, "bad rank layout / mesh description");
+  if (int rc = first_null({{l, "layout"}, {nobstotal, "nobstotal"}, {n_all, "n_all"}, {ac_ext, "ac_ext"}})) return rc;
+  if (l->nctype < 1) return fail(LETKF_E_INVALID, "layout->nctype must be positive");
+  if (l->nprocs < 1) return fail(LETKF_E_INVALID, "layout->nprocs must be positive");
+  if (l->prc_num_x < 1 || l->nprocs % l->prc_num_x != 0)
+    return fail(LETKF_E_INVALID, "layout->prc_num_x must be positive and divide nprocs");
+  if (l->myrank < 0 || l->myrank >= l->nprocs) return fail(LETKF_E_INVALID, "layout->myrank outside 0..nprocs-1");
+  if (int rc = first_null({{l->ngrd_i, "layout->ngrd_i"}, {l->ngrd_j, "layout->ngrd_j"}, {l->ngrdsch_i, "layout->ngrdsch_i"},
+                           {l->ngrdsch_j, "layout->ngrdsch_j"}}))
+    return rc;
+  for (int ic = 0; ic < l->nctype; ++ic) {
+    if (l->ngrd_i[ic] < 1 || l->ngrd_j[ic] < 1) return fail(LETKF_E_INVALID, "layout->ngrd_i / ngrd_j: an empty mesh");
+    if (l->ngrdsch_i[ic] < 0 || l->ngrdsch_j[ic] < 0) return fail(LETKF_E_INVALID, "layout->ngrdsch_i / ngrdsch_j is negative");
+  }
+  if (cap < 0) return fail(LETKF_E_INVALID, "cap is negative");
   if (cap > 0 && !src_row) return fail(LETKF_E_INVALID, "src_row is NULL");
-  long nt = 0;
-  hipError_t e = letkf::obs_halo_plan(*l, n_all, ac_ext, src_row, cap, &nt, c->num_cu, c->stream);
-  *nobstotal = nt;
-  if (e == hipErrorInvalidValue && nt > cap) return fail(LETKF_E_INVALID, "src_row capacity is smaller than nobstotal");
+  long nt = -1;                                          // stays so when a count of n_all is refused: nothing is written then
+  const char* refused = nullptr;
+  hipError_t e = letkf::obs_halo_plan(*l, n_all, ac_ext, src_row, cap, &nt, &refused, c->num_cu, c->stream);
+  if (nt >= 0) *nobstotal = nt;
+  if (refused) return fail(LETKF_E_INVALID, refused);
   HIP_TRY(e);
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_halo_plan_dev)
@@ -58,18 +88,21 @@ int letkf_obs_halo_plan_dev(letkf_ctx* c, const letkf_halo_layout* l, const int3
 int letkf_obs_gather_rows_dev(letkf_ctx* c, int64_t nrows, const int32_t* src_row, int32_t ncols, const double* src,
                               int64_t ld_src, double* dst, int64_t ld_dst) try {
   if (int rc = check_ctx(c)) return rc;
-  if (nrows < 0 || ncols < 0) return fail(LETKF_E_INVALID, "negative size");
+  if (nrows < 0) return fail(LETKF_E_INVALID, "nrows is negative");
+  if (ncols < 0) return fail(LETKF_E_INVALID, "ncols is negative");
   if (nrows == 0 || ncols == 0) return LETKF_OK;
-  if (!src_row || !src || !dst || ld_src < ncols || ld_dst < ncols) return fail(LETKF_E_INVALID, "bad argument");
+  if (int rc = first_null({{src_row, "src_row"}, {src, "src"}, {dst, "dst"}})) return rc;
+  if (ld_src < ncols) return fail(LETKF_E_INVALID, "ld_src is smaller than ncols");
+  if (ld_dst < ncols) return fail(LETKF_E_INVALID, "ld_dst is smaller than ncols");
   HIP_TRY(letkf::launch_gather_rows(nrows, src_row, ncols, src, ld_src, dst, ld_dst, c->num_cu, c->stream));
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_gather_rows_dev)
 
 int letkf_obs_gather_i32_dev(letkf_ctx* c, int64_t nrows, const int32_t* src_row, const int32_t* src, int32_t* dst) try {
   if (int rc = check_ctx(c)) return rc;
-  if (nrows < 0) return fail(LETKF_E_INVALID, "negative size");
+  if (nrows < 0) return fail(LETKF_E_INVALID, "nrows is negative");
   if (nrows == 0) return LETKF_OK;
-  if (!src_row || !src || !dst) return fail(LETKF_E_INVALID, "bad argument");
+  if (int rc = first_null({{src_row, "src_row"}, {src, "src"}, {dst, "dst"}})) return rc;
   HIP_TRY(letkf::launch_gather_i32(nrows, src_row, src, dst, c->num_cu, c->stream));
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_gather_i32_dev)
@@ -78,14 +111,24 @@ int letkf_obs_mesh_dims(int32_t nctype, const int32_t* typ_ctype, const double* 
                         const double* obs_sort_grid_spacing, const int32_t* max_nobs_per_grid, const double* obs_min_spacing,
                         double dx, double dy, int32_t nlon, int32_t nlat, int32_t* ngrd_i, int32_t* ngrd_j, double* grdspc_i,
                         double* grdspc_j, int32_t* ngrdsch_i, int32_t* ngrdsch_j, int32_t* ngrdext_i, int32_t* ngrdext_j) try {
-  if (nctype < 0 || nobtype < 1 || nlon < 1 || nlat < 1) return fail(LETKF_E_INVALID, "bad sizes");
-  if (nctype > 0 && (!typ_ctype || !hori_loc_ctype || !obs_sort_grid_spacing || !max_nobs_per_grid || !obs_min_spacing ||
-                     !ngrd_i || !ngrd_j || !grdspc_i || !grdspc_j || !ngrdsch_i || !ngrdsch_j || !ngrdext_i || !ngrdext_j))
-    return fail(LETKF_E_INVALID, "an array is NULL");
+  if (nctype < 0) return fail(LETKF_E_INVALID, "nctype is negative");
+  if (nobtype < 1) return fail(LETKF_E_INVALID, "nobtype must be positive");
+  if (nlon < 1) return fail(LETKF_E_INVALID, "nlon must be positive");
+  if (nlat < 1) return fail(LETKF_E_INVALID, "nlat must be positive");
+  if (nctype == 0) return LETKF_OK;
+  if (int rc = first_null({{typ_ctype, "typ_ctype"}, {hori_loc_ctype, "hori_loc_ctype"},
+                           {obs_sort_grid_spacing, "obs_sort_grid_spacing"}, {max_nobs_per_grid, "max_nobs_per_grid"},
+                           {obs_min_spacing, "obs_min_spacing"}, {ngrd_i, "ngrd_i"}, {ngrd_j, "ngrd_j"}, {grdspc_i, "grdspc_i"},
+                           {grdspc_j, "grdspc_j"}, {ngrdsch_i, "ngrdsch_i"}, {ngrdsch_j, "ngrdsch_j"}, {ngrdext_i, "ngrdext_i"},
+                           {ngrdext_j, "ngrdext_j"}}))
+    return rc;
+  // the types first, so that a refusal leaves every output as it was
+  for (int ic = 0; ic < nctype; ++ic)
+    if (typ_ctype[ic] < 1 || typ_ctype[ic] > nobtype) return fail(LETKF_E_INVALID, "typ_ctype: a report type outside 1..nobtype");
   if (letkf::obs_mesh_dims(nctype, typ_ctype, hori_loc_ctype, nobtype, obs_sort_grid_spacing, max_nobs_per_grid,
                            obs_min_spacing, dx, dy, nlon, nlat, ngrd_i, ngrd_j, grdspc_i, grdspc_j, ngrdsch_i, ngrdsch_j,
                            ngrdext_i, ngrdext_j))
-    return fail(LETKF_E_INVALID, "a report type outside 1..nobtype or an empty mesh");
+    return fail(LETKF_E_INVALID, "a sorting mesh came out empty (check hori_loc_ctype / obs_sort_grid_spacing / dx / dy)");
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_mesh_dims)
 
@@ -94,7 +137,8 @@ int letkf_set_obs_local_dev(letkf_ctx* c, const letkf_setobs_params* p, const le
                             letkf_obs_table** tab) try {
   if (int rc = check_ctx(c)) return rc;
   std::string msg;
-  if (int rc = letkf::set_obs_local(c->device, c->stream, c->num_cu, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab, &msg))
+  if (int rc = letkf::set_obs_local(c->device, c->stream, c->num_cu, c->lds_max, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab,
+                                    &msg))
     return fail(rc, msg);
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_set_obs_local_dev)
@@ -110,7 +154,10 @@ int letkf_set_obs_finish_dev(letkf_ctx* c, letkf_obs_table* tab, const int32_t* 
 int letkf_set_obs_dev(letkf_ctx* c, const letkf_setobs_params* p, const letkf_qc_params* qcp, const letkf_obs_file_rows* files,
                       int64_t nobs, const int32_t* set, const int32_t* idx, int32_t* qc, double* ensval, int64_t kld,
                       letkf_obs_table** tab) try {
-  if (!p || p->nprocs != 1) return fail(LETKF_E_INVALID, "letkf_set_obs_dev is the one-rank call: nprocs must be 1");
+  if (!tab) return fail(LETKF_E_INVALID, "tab is NULL");
+  *tab = nullptr;
+  if (!p) return fail(LETKF_E_INVALID, "p is NULL");
+  if (p->nprocs != 1) return fail(LETKF_E_INVALID, "letkf_set_obs_dev is the one-rank call: nprocs must be 1");
   if (int rc = letkf_set_obs_local_dev(c, p, qcp, files, nobs, set, idx, qc, ensval, kld, tab)) return rc;
   letkf_obs_table_info i;
   letkf::obs_table_info(*tab, &i);
@@ -123,12 +170,14 @@ int letkf_set_obs_dev(letkf_ctx* c, const letkf_setobs_params* p, const letkf_qc
 } LETKF_ENTRY_END(letkf_set_obs_dev)
 
 int letkf_obs_table_info_get(const letkf_obs_table* tab, letkf_obs_table_info* info) try {
-  if (letkf::obs_table_info(tab, info)) return fail(LETKF_E_INVALID, "tab / info is NULL");
+  if (int rc = first_null({{tab, "tab"}, {info, "info"}})) return rc;
+  letkf::obs_table_info(tab, info);
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_table_info_get)
 
 int letkf_obs_table_search(const letkf_obs_table* tab, letkf_search_tables* tables) try {
-  if (letkf::obs_table_search(tab, tables)) return fail(LETKF_E_INVALID, "tab / tables is NULL or the finish half has not run");
+  if (int rc = first_null({{tab, "tab"}, {tables, "tables"}})) return rc;
+  if (letkf::obs_table_search(tab, tables)) return fail(LETKF_E_INVALID, "tab: the finish half has not run");
   return LETKF_OK;
 } LETKF_ENTRY_END(letkf_obs_table_search)
 

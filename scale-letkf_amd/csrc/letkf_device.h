@@ -252,12 +252,12 @@ hipError_t launch_trivial_points(const PointArgs& a, hipStream_t st);
 hipError_t launch_zero_transmd_unobserved(int64_t nbatch, int ne, const int32_t* nobsl, double* transmd, hipStream_t st);
 hipError_t launch_zero_counts_where_beta_is_zero(int64_t n, const double* beta, int32_t* cnt, hipStream_t st);
 hipError_t launch_obs_departure(const letkf_qc_params& p, long nobs, const int* elm, const double* dat, const double* err,
-                                double* ensval, long kld, double* val, int* qc, int num_cu, hipStream_t st);
+                                double* ensval, long kld, double* val, int* qc, int num_cu, size_t lds_max, hipStream_t st);
 hipError_t obs_mesh_sort(const letkf_mesh& m, long nobs, const int* ctype, const double* ri, const double* rj,
-                         const int* qc, int* n_cell, int* key, long* nsorted, void* scratch, size_t* scratch_bytes,
-                         int num_cu, hipStream_t st);
+                         const int* qc, int* n_cell, int* key, long* nsorted, bool* bad_ctype, void* scratch,
+                         size_t* scratch_bytes, int num_cu, hipStream_t st);
 hipError_t obs_halo_plan(const letkf_halo_layout& l, const int* n_all, int* ac_ext, int* src_row, long cap,
-                         long* nobstotal, int num_cu, hipStream_t st);
+                         long* nobstotal, const char** refused, int num_cu, hipStream_t st);
 hipError_t launch_gather_rows(long nrows, const int* src_row, int ncols, const double* src, long ld_src, double* dst,
                               long ld_dst, int num_cu, hipStream_t st);
 hipError_t launch_gather_i32(long nrows, const int* src_row, const int* src, int* dst, int num_cu, hipStream_t st);
@@ -288,12 +288,13 @@ hipError_t launch_ens_spread(int k, int nv, long npts, const double* x, long sp,
                              hipStream_t st);
 hipError_t launch_ens_mean(int k, int nv, long npts, double* x, long sp, long sm, long sv, hipStream_t st);
 // set_letkf_obs behind one call (letkf_setobs.hip); int results are LETKF_OK / LETKF_E_*, *msg says why
+// (obs_mesh_dims: 0, 1 = a typ_ctype outside 1..nobtype, 2 = an empty mesh)
 int obs_mesh_dims(int nctype, const int* typ_ctype, const double* hori_loc_ctype, int nobtype, const double* spacing,
                   const int* max_nobs, const double* min_spacing, double dx, double dy, int nlon, int nlat, int* ngrd_i,
                   int* ngrd_j, double* grdspc_i, double* grdspc_j, int* ngrdsch_i, int* ngrdsch_j, int* ngrdext_i,
                   int* ngrdext_j);
-int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_params* p, const letkf_qc_params* qcp,
-                  const letkf_obs_file_rows* f,
+int set_obs_local(int device, hipStream_t st, int num_cu, size_t lds_max, const letkf_setobs_params* p,
+                  const letkf_qc_params* qcp, const letkf_obs_file_rows* f,
                   long nobs, const int* set, const int* idx, int* qc, double* ensval, long kld, letkf_obs_table** out,
                   std::string* msg);
 int set_obs_finish(hipStream_t st, int num_cu, letkf_obs_table* t, const int* n_all, const int* tot_g, long nrecv,

@@ -128,6 +128,115 @@ __global__ void __launch_bounds__(64) departure_kernel(const letkf_qc_params P, 
   }
 }
 
+// Rows of which 64 do not fit in LDS (kld >= 320 at 160 KiB): the row rule of departure_kernel, statement for statement, on a
+// pointer to the row -- LDS or global memory.  Same sequential member sum, so the same bits.
+__device__ __forceinline__ void departure_row(const letkf_qc_params& P, const long n, double* e, const int* __restrict__ elm,
+                                              const double* __restrict__ dat, const double* __restrict__ err,
+                                              double* __restrict__ val, int* __restrict__ qc) {
+  int q = qc[n];
+  if (q > 0) return;                                     // letkf_obs.f90:362
+  const int K = P.member;
+  const int el = elm[n];
+  const double d = dat[n];
+  bool live = true;
+  if (el == kIdRadarRef || el == kIdRadarRefZero) {      // :372-411
+    if (!P.use_radar_ref) {
+      q = kQcOtype;
+      live = false;
+    } else if (d == kUndef) {
+      q = kQcObsBad;
+      live = false;
+    } else {
+      int mem_ref = 0;
+      for (int i = 0; i < K; ++i) mem_ref += e[i] > P.radar_ref_thres_dbz + 1.0e-6 ? 1 : 0;
+      const int need = d > P.radar_ref_thres_dbz + 1.0e-6 ? P.min_radar_ref_member_obsref : P.min_radar_ref_member;
+      if (mem_ref < need) {
+        q = kQcRefMem;
+        live = false;
+      }
+    }
+  }
+  if (live && el == kIdRadarVr && !P.use_radar_vr) {     // :413-418
+    q = kQcOtype;
+    live = false;
+  }
+  int mem_cld = 0;
+  if (live && P.h08 && el == kIdH08IR) {                 // -DH08, :432-469
+    if (d == kUndef || P.h08_lev[n] < P.h08_limit_lev) {
+      q = kQcObsBad;
+      live = false;
+    } else {
+      for (int i = 0; i < K; ++i)
+        if (e[i] < 0.0) {
+          ++mem_cld;
+          e[i] = e[i] * (-1.0);
+        }
+    }
+  }
+  if (live) {
+    double v = e[0];                                     // :475-479
+    for (int i = 1; i < K; ++i) v = v + e[i];
+    v = v / (double)K;
+    if (P.h08 && P.h08_val2) {                           // -DH08, :480-487
+      const double clr = P.h08_val2[n];
+      P.h08_val2[n] = (fabs(v - clr) + fabs(d - clr)) * 0.5;
+    }
+    for (int i = 0; i < K; ++i) e[i] = e[i] - v;         // :488-490
+    v = d - v;                                           // :491
+    val[n] = v;
+    if (P.det_run) e[K] = d - e[K];                      // :492-494
+    double ge;                                           // :504-561
+    switch (el) {
+      case kIdRain: ge = P.gross_error_rain; break;
+      case kIdRadarRef:
+      case kIdRadarRefZero: ge = P.gross_error_radar_ref; break;
+      case kIdRadarVr: ge = P.gross_error_radar_vr; break;
+      case kIdRadarPrh: ge = P.gross_error_radar_prh; break;
+      case kIdTclon: ge = P.gross_error_tcx; break;
+      case kIdTclat: ge = P.gross_error_tcy; break;
+      case kIdTcmip: ge = P.gross_error_tcp; break;
+      default: ge = P.gross_error;
+    }
+    if (P.h08 && el == kIdH08IR) {                       // -DH08, :520-541
+      ge = mem_cld < P.h08_min_cld_member ? 1.0 : P.gross_error_h08;
+      if (fabs(v) > ge * err[n]) q = kQcGross;
+      if (d < P.h08_bt_min) q = kQcGross;
+    } else if (fabs(v) > ge * err[n]) {
+      q = kQcGross;
+    }
+  }
+  qc[n] = q;
+}
+
+// ROWS > 0: tiles of ROWS rows through LDS as in departure_kernel, lanes 0 .. ROWS-1 at work on the rows.  ROWS = 0: not even
+// those fit; tiles of 64 rows, lane i walks row i where it lies in global memory.  Neither has been measured.
+constexpr int kDepWideRows = 16;
+template <int ROWS>
+__global__ void __launch_bounds__(64) departure_wide_kernel(const letkf_qc_params P, const long nobs, const int* __restrict__ elm,
+                                                            const double* __restrict__ dat, const double* __restrict__ err,
+                                                            double* ensval, const long kld, double* __restrict__ val,
+                                                            int* __restrict__ qc) {
+  extern __shared__ double wide_rows[];                  // [ROWS][ldr]
+  constexpr int kTile = ROWS > 0 ? ROWS : 64;
+  const int lane = threadIdx.x;
+  const long ldr = kld | 1;
+  for (long n0 = (long)blockIdx.x * kTile; n0 < nobs; n0 += (long)gridDim.x * kTile) {
+    const long nr = min((long)kTile, nobs - n0);
+    double* g = ensval + n0 * kld;
+    if constexpr (ROWS > 0) {
+      const long tot = nr * kld;
+      for (long t = lane; t < tot; t += 64) wide_rows[(t / kld) * ldr + (t % kld)] = g[t];
+      __syncthreads();
+      if (lane < nr) departure_row(P, n0 + lane, wide_rows + lane * ldr, elm, dat, err, val, qc);
+      __syncthreads();
+      for (long t = lane; t < tot; t += 64) g[t] = wide_rows[(t / kld) * ldr + (t % kld)];
+      __syncthreads();
+    } else {
+      if (lane < nr) departure_row(P, n0 + lane, g + lane * kld, elm, dat, err, val, qc);
+    }
+  }
+}
+
 struct MeshDev {
   int nctype, nlon, nlat, ihalo, jhalo, rank_i, rank_j, fix_j;
   const int* ngrd_i;      // device copies
@@ -141,31 +250,40 @@ __device__ __forceinline__ long mesh_cell(const MeshDev& m, int ic, double ri, d
   const double ril = ri - (double)(m.rank_i * m.nlon);
   const double rjl = rj - (double)(m.rank_j * m.nlat);
   const int gi = m.ngrd_i[ic], gj = m.ngrd_j[ic];
-  int i = (int)ceil((ril - (double)m.ihalo - 0.5) * (double)gi / (double)m.nlon);
-  int j = (int)ceil((rjl - (double)m.jhalo - 0.5) * (double)(m.fix_j ? gj : gi) / (double)m.nlat);
-  i = i < 1 ? 1 : (i > gi ? gi : i);
-  j = j < 1 ? 1 : (j > gj ? gj : j);
+  // clamped as doubles, before the conversion: defined for every double (NaN and -inf: cell 1, +inf: the last cell)
+  const double ci = ceil((ril - (double)m.ihalo - 0.5) * (double)gi / (double)m.nlon);
+  const double cj = ceil((rjl - (double)m.jhalo - 0.5) * (double)(m.fix_j ? gj : gi) / (double)m.nlat);
+  const int i = !(ci >= 1.0) ? 1 : (ci > (double)gi ? gi : (int)ci);
+  const int j = !(cj >= 1.0) ? 1 : (cj > (double)gj ? gj : (int)cj);
   return m.coff[ic] + (long)(j - 1) * gi + (i - 1);
 }
 
 __global__ void mesh_key_kernel(const MeshDev m, const long nobs, const int* __restrict__ ctype,
                                 const double* __restrict__ ri, const double* __restrict__ rj,
                                 const int* __restrict__ qc, unsigned long long* __restrict__ keys,
-                                int* __restrict__ n_cell) {
+                                int* __restrict__ n_cell, int* __restrict__ bad) {
   for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < nobs; n += (long)gridDim.x * blockDim.x) {
     unsigned long long key = ~0ull;                      // rejected observations sort to the end
     if (qc[n] == kQcGood) {
-      const long c = mesh_cell(m, ctype[n], ri[n], rj[n]);
-      key = ((unsigned long long)c << 32) | (unsigned long long)(unsigned int)n;
-      atomicAdd(&n_cell[c], 1);
+      const int ic = ctype[n];
+      if (ic < 0 || ic >= m.nctype) {                    // no cell to count it in: the entry refuses
+        atomicOr(bad, 1);
+      } else {
+        const long c = mesh_cell(m, ic, ri[n], rj[n]);
+        key = ((unsigned long long)c << 32) | (unsigned long long)(unsigned int)n;
+        atomicAdd(&n_cell[c], 1);
+      }
     }
     keys[n] = key;
   }
 }
 
-__global__ void key_low_kernel(const long n, const unsigned long long* __restrict__ keys, int* __restrict__ key) {
+// nothing is written once mesh_key_kernel has flagged a row; the rejected rows, sorted to the end, leave key[nsorted ..] alone
+__global__ void key_low_kernel(const long n, const unsigned long long* __restrict__ keys, const int* __restrict__ bad,
+                               int* __restrict__ key) {
+  if (*bad) return;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x)
-    key[t] = (int)(unsigned int)(keys[t] & 0xFFFFFFFFull);
+    if (keys[t] != ~0ull) key[t] = (int)(unsigned int)(keys[t] & 0xFFFFFFFFull);
 }
 
 // one wave per extended cell: src_row[dst0 + t] = src0 + t
@@ -201,20 +319,33 @@ __global__ void gather_i32_kernel(const long nrows, const int* __restrict__ src_
 }  // namespace
 
 hipError_t launch_obs_departure(const letkf_qc_params& p, long nobs, const int* elm, const double* dat, const double* err,
-                                double* ensval, long kld, double* val, int* qc, int num_cu, hipStream_t st) {
+                                double* ensval, long kld, double* val, int* qc, int num_cu, size_t lds_max, hipStream_t st) {
   if (nobs <= 0) return hipSuccess;
-  const size_t lds = (size_t)kDepRows * (size_t)(kld | 1) * sizeof(double);
-  if (hipError_t e = lds_opt_in(&departure_kernel, lds)) return e;
-  const int grid = grid_for((nobs + kDepRows - 1) / kDepRows, 1, num_cu);
-  hipLaunchKernelGGL(departure_kernel, dim3(grid), dim3(64), lds, st, p, nobs, elm, dat, err, ensval, kld, val, qc);
+  const size_t row = (size_t)(kld | 1) * sizeof(double);
+  if (kDepRows * row <= lds_max) {
+    const size_t lds = kDepRows * row;
+    if (hipError_t e = lds_opt_in(&departure_kernel, lds)) return e;
+    const int grid = grid_for((nobs + kDepRows - 1) / kDepRows, 1, num_cu);
+    hipLaunchKernelGGL(departure_kernel, dim3(grid), dim3(64), lds, st, p, nobs, elm, dat, err, ensval, kld, val, qc);
+  } else if (kDepWideRows * row <= lds_max) {
+    const size_t lds = kDepWideRows * row;
+    if (hipError_t e = lds_opt_in(&departure_wide_kernel<kDepWideRows>, lds)) return e;
+    const int grid = grid_for((nobs + kDepWideRows - 1) / kDepWideRows, 1, num_cu);
+    hipLaunchKernelGGL(departure_wide_kernel<kDepWideRows>, dim3(grid), dim3(64), lds, st, p, nobs, elm, dat, err, ensval, kld,
+                       val, qc);
+  } else {
+    const int grid = grid_for((nobs + 63) / 64, 1, num_cu);
+    hipLaunchKernelGGL(departure_wide_kernel<0>, dim3(grid), dim3(64), 0, st, p, nobs, elm, dat, err, ensval, kld, val, qc);
+  }
   return hipGetLastError();
 }
 
 // Scratch layout (bytes) for the sort: [keys_in nobs*8][keys_out nobs*8][ngrd_i, ngrd_j: nctype*4 each][coff (nctype+1)*8]
-// [rocprim temp].  Returns the bytes needed when scratch == nullptr.
+// [flag 8][rocprim temp].  Returns the bytes needed when scratch == nullptr.  *bad_ctype: an accepted row's ctype lies outside
+// 0 .. nctype-1 -- key and *nsorted are then left alone, n_cell holds the counts of the other accepted rows.
 hipError_t obs_mesh_sort(const letkf_mesh& m, long nobs, const int* ctype, const double* ri, const double* rj,
-                         const int* qc, int* n_cell, int* key, long* nsorted, void* scratch, size_t* scratch_bytes,
-                         int num_cu, hipStream_t st) {
+                         const int* qc, int* n_cell, int* key, long* nsorted, bool* bad_ctype, void* scratch,
+                         size_t* scratch_bytes, int num_cu, hipStream_t st) {
   std::vector<long> coff(m.nctype + 1, 0);
   for (int ic = 0; ic < m.nctype; ++ic) coff[ic + 1] = coff[ic] + (long)m.ngrd_i[ic] * m.ngrd_j[ic];
   const long ncell = coff[m.nctype];
@@ -225,7 +356,7 @@ hipError_t obs_mesh_sort(const letkf_mesh& m, long nobs, const int* ctype, const
                                           (size_t)(nobs > 0 ? nobs : 1), 0, 32 + cell_bits, st);
   if (e != hipSuccess) return e;
   const size_t a_keys = ((size_t)(nobs > 0 ? nobs : 1) * 8 + 255) & ~(size_t)255;
-  const size_t a_tab = ((size_t)m.nctype * 8 + (size_t)(m.nctype + 1) * 8 + 255) & ~(size_t)255;
+  const size_t a_tab = ((size_t)m.nctype * 8 + (size_t)(m.nctype + 1) * 8 + 8 + 255) & ~(size_t)255;
   const size_t need = 2 * a_keys + a_tab + temp_bytes + 256;
   if (!scratch) {
     *scratch_bytes = need;
@@ -238,26 +369,37 @@ hipError_t obs_mesh_sort(const letkf_mesh& m, long nobs, const int* ctype, const
   int* d_gi = reinterpret_cast<int*>(base + 2 * a_keys);
   int* d_gj = d_gi + m.nctype;
   long* d_coff = reinterpret_cast<long*>(base + 2 * a_keys + (size_t)m.nctype * 8);
+  int* d_bad = reinterpret_cast<int*>(d_coff + m.nctype + 1);
   void* temp = base + 2 * a_keys + a_tab;
+  *bad_ctype = false;
   if ((e = hipMemcpyAsync(d_gi, m.ngrd_i, sizeof(int) * m.nctype, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(d_gj, m.ngrd_j, sizeof(int) * m.nctype, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(d_coff, coff.data(), sizeof(long) * (m.nctype + 1), hipMemcpyHostToDevice, st)) != hipSuccess)
     return e;
   if ((e = hipMemsetAsync(n_cell, 0, sizeof(int) * (size_t)(ncell > 0 ? ncell : 1), st)) != hipSuccess) return e;
-  *nsorted = 0;
-  if (nobs <= 0) return hipStreamSynchronize(st);
+  if ((e = hipMemsetAsync(d_bad, 0, sizeof(int), st)) != hipSuccess) return e;
+  if (nobs <= 0) {
+    *nsorted = 0;
+    return hipStreamSynchronize(st);
+  }
   MeshDev md{m.nctype, m.nlon, m.nlat, m.ihalo, m.jhalo, m.rank_i, m.rank_j, m.fix_ij_obsgrd != 0, d_gi, d_gj, d_coff};
   hipLaunchKernelGGL(mesh_key_kernel, dim3(grid_for(nobs, 256, num_cu)), dim3(256), 0, st, md, nobs, ctype, ri, rj, qc,
-                     kin, n_cell);
+                     kin, n_cell, d_bad);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = rocprim::radix_sort_keys(temp, temp_bytes, kin, kout, (size_t)nobs, 0, 32 + cell_bits, st)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(key_low_kernel, dim3(grid_for(nobs, 256, num_cu)), dim3(256), 0, st, nobs, kout, key);
+  hipLaunchKernelGGL(key_low_kernel, dim3(grid_for(nobs, 256, num_cu)), dim3(256), 0, st, nobs, kout, d_bad, key);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // number of accepted observations = total of the cell counts
   std::vector<int> h(ncell > 0 ? ncell : 1, 0);
   if ((e = hipMemcpyAsync(h.data(), n_cell, sizeof(int) * (size_t)ncell, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  int h_bad = 0;
+  if ((e = hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  if (h_bad) {
+    *bad_ctype = true;
+    return hipSuccess;
+  }
   long tot = 0;
   for (long c = 0; c < ncell; ++c) tot += h[c];
   *nsorted = tot;
@@ -265,8 +407,11 @@ hipError_t obs_mesh_sort(const letkf_mesh& m, long nobs, const int* ctype, const
 }
 
 // Host plan (letkf_obs.f90:922-976, :1036-1100) + device expansion into src_row.  n_all: device [nprocs][ncell].
+// *refused (and hipErrorInvalidValue): what the plan objects to -- a count of n_all, found on the host before anything is
+// launched or written, or the capacity of src_row (*nobstotal then says what it takes; ac_ext is written, src_row is not).
 hipError_t obs_halo_plan(const letkf_halo_layout& l, const int* n_all, int* ac_ext, int* src_row, long cap,
-                         long* nobstotal, int num_cu, hipStream_t st) {
+                         long* nobstotal, const char** refused, int num_cu, hipStream_t st) {
+  *refused = nullptr;
   const int nc = l.nctype, np = l.nprocs;
   std::vector<long> coff(nc + 1, 0), xoff(nc + 1, 0), ecell(nc + 1, 0);
   for (int ic = 0; ic < nc; ++ic) {
@@ -283,6 +428,12 @@ hipError_t obs_halo_plan(const letkf_halo_layout& l, const int* n_all, int* ac_e
       return e;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
   }
+  long total = 0;
+  for (int v : h) {
+    if (v < 0) return *refused = "n_all holds a negative cell count", hipErrorInvalidValue;
+    total += v;
+  }
+  if (total >= (1L << 31)) return *refused = "the total of n_all reaches 2^31 rows", hipErrorInvalidValue;
   std::vector<long> start((size_t)np * (ncell > 0 ? ncell : 1), 0), dspr(np + 1, 0);
   for (int ip = 0; ip < np; ++ip) {                      // ac(:,:,ip) and dspr (:979-984)
     long acc = 0;
@@ -331,7 +482,7 @@ hipError_t obs_halo_plan(const letkf_halo_layout& l, const int* n_all, int* ac_e
   *nobstotal = acx;
   if ((e = hipMemcpyAsync(ac_ext, h_ac.data(), sizeof(int) * (size_t)xoff[nc], hipMemcpyHostToDevice, st)) != hipSuccess)
     return e;
-  if (acx > cap) return hipErrorInvalidValue;
+  if (acx > cap) return *refused = "src_row capacity (cap) is smaller than nobstotal", hipErrorInvalidValue;
   if (acx > 0) {
     // the three per-cell arrays ride in a temporary device buffer
     int* d_plan = nullptr;

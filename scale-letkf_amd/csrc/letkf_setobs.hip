@@ -303,7 +303,7 @@ int obs_mesh_dims(int nctype, const int* typ_ctype, const double* hori_loc_ctype
                   int* ngrdext_j) {
   for (int ic = 0; ic < nctype; ++ic) {
     const int ityp = typ_ctype[ic];
-    if (ityp < 1 || ityp > nobtype) return LETKF_E_INVALID;
+    if (ityp < 1 || ityp > nobtype) return 1;
     double target;
     if (spacing[ityp - 1] > 0.0)
       target = spacing[ityp - 1];
@@ -320,32 +320,46 @@ int obs_mesh_dims(int nctype, const int* typ_ctype, const double* hori_loc_ctype
     ngrdsch_j[ic] = (int)std::ceil(hori_loc_ctype[ic] * kDistZeroFac / grdspc_j[ic]);
     ngrdext_i[ic] = ngrd_i[ic] + ngrdsch_i[ic] * 2;
     ngrdext_j[ic] = ngrd_j[ic] + ngrdsch_j[ic] * 2;
-    if (ngrd_i[ic] < 1 || ngrd_j[ic] < 1) return LETKF_E_INVALID;
+    if (ngrd_i[ic] < 1 || ngrd_j[ic] < 1) return 2;
   }
   return LETKF_OK;
 }
 
-int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_params* p, const letkf_qc_params* qcp,
-                  const letkf_obs_file_rows* f,
+int set_obs_local(int device, hipStream_t st, int num_cu, size_t lds_max, const letkf_setobs_params* p,
+                  const letkf_qc_params* qcp, const letkf_obs_file_rows* f,
                   long nobs, const int* set, const int* idx, int* qc, double* ensval, long kld, letkf_obs_table** out,
                   std::string* msg) {
-  if (!p || !qcp || !f || !out) return *msg = "params / qc / files / tab is NULL", LETKF_E_INVALID;
+  if (!out) return *msg = "tab is NULL", LETKF_E_INVALID;
   *out = nullptr;
+  if (!p) return *msg = "p is NULL", LETKF_E_INVALID;
+  if (!qcp) return *msg = "qcp is NULL", LETKF_E_INVALID;
+  if (!f) return *msg = "files is NULL", LETKF_E_INVALID;
   const letkf_qc_params& q = *qcp;
   if (p->nobtype < 1 || p->nobtype > 32) return *msg = "nobtype must be 1..32", LETKF_E_INVALID;
-  if (!p->hori_local || !p->vert_local || !p->obs_sort_grid_spacing || !p->obs_min_spacing || !p->max_nobs_per_grid)
-    return *msg = "a per-report-type namelist array is NULL", LETKF_E_INVALID;
-  if (p->nlon < 1 || p->nlat < 1 || p->nprocs < 1 || p->prc_num_x < 1 || p->nprocs % p->prc_num_x != 0 || p->myrank < 0 ||
-      p->myrank >= p->nprocs || !(p->dx > 0.0) || !(p->dy > 0.0))
-    return *msg = "bad domain / rank layout", LETKF_E_INVALID;
-  if (f->nfile < 0 || (f->nfile > 0 && !f->off)) return *msg = "bad file offsets", LETKF_E_INVALID;
-  if (nobs < 0 || nobs >= (1L << 31)) return *msg = "nobs out of range", LETKF_E_INVALID;
-  if (q.member < 1 || kld < q.member + (q.det_run ? 1 : 0) || kld >= (1L << 20))
-    return *msg = "kld must hold MEMBER (+1 with DET_RUN) columns", LETKF_E_INVALID;
-  if ((size_t)64 * (size_t)(kld | 1) * sizeof(double) > 160 * 1024) return *msg = "kld too large", LETKF_E_INVALID;
-  if (nobs > 0 && (!set || !idx || !qc || !ensval)) return *msg = "an obsda array is NULL", LETKF_E_INVALID;
-  if (nobs > 0 && f->nfile == 0) return *msg = "obsda rows without observation files", LETKF_E_INVALID;
-  if (q.h08 && nobs > 0 && !q.h08_lev) return *msg = "h08 = 1 needs qc->h08_lev", LETKF_E_INVALID;
+  if (!p->hori_local) return *msg = "p->hori_local is NULL", LETKF_E_INVALID;
+  if (!p->vert_local) return *msg = "p->vert_local is NULL", LETKF_E_INVALID;
+  if (!p->obs_sort_grid_spacing) return *msg = "p->obs_sort_grid_spacing is NULL", LETKF_E_INVALID;
+  if (!p->obs_min_spacing) return *msg = "p->obs_min_spacing is NULL", LETKF_E_INVALID;
+  if (!p->max_nobs_per_grid) return *msg = "p->max_nobs_per_grid is NULL", LETKF_E_INVALID;
+  if (p->nlon < 1) return *msg = "nlon must be positive", LETKF_E_INVALID;
+  if (p->nlat < 1) return *msg = "nlat must be positive", LETKF_E_INVALID;
+  if (p->nprocs < 1) return *msg = "nprocs must be positive", LETKF_E_INVALID;
+  if (p->prc_num_x < 1 || p->nprocs % p->prc_num_x != 0) return *msg = "prc_num_x must be positive and divide nprocs", LETKF_E_INVALID;
+  if (p->myrank < 0 || p->myrank >= p->nprocs) return *msg = "myrank outside 0..nprocs-1", LETKF_E_INVALID;
+  if (!(p->dx > 0.0)) return *msg = "dx must be positive", LETKF_E_INVALID;
+  if (!(p->dy > 0.0)) return *msg = "dy must be positive", LETKF_E_INVALID;
+  if (f->nfile < 0) return *msg = "files->nfile is negative", LETKF_E_INVALID;
+  if (f->nfile > 0 && !f->off) return *msg = "files->off is NULL", LETKF_E_INVALID;
+  if (nobs < 0 || nobs >= (1L << 31)) return *msg = "nobs outside 0..2^31-1", LETKF_E_INVALID;
+  if (q.member < 1) return *msg = "qcp->member must be positive", LETKF_E_INVALID;
+  if (kld < q.member + (q.det_run ? 1 : 0)) return *msg = "kld must hold MEMBER (+1 with DET_RUN) columns", LETKF_E_INVALID;
+  if (kld >= (1L << 20)) return *msg = "kld must be below 2^20", LETKF_E_INVALID;
+  if (nobs > 0 && !set) return *msg = "set is NULL", LETKF_E_INVALID;
+  if (nobs > 0 && !idx) return *msg = "idx is NULL", LETKF_E_INVALID;
+  if (nobs > 0 && !qc) return *msg = "qc is NULL", LETKF_E_INVALID;
+  if (nobs > 0 && !ensval) return *msg = "ensval is NULL", LETKF_E_INVALID;
+  if (nobs > 0 && f->nfile == 0) return *msg = "nobs > 0 with files->nfile = 0: obsda rows without observation files", LETKF_E_INVALID;
+  if (q.h08 && nobs > 0 && !q.h08_lev) return *msg = "h08 = 1 needs qcp->h08_lev", LETKF_E_INVALID;
 
   letkf_obs_table* t = new letkf_obs_table();
   std::unique_ptr<letkf_obs_table> guard(t);
@@ -363,11 +377,16 @@ int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_par
   t->files = *f;
   t->off.assign(f->nfile + 1, 0);
   for (int i = 0; i <= f->nfile && f->nfile > 0; ++i) t->off[i] = f->off[i];
+  if (t->off[0] != 0) return *msg = "files->off must start at 0", LETKF_E_INVALID;
   for (int i = 0; i < f->nfile; ++i)
-    if (t->off[i + 1] < t->off[i] || t->off[0] != 0) return *msg = "file offsets must start at 0 and not decrease", LETKF_E_INVALID;
+    if (t->off[i + 1] < t->off[i]) return *msg = "files->off must not decrease", LETKF_E_INVALID;
   t->nrows = t->off[f->nfile];
-  if (t->nrows > 0 && (!f->elm || !f->typ || !f->lev || !f->dat || !f->err || !f->ri || !f->rj))
-    return *msg = "a file-row array is NULL", LETKF_E_INVALID;
+  if (t->nrows > 0) {
+    const void* arr[] = {f->elm, f->typ, f->lev, f->dat, f->err, f->ri, f->rj};
+    const char* name[] = {"elm", "typ", "lev", "dat", "err", "ri", "rj"};
+    for (int i = 0; i < 7; ++i)
+      if (!arr[i]) return *msg = std::string("files->") + name[i] + " is NULL", LETKF_E_INVALID;
+  }
   t->nobs = nobs;
   t->kld = (int)kld;
   t->set = set;
@@ -390,7 +409,7 @@ int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_par
   int hflags[2 + LETKF_NID_OBS];
   SO_TRY(hipMemcpyAsync(hflags, t->d_flags, sizeof(hflags), hipMemcpyDeviceToHost, st));
   SO_TRY(hipStreamSynchronize(st));
-  if (hflags[0]) return *msg = "an observation file row has an element outside uid_obs or a report type outside 1..nobtype", LETKF_E_INVALID;
+  if (hflags[0]) return *msg = "files: a row's elm lies outside uid_obs or its typ outside 1..nobtype", LETKF_E_INVALID;
 
   // ---- combined-type tables (:307-342): types outer, elements inner, so the ctypes come in ascending order
   t->ctype_elmtyp.assign((size_t)LETKF_NID_OBS * nt_, 0);
@@ -417,7 +436,7 @@ int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_par
                     t->min_spacing.data(), p->dx, p->dy, p->nlon, p->nlat, t->ngrd_i.data(), t->ngrd_j.data(),
                     t->grdspc_i.data(), t->grdspc_j.data(), t->ngrdsch_i.data(), t->ngrdsch_j.data(), t->ngrdext_i.data(),
                     t->ngrdext_j.data()))
-    return *msg = "a sorting mesh came out empty (check HORI_LOCAL / OBS_SORT_GRID_SPACING)", LETKF_E_INVALID;
+    return *msg = "a sorting mesh came out empty (check hori_local / obs_sort_grid_spacing / dx / dy)", LETKF_E_INVALID;
   t->ac_off.assign(nc, 0);
   for (int ic = 0; ic < nc; ++ic) {
     t->ncell += (long)t->ngrd_i[ic] * t->ngrd_j[ic];
@@ -451,10 +470,11 @@ int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_par
     SO_TRY(hipGetLastError());
     SO_TRY(hipMemcpyAsync(hflags, t->d_flags, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
     SO_TRY(hipStreamSynchronize(st));
-    if (hflags[1]) return *msg = "an obsda row's set / idx lies outside the observation files", LETKF_E_INVALID;
+    if (hflags[1]) return *msg = "an obsda row's set / idx lies outside files", LETKF_E_INVALID;
 
     // ---- departure + QC (:361-561), counts (:744-760), bucket sort (:762-822)
-    SO_TRY(launch_obs_departure(t->qc, nobs, t->d_row_elm, t->d_row_dat, t->d_row_err, ensval, kld, t->d_val, qc, num_cu, st));
+    SO_TRY(launch_obs_departure(t->qc, nobs, t->d_row_elm, t->d_row_dat, t->d_row_err, ensval, kld, t->d_val, qc, num_cu, lds_max,
+                                st));
     hipLaunchKernelGGL(counts_kernel, dim3(grid_for(nobs, 256, num_cu)), dim3(256), sizeof(int) * 2 * nc, st, nobs, nc,
                        t->d_row_ctype, qc, t->d_tot);
     SO_TRY(hipGetLastError());
@@ -462,12 +482,13 @@ int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_par
                  p->fix_ij_obsgrd, t->ngrd_i.data(), t->ngrd_j.data()};
     size_t need = 0;
     long ns = 0;
-    SO_TRY(obs_mesh_sort(m, nobs, t->d_row_ctype, t->d_row_ri, t->d_row_rj, qc, t->d_n_cell, t->d_key, &ns, nullptr, &need,
-                         num_cu, st));
+    bool bad = false;                                      // every ctype here is ctype_elmtyp's: never set
+    SO_TRY(obs_mesh_sort(m, nobs, t->d_row_ctype, t->d_row_ri, t->d_row_rj, qc, t->d_n_cell, t->d_key, &ns, &bad, nullptr,
+                         &need, num_cu, st));
     char* scratch = nullptr;
     SO_TRY(dalloc(t, &scratch, need));
-    SO_TRY(obs_mesh_sort(m, nobs, t->d_row_ctype, t->d_row_ri, t->d_row_rj, qc, t->d_n_cell, t->d_key, &ns, scratch, &need,
-                         num_cu, st));
+    SO_TRY(obs_mesh_sort(m, nobs, t->d_row_ctype, t->d_row_ri, t->d_row_rj, qc, t->d_n_cell, t->d_key, &ns, &bad, scratch,
+                         &need, num_cu, st));
     t->nsorted = ns;
   }
   // ---- the rank's send buffer
@@ -487,10 +508,11 @@ int set_obs_local(int device, hipStream_t st, int num_cu, const letkf_setobs_par
 int set_obs_finish(hipStream_t st, int num_cu, letkf_obs_table* t, const int* n_all, const int* tot_g, long nrecv,
                    const double* recv, std::string* msg) {
   if (!t) return *msg = "tab is NULL", LETKF_E_INVALID;
-  if (t->finished) return *msg = "the finish half already ran on this table", LETKF_E_INVALID;
+  if (t->finished) return *msg = "tab: the finish half already ran on this table", LETKF_E_INVALID;
   const int nc = t->nctype, np = t->p.nprocs, kld = t->kld;
   if (nc > 0 && t->ncell > 0 && !n_all) return *msg = "n_all is NULL", LETKF_E_INVALID;
-  if (nrecv < 0 || (nrecv > 0 && !recv)) return *msg = "bad receive buffer", LETKF_E_INVALID;
+  if (nrecv < 0) return *msg = "nrecv is negative", LETKF_E_INVALID;
+  if (nrecv > 0 && !recv) return *msg = "recv is NULL", LETKF_E_INVALID;
   // the row map indexes the receive buffer: its rows must be exactly the cell counts' total
   long total = 0;
   if (nc > 0 && t->ncell > 0) {
@@ -498,10 +520,11 @@ int set_obs_finish(hipStream_t st, int num_cu, letkf_obs_table* t, const int* n_
     SO_TRY(hipMemcpyAsync(h.data(), n_all, sizeof(int) * h.size(), hipMemcpyDeviceToHost, st));
     SO_TRY(hipStreamSynchronize(st));
     for (int v : h) {
-      if (v < 0) return *msg = "negative cell count in n_all", LETKF_E_INVALID;
+      if (v < 0) return *msg = "n_all holds a negative cell count", LETKF_E_INVALID;
       total += v;
     }
   }
+  if (total >= (1L << 31)) return *msg = "the total of n_all reaches 2^31 rows", LETKF_E_INVALID;
   if (total != nrecv) return *msg = "nrecv differs from the total of n_all", LETKF_E_INVALID;
   SO_TRY(dalloc(t, &t->d_ac_ext, t->nacx));
   SO_TRY(dalloc(t, &t->d_src_row, nrecv));
@@ -509,8 +532,9 @@ int set_obs_finish(hipStream_t st, int num_cu, letkf_obs_table* t, const int* n_
   if (nc > 0) {
     letkf_halo_layout l{nc, np, t->p.prc_num_x, t->p.myrank, t->ngrd_i.data(), t->ngrd_j.data(), t->ngrdsch_i.data(),
                         t->ngrdsch_j.data()};
-    hipError_t e = obs_halo_plan(l, n_all, t->d_ac_ext, t->d_src_row, nrecv, &nt, num_cu, st);
-    if (e == hipErrorInvalidValue && nt > nrecv) return *msg = "the plan needs more rows than were received", LETKF_E_INVALID;
+    const char* refused = nullptr;
+    hipError_t e = obs_halo_plan(l, n_all, t->d_ac_ext, t->d_src_row, nrecv, &nt, &refused, num_cu, st);
+    if (refused) return *msg = refused, LETKF_E_INVALID;
     SO_TRY(e);
   }
   t->nobstotal = nt;
@@ -603,7 +627,9 @@ int obs_table_search(const letkf_obs_table* t, letkf_search_tables* s) {
 }
 
 int obs_table_set_varloc(hipStream_t st, letkf_obs_table* t, const double* varloc, std::string* msg) {
-  if (!t || !t->finished || (t->nctype > 0 && !varloc)) return *msg = "table not finished or varloc NULL", LETKF_E_INVALID;
+  if (!t) return *msg = "tab is NULL", LETKF_E_INVALID;
+  if (!t->finished) return *msg = "tab: the finish half has not run", LETKF_E_INVALID;
+  if (t->nctype > 0 && !varloc) return *msg = "varloc is NULL", LETKF_E_INVALID;
   if (t->nctype > 0)
     SO_TRY(hipMemcpyAsync(t->d_small_d + 2 * t->nctype, varloc, sizeof(double) * t->nctype, hipMemcpyHostToDevice, st));
   SO_TRY(hipStreamSynchronize(st));
@@ -661,7 +687,8 @@ void obs_table_destroy(letkf_obs_table* t) { delete t; }
 
 int obs_table_download(hipStream_t st, const letkf_obs_table* t, double* ensval, double* val, int* qc, double* ob[5],
                        int* ac_ext, std::string* msg) {
-  if (!t || !t->finished) return *msg = "table not finished", LETKF_E_INVALID;
+  if (!t) return *msg = "tab is NULL", LETKF_E_INVALID;
+  if (!t->finished) return *msg = "tab: the finish half has not run", LETKF_E_INVALID;
   const size_t nt = (size_t)t->nobstotal;
   if (ensval && nt) SO_TRY(hipMemcpyAsync(ensval, t->d_ens_sort, sizeof(double) * nt * t->kld, hipMemcpyDeviceToHost, st));
   if (val && nt) SO_TRY(hipMemcpyAsync(val, t->d_val_sort, sizeof(double) * nt, hipMemcpyDeviceToHost, st));

@@ -128,8 +128,8 @@ def qc_of(w, **over):
 
 
 def oracle_local(w, rk, nml):
-    """The local half for one rank.  Returns dict(files (pre-processed), ctype tables, mesh dims, rows, val, qc, ensval,
-    tot, n_cell, key, send)."""
+    """The local half for one rank (w["fix_ij_obsgrd"], default 0: letkf_mesh.fix_ij_obsgrd of the sort).  Returns dict(files
+    (pre-processed), ctype tables, mesh dims, rows, val, qc, ensval, tot, n_cell, key, send)."""
     L, O = lib(), _oracle.oracle()
     O.orc_obs_mesh_sort.restype = C.c_int64
     f = {key: v.copy() for key, v in w["files"].items()}
@@ -174,7 +174,7 @@ def oracle_local(w, rk, nml):
     n_cell = np.zeros(max(ncell, 1), np.int32)
     key = np.zeros(max(n, 1), np.int32)
     m = fill(Mesh, nctype=nc, nlon=w["nlon"], nlat=w["nlat"], ihalo=w["ihalo"], jhalo=w["ihalo"], rank_i=rk["pi"],
-             rank_j=rk["pj"], fix_ij_obsgrd=0, ngrd_i=dims["ngrd_i"].ctypes.data, ngrd_j=dims["ngrd_j"].ctypes.data)
+             rank_j=rk["pj"], fix_ij_obsgrd=int(w.get("fix_ij_obsgrd", 0)), ngrd_i=dims["ngrd_i"].ctypes.data, ngrd_j=dims["ngrd_j"].ctypes.data)
     ns = O.orc_obs_mesh_sort(C.byref(m), C.c_int64(n), _p(rows["ctype"]), _p(rows["ri"]), _p(rows["rj"]), _p(qc),
                              _p(n_cell), _p(key)) if n else 0
     key = key[:ns]
@@ -246,7 +246,8 @@ def setobs_params(cls, w, nml, myrank=0):
              ("obs_min_spacing", np.float64), ("max_nobs_per_grid", np.int32))]
     p = fill(cls, nobtype=NOBTYPE, use_obserr_radar_ref=nml["use_obserr_radar_ref"],
              use_obserr_radar_vr=nml["use_obserr_radar_vr"], nlon=w["nlon"], nlat=w["nlat"], ihalo=w["ihalo"],
-             jhalo=w["ihalo"], nprocs=w["px"] * w["py"], prc_num_x=w["px"], myrank=myrank, fix_ij_obsgrd=0,
+             jhalo=w["ihalo"], nprocs=w["px"] * w["py"], prc_num_x=w["px"], myrank=myrank,
+             fix_ij_obsgrd=int(w.get("fix_ij_obsgrd", 0)),
              criterion=nml["criterion"], min_radar_ref_dbz=nml["min_radar_ref_dbz"], low_ref_shift=nml["low_ref_shift"],
              obserr_radar_ref=nml["obserr_radar_ref"], obserr_radar_vr=nml["obserr_radar_vr"],
              hori_local_radar_obsnoref=nml["hori_local_radar_obsnoref"], hori_local_radar_vr=nml["hori_local_radar_vr"],
