@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("LETKF_AMD_LIB") or os.path.join(HERE, "lib", "libletk
 OSSE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_osse.so")   # the OSSE tools (include/letkf_amd_obsmake.h); links against the production library
 OBSSIM_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obssim.so")   # the model-to-observation simulator (include/letkf_amd_obssim.h); links against the production library too
 SUPEROB_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_superob.so")   # superob (include/letkf_amd_superob.h); links against the production library too
+OBSSCAN_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsscan.so")   # obsope_cal's first scan (include/letkf_amd_obsscan.h); made by `make obsscan`, after the default goal
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -30,14 +31,16 @@ class LetkfError(RuntimeError):
 def build(force=False):
     """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
+    srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*"))
     srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH)
+    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
         subprocess.check_call(["make", "-j4", "-C", HERE] + (["-B"] if force else []), stdout=2)
+        subprocess.check_call(["make", "-j4", "-C", HERE, "obsscan"], stdout=2)   # (a goal of its own, after the default one)
     return LIB_PATH
 
 
@@ -529,6 +532,39 @@ SUPEROB_ARGTYPES = {
 }
 SUPEROB_SURFACE_TYPES = 0x4780   # report types 8, 9, 10, 11, 15 (scale/obs/superob.f90:289-291)
 
+
+
+class ObsscanParams(C.Structure):
+    """letkf_obsscan_params (include/letkf_amd_obsscan.h): dif is a device array per file row, obsda_run a HOST array or NULL"""
+    _fields_ = ([("dif", C.c_void_p), ("obsda_run", C.c_void_p)] +
+                [(n, C.c_int32) for n in ("nlon", "nlat", "ihalo", "jhalo", "prc_num_x", "prc_num_y", "slot_start", "slot_end",
+                                          "slot_base", "myrank_d")] + [("slot_tinterval", C.c_double)])
+
+
+class ObsscanOut(C.Structure):
+    """letkf_obsscan_out (include/letkf_amd_obsscan.h): bsn / bsna are HOST arrays, the rest device arrays; rank, slot and own
+    may be NULL"""
+    _fields_ = [(n, C.c_void_p) for n in ("set", "idx", "qc", "bsn", "bsna", "rank", "slot", "own")]
+
+
+class ObsscanLists(C.Structure):
+    """letkf_obsscan_lists (include/letkf_amd_obsscan.h): a scan's lists as letkf_obsope_slot_dev takes them; bsna is a HOST array"""
+    _fields_ = ([(n, C.c_int32) for n in ("nprocs_d", "slot_start", "slot_end", "reserved0")] +
+                [(n, C.c_void_p) for n in ("bsna", "set", "idx", "qc")])
+
+
+# ... and of the eighth companion header include/letkf_amd_obsscan.h, a table of its own: the entries are exported by the library
+# of the scan (OBSSCAN_LIB_PATH, obsscan_lib()), not by the other four
+OBSSCAN_VERSION = 1
+OBSSCAN_ARGTYPES = {
+    "letkf_obsscan_dev": [_VP, _VP, _VP, _VP],
+    "letkf_obsscan_rows": [_VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP],
+    "letkf_obsscan_slot_bounds": [_I32, _I32, _I32, _F64, _VP, _VP],
+    "letkf_obsope_slot_dev": [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _I64],
+}
+OBSSCAN_MAX_BUCKETS = 1 << 22
+IQC_TIME, IQC_OUT_H = 97, 98
+
 _libs = {}
 
 
@@ -574,6 +610,35 @@ def superob_lib():
     """dlopen the library of superob, after the main one whose context it uses."""
     lib()
     return _load(SUPEROB_LIB_PATH, (SUPEROB_ARGTYPES,))
+
+
+def obsscan_lib():
+    """dlopen the library of the first scan, after the main one whose context and operator it uses."""
+    lib()
+    return _load(OBSSCAN_LIB_PATH, (OBSSCAN_ARGTYPES,))
+
+
+def obsscan_rows(bsna, slot_start, ip, islot=0):
+    """letkf_obsscan_rows: (first, count) of the list rows of subdomain ip in slot islot (0: the whole subdomain); bsna is the
+    int32 table (nprocs_d, nslots + 3) a scan returned"""
+    import numpy as np
+    t = np.ascontiguousarray(bsna, dtype=np.int32)
+    first, count = C.c_int64(), C.c_int64()
+    rc = obsscan_lib().letkf_obsscan_rows(t.ctypes.data, t.shape[0], slot_start, slot_start + t.shape[1] - 4, ip, islot,
+                                          C.addressof(first), C.addressof(count))
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_obsscan_rows: {lib().letkf_amd_last_error().decode()}")
+    return first.value, count.value
+
+
+def obsscan_slot_bounds(slot_start, slot_end, slot_base, slot_tinterval):
+    """letkf_obsscan_slot_bounds: (slot_lb, slot_ub), float64 [nslots]"""
+    import numpy as np
+    lb, ub = (np.zeros(max(slot_end - slot_start + 1, 0)) for _ in range(2))
+    rc = obsscan_lib().letkf_obsscan_slot_bounds(slot_start, slot_end, slot_base, slot_tinterval, lb.ctypes.data, ub.ctypes.data)
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_obsscan_slot_bounds: {lib().letkf_amd_last_error().decode()}")
+    return lb, ub
 
 
 def superob_default_methods(nobtype, nid):
@@ -1113,6 +1178,51 @@ class Context:
             setattr(o, name, _ptr(out.get(name)))
         self._check(superob_lib().letkf_superob_dev(self._c, C.byref(p), C.byref(o)))
         return out
+
+    def obsscan(self, files, dif, layout, slots, obsda_run=None, myrank_d=None, extras=True, out=None):
+        """letkf_obsscan_dev (include/letkf_amd_obsscan.h): obsope_cal's first scan over all rows of `files` (ObsFileRows; off, ri
+        and rj are read) and the device tensor dif.  layout = (nlon, nlat, ihalo, jhalo, prc_num_x, prc_num_y); slots =
+        (slot_start, slot_end, slot_base, slot_tinterval); obsda_run: host flags per file (None: all run).  Returns a dict: the
+        device tensors set, idx, qc (one per row of the files that run), the host int32 arrays bsn (nprocs_d, nslots + 2) and bsna
+        (nprocs_d, nslots + 3), and with extras the device tensors rank and slot per file row and, given myrank_d, own.  `out`:
+        the dict to write into (a device entry that is None stays NULL)."""
+        import numpy as np
+        import torch
+        nfile = files.nfile
+        off = np.ctypeslib.as_array(C.cast(files.off, C.POINTER(C.c_int64)), shape=(nfile + 1,))
+        run = None if obsda_run is None else np.ascontiguousarray(obsda_run, dtype=np.int32)
+        n = int(off[-1])
+        nlist = int(sum(off[f + 1] - off[f] for f in range(nfile) if run is None or run[f]))
+        p = ObsscanParams()
+        p.dif, p.obsda_run = _ptr(dif), None if run is None else run.ctypes.data
+        p.nlon, p.nlat, p.ihalo, p.jhalo, p.prc_num_x, p.prc_num_y = layout
+        p.slot_start, p.slot_end, p.slot_base, p.slot_tinterval = slots
+        p.myrank_d = 0 if myrank_d is None else myrank_d
+        nprocs, nb = p.prc_num_x * p.prc_num_y, p.slot_end - p.slot_start + 3
+        if out is None:
+            dev = dif.device
+            out = {name: torch.zeros(nlist, dtype=torch.int32, device=dev) for name in ("set", "idx", "qc")}
+            for name in ("rank", "slot", "own"):
+                want = extras and (name != "own" or myrank_d is not None)
+                out[name] = torch.zeros(n, dtype=torch.int32, device=dev) if want else None
+            out["bsn"] = np.zeros((nprocs, nb), dtype=np.int32)
+            out["bsna"] = np.zeros((nprocs, nb + 1), dtype=np.int32)
+        o = ObsscanOut()
+        for name, _ in ObsscanOut._fields_:
+            v = out.get(name)
+            setattr(o, name, v.ctypes.data if isinstance(v, np.ndarray) else _ptr(v))
+        self._check(obsscan_lib().letkf_obsscan_dev(self._c, C.byref(p), C.byref(files), C.byref(o)))
+        return out
+
+    def obsope_slot(self, scan, slot_start, ip, islot, params, files, fields, ensval, kld):
+        """letkf_obsope_slot_dev (include/letkf_amd_obsscan.h): the operator on the list rows of subdomain ip in slot islot of
+        `scan`, the dict Context.obsscan returned; ensval is indexed by the global list row."""
+        bsna = scan["bsna"]
+        l = ObsscanLists()
+        l.nprocs_d, l.slot_start, l.slot_end = bsna.shape[0], slot_start, slot_start + bsna.shape[1] - 4
+        l.bsna, l.set, l.idx, l.qc = bsna.ctypes.data, _ptr(scan["set"]), _ptr(scan["idx"]), _ptr(scan["qc"])
+        self._check(obsscan_lib().letkf_obsope_slot_dev(self._c, C.byref(l), ip, islot, C.byref(params), C.byref(files),
+                                                        C.byref(fields), _ptr(ensval), kld))
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),

@@ -2,7 +2,8 @@
 // buffers, the plumbing of the list-driven entries and the launch of the loop body.  Host side, not installed; beside them only
 // letkf_monit_entry.hip (the entries of include/letkf_amd_monit.h) and, from the libraries of the OSSE tools, of the simulator and
 // of superob, letkf_obsmake_entry.hip (include/letkf_amd_obsmake.h), letkf_obssim_entry.hip (include/letkf_amd_obssim.h) and
-// letkf_superob_entry.hip (include/letkf_amd_superob.h) include it.  Every function is defined in the one unit named above its
+// letkf_superob_entry.hip (include/letkf_amd_superob.h) include it, and obsscan/letkf_obsscan_entry.hip
+// (include/letkf_amd_obsscan.h) from the library of the first scan.  Every function is defined in the one unit named above its
 // declaration.
 #pragma once
 #include <hip/hip_runtime.h>
