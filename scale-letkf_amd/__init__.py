@@ -19,6 +19,7 @@ OSSE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_osse.so")   # the OSSE t
 OBSSIM_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obssim.so")   # the model-to-observation simulator (include/letkf_amd_obssim.h); links against the production library too
 SUPEROB_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_superob.so")   # superob (include/letkf_amd_superob.h); links against the production library too
 OBSSCAN_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsscan.so")   # obsope_cal's first scan (include/letkf_amd_obsscan.h); made by `make obsscan`, after the default goal
+MAPPROJ_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_mapproj.so")   # the map projection (include/letkf_amd_mapproj.h); made by `make mapproj`, in the same way
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -31,16 +32,18 @@ class LetkfError(RuntimeError):
 def build(force=False):
     """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
-    srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*"))
+    srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*")) + glob.glob(os.path.join(HERE, "csrc", "mapproj", "*"))
     srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
+    srcs = [s for s in srcs if os.path.isfile(s)]      # (a directory's time is that of its last new entry, not of a source)
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH)
+    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
         subprocess.check_call(["make", "-j4", "-C", HERE] + (["-B"] if force else []), stdout=2)
         subprocess.check_call(["make", "-j4", "-C", HERE, "obsscan"], stdout=2)   # (a goal of its own, after the default one)
+        subprocess.check_call(["make", "-j4", "-C", HERE, "mapproj"], stdout=2)   # (and so is this)
     return LIB_PATH
 
 
@@ -565,6 +568,37 @@ OBSSCAN_ARGTYPES = {
 OBSSCAN_MAX_BUCKETS = 1 << 22
 IQC_TIME, IQC_OUT_H = 97, 98
 
+
+class MapprojParams(C.Structure):
+    """letkf_mapproj_params (include/letkf_amd_mapproj.h): PARAM_MAPPROJ and what phys2ij reads of the grid; degrees and metres"""
+    _fields_ = ([("type", C.c_int32), ("reserved0", C.c_int32)] +
+                [(n, C.c_double) for n in ("basepoint_lon", "basepoint_lat", "basepoint_x", "basepoint_y", "lc_lat1", "lc_lat2",
+                                           "radius", "cxg1", "cyg1", "dx", "dy")])
+
+
+class Mapproj(C.Structure):
+    """letkf_mapproj (include/letkf_amd_mapproj.h): what letkf_mapproj_setup derives; plain data"""
+    _fields_ = ([("type", C.c_int32), ("reserved0", C.c_int32)] +
+                [(n, C.c_double) for n in ("hemisphere", "lon0", "c", "fact", "radius", "pole_x", "pole_y", "cxg1", "cyg1", "dx",
+                                           "dy")])
+
+
+# ... and of the ninth companion header include/letkf_amd_mapproj.h: the entries are exported by the library of the projection
+# (MAPPROJ_LIB_PATH, mapproj_lib()).  (The table's name does not end in ARGTYPES: tests/test_obsscan_binding.py counts the names
+# that do, and stays as it is.)
+MAPPROJ_VERSION = 1
+MAPPROJ_SIGNATURES = {
+    "letkf_mapproj_setup": [_VP, _VP],
+    "letkf_phys2ij_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
+    "letkf_ij2phys_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
+    "letkf_mapproj_grid_dev": [_VP, _VP, _I32, _I32, _I32, _I32, _F64, _F64, _VP, _VP, _VP],
+    "letkf_phys2ij_host": [_VP, _F64, _F64, _VP, _VP, _VP],
+    "letkf_ij2phys_host": [_VP, _F64, _F64, _VP, _VP, _VP],
+}
+MAPPROJ_LC = 1
+MAPPROJ_RADIUS_SCALE = 6.37122e6
+MAPPROJ_PI_REF = 3.1415926535
+
 _libs = {}
 
 
@@ -616,6 +650,43 @@ def obsscan_lib():
     """dlopen the library of the first scan, after the main one whose context and operator it uses."""
     lib()
     return _load(OBSSCAN_LIB_PATH, (OBSSCAN_ARGTYPES,))
+
+
+def mapproj_lib():
+    """dlopen the library of the map projection, after the main one whose context it uses."""
+    lib()
+    return _load(MAPPROJ_LIB_PATH, (MAPPROJ_SIGNATURES,))
+
+
+def mapproj_setup(basepoint_lon, basepoint_lat, basepoint_x, basepoint_y, lc_lat1, lc_lat2, cxg1, cyg1, dx, dy,
+                  radius=MAPPROJ_RADIUS_SCALE, type=MAPPROJ_LC):
+    """letkf_mapproj_setup: the derived constants (a Mapproj) of a Lambert conformal conic projection; degrees and metres"""
+    p, proj = MapprojParams(), Mapproj()
+    p.type = type
+    (p.basepoint_lon, p.basepoint_lat, p.basepoint_x, p.basepoint_y, p.lc_lat1, p.lc_lat2, p.radius, p.cxg1, p.cyg1, p.dx,
+     p.dy) = basepoint_lon, basepoint_lat, basepoint_x, basepoint_y, lc_lat1, lc_lat2, radius, cxg1, cyg1, dx, dy
+    rc = mapproj_lib().letkf_mapproj_setup(C.addressof(p), C.addressof(proj))
+    if rc != LETKF_OK:
+        raise LetkfError(f"letkf_mapproj_setup: {lib().letkf_amd_last_error().decode()}")
+    return proj
+
+
+def _mapproj_host(entry, proj, a, b, rotc):
+    u, v, r = C.c_double(), C.c_double(), (C.c_double * 2)()
+    rc = getattr(mapproj_lib(), entry)(C.addressof(proj), a, b, C.addressof(u), C.addressof(v), C.addressof(r) if rotc else None)
+    if rc != LETKF_OK:
+        raise LetkfError(f"{entry}: {lib().letkf_amd_last_error().decode()}")
+    return (u.value, v.value, (r[0], r[1])) if rotc else (u.value, v.value)
+
+
+def phys2ij_host(proj, lon, lat, rotc=False):
+    """letkf_phys2ij_host: (ri, rj) of one point in degrees, with rotc (ri, rj, (rotc0, rotc1))"""
+    return _mapproj_host("letkf_phys2ij_host", proj, lon, lat, rotc)
+
+
+def ij2phys_host(proj, ri, rj, rotc=False):
+    """letkf_ij2phys_host: (lon, lat) in degrees of one point, with rotc (lon, lat, (rotc0, rotc1))"""
+    return _mapproj_host("letkf_ij2phys_host", proj, ri, rj, rotc)
 
 
 def obsscan_rows(bsna, slot_start, ip, islot=0):
@@ -1223,6 +1294,37 @@ class Context:
         l.bsna, l.set, l.idx, l.qc = bsna.ctypes.data, _ptr(scan["set"]), _ptr(scan["idx"]), _ptr(scan["qc"])
         self._check(obsscan_lib().letkf_obsope_slot_dev(self._c, C.byref(l), ip, islot, C.byref(params), C.byref(files),
                                                         C.byref(fields), _ptr(ensval), kld))
+
+    def _mapproj_rows(self, entry, proj, a, b, rotc, out):
+        import torch
+        n = a.numel()
+        if out is None:
+            out = tuple(torch.empty(n, dtype=torch.float64, device=a.device) for _ in range(2))
+            out += (torch.empty((n, 2), dtype=torch.float64, device=a.device) if rotc else None,)
+        self._check(getattr(mapproj_lib(), entry)(self._c, C.addressof(proj), n, _ptr(a), _ptr(b), *(_ptr(t) for t in out)))
+        return out
+
+    def phys2ij(self, proj, lon, lat, rotc=True, out=None):
+        """letkf_phys2ij_dev (include/letkf_amd_mapproj.h): the device tensors lon, lat (float64, degrees) to (ri, rj, rotc): ri,
+        rj [n] and rotc [n, 2], or None without it.  `out`: the three tensors to write into (rotc may be None)."""
+        return self._mapproj_rows("letkf_phys2ij_dev", proj, lon, lat, rotc, out)
+
+    def ij2phys(self, proj, ri, rj, rotc=True, out=None):
+        """letkf_ij2phys_dev: the device tensors ri, rj to (lon, lat, rotc) in degrees, as phys2ij the other way"""
+        return self._mapproj_rows("letkf_ij2phys_dev", proj, ri, rj, rotc, out)
+
+    def mapproj_grid(self, proj, nlon, nlat, ihalo, jhalo, cx1, cy1, want=("lon", "lat", "rotc"), device=None, out=None):
+        """letkf_mapproj_grid_dev: lon2d, lat2d [nlat, nlon] in degrees and rotc2d [nlat, nlon, 2] of a subdomain whose GRID_CX(1)
+        / GRID_CY(1) are cx1 / cy1, as a dict with the keys of `want` (the others None); the layouts Context.obssim takes.
+        `out`: the dict to write into."""
+        import torch
+        if out is None:
+            dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+            out = {k: torch.empty((nlat, nlon) + ((2,) if k == "rotc" else ()), dtype=torch.float64, device=dev) if k in want else None
+                   for k in ("lon", "lat", "rotc")}
+        self._check(mapproj_lib().letkf_mapproj_grid_dev(self._c, C.addressof(proj), nlon, nlat, ihalo, jhalo, cx1, cy1,
+                                                         _ptr(out.get("lon")), _ptr(out.get("lat")), _ptr(out.get("rotc"))))
+        return out
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),

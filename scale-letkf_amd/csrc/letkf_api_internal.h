@@ -3,7 +3,8 @@
 // letkf_monit_entry.hip (the entries of include/letkf_amd_monit.h) and, from the libraries of the OSSE tools, of the simulator and
 // of superob, letkf_obsmake_entry.hip (include/letkf_amd_obsmake.h), letkf_obssim_entry.hip (include/letkf_amd_obssim.h) and
 // letkf_superob_entry.hip (include/letkf_amd_superob.h) include it, and obsscan/letkf_obsscan_entry.hip
-// (include/letkf_amd_obsscan.h) from the library of the first scan.  Every function is defined in the one unit named above its
+// (include/letkf_amd_obsscan.h) from the library of the first scan and mapproj/letkf_mapproj_entry.hip
+// (include/letkf_amd_mapproj.h) from the library of the map projection.  Every function is defined in the one unit named above its
 // declaration.
 #pragma once
 #include <hip/hip_runtime.h>
