@@ -20,6 +20,7 @@ OBSSIM_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obssim.so")   # the mo
 SUPEROB_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_superob.so")   # superob (include/letkf_amd_superob.h); links against the production library too
 OBSSCAN_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsscan.so")   # obsope_cal's first scan (include/letkf_amd_obsscan.h); made by `make obsscan`, after the default goal
 MAPPROJ_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_mapproj.so")   # the map projection (include/letkf_amd_mapproj.h); made by `make mapproj`, in the same way
+OBSFILE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsfile.so")   # the record codec of the observation files (include/letkf_amd_obsfile.h); made by `make obsfile`, in the same way
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -33,17 +34,19 @@ def build(force=False):
     """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*")) + glob.glob(os.path.join(HERE, "csrc", "mapproj", "*"))
+    srcs += glob.glob(os.path.join(HERE, "csrc", "obsfile", "*"))
     srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
     srcs = [s for s in srcs if os.path.isfile(s)]      # (a directory's time is that of its last new entry, not of a source)
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH)
+    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH, OBSFILE_LIB_PATH)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
         subprocess.check_call(["make", "-j4", "-C", HERE] + (["-B"] if force else []), stdout=2)
         subprocess.check_call(["make", "-j4", "-C", HERE, "obsscan"], stdout=2)   # (a goal of its own, after the default one)
         subprocess.check_call(["make", "-j4", "-C", HERE, "mapproj"], stdout=2)   # (and so is this)
+        subprocess.check_call(["make", "-j4", "-C", HERE, "obsfile"], stdout=2)   # (and this)
     return LIB_PATH
 
 
@@ -599,6 +602,51 @@ MAPPROJ_LC = 1
 MAPPROJ_RADIUS_SCALE = 6.37122e6
 MAPPROJ_PI_REF = 3.1415926535
 
+class ObsfileCols(C.Structure):
+    """letkf_obsfile_cols (include/letkf_amd_obsfile.h): the decoded columns of a conventional or radar file, device arrays"""
+    _fields_ = [(n, C.c_void_p) for n in ("elm", "typ", "lon", "lat", "lev", "dat", "err", "dif")]
+
+
+class ObsfileParams(C.Structure):
+    """letkf_obsfile_params (include/letkf_amd_obsfile.h): format 1 conventional, 2 radar"""
+    _fields_ = ([(n, C.c_int32) for n in ("format", "nrec", "big_endian", "missing", "proj_given", "reserved0")] +
+                [(n, C.c_double) for n in ("obserr_tcp", "obserr_tcx", "obserr_tcy")])
+
+
+class ObsdaParams(C.Structure):
+    """letkf_obsda_params (include/letkf_amd_obsfile.h)"""
+    _fields_ = ([(n, C.c_int32) for n in ("nrec", "big_endian", "nmem", "finish", "member", "reserved0")] +
+                [(n, C.c_int64) for n in ("nobs", "kld")])
+
+
+class ObsdaCols(C.Structure):
+    """letkf_obsda_cols (include/letkf_amd_obsfile.h): the obsda arrays, device arrays"""
+    _fields_ = [(n, C.c_void_p) for n in ("set", "idx", "qc", "ensval", "lev", "val2")]
+
+
+class ObsfileRows(C.Structure):
+    """letkf_obsfile_rows (include/letkf_amd_obsfile.h): off is a HOST int64 array, the columns device arrays"""
+    _fields_ = ([("nfile", C.c_int32), ("reserved0", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("off", "elm", "typ", "lon", "lat", "lev", "dat", "err", "dif")])
+
+
+# ... and of the tenth companion header include/letkf_amd_obsfile.h: the entries are exported by the library of the record codec
+# (OBSFILE_LIB_PATH, obsfile_lib()).  (SIGNATURES, as the projection's table: the frozen binding tests count the names that end in
+# ARGTYPES.)
+OBSFILE_VERSION = 1
+OBSFILE_SIGNATURES = {
+    "letkf_obsfile_count": [_I32, _I32, _I64, _VP],
+    "letkf_obsfile_bytes": [_I32, _I32, _I64, _VP],
+    "letkf_obs_decode_dev": [_VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP],
+    "letkf_obs_encode_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP],
+    "letkf_obsda_assemble_dev": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_obsda_encode_dev": [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP],
+    "letkf_obsdep_encode_dev": [_VP, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+}
+OBSFILE_CONV, OBSFILE_RADAR, OBSFILE_OBSDA, OBSFILE_DEP = 1, 2, 3, 4
+OBSFILE_TILE_ROWS, OBSFILE_TILE_MEMBERS, OBSFILE_MAX_MEMBERS, OBSFILE_TYP_RADAR = 64, 16, 65536, 22
+OBSFILE_COLUMNS = ("elm", "typ", "lon", "lat", "lev", "dat", "err", "dif")
+
 _libs = {}
 
 
@@ -656,6 +704,42 @@ def mapproj_lib():
     """dlopen the library of the map projection, after the main one whose context it uses."""
     lib()
     return _load(MAPPROJ_LIB_PATH, (MAPPROJ_SIGNATURES,))
+
+
+def obsfile_lib():
+    """dlopen the library of the record codec, after the main one whose context and scan it uses."""
+    lib()
+    return _load(OBSFILE_LIB_PATH, (OBSFILE_SIGNATURES,))
+
+
+def _obsfile_size(entry, fmt, nrec, n):
+    out = C.c_int64()
+    rc = getattr(obsfile_lib(), entry)(fmt, nrec, n, C.addressof(out))
+    if rc != LETKF_OK:
+        raise LetkfError(f"{entry}: {lib().letkf_amd_last_error().decode()}")
+    return out.value
+
+
+def obsfile_count(fmt, nrec, nbytes):
+    """letkf_obsfile_count: the rows of a file of nbytes (get_nobs / get_nobs_radar); raises where it is no whole number"""
+    return _obsfile_size("letkf_obsfile_count", fmt, nrec, nbytes)
+
+
+def obsfile_bytes(fmt, nrec, nrows):
+    """letkf_obsfile_bytes: the bytes of a file image of nrows rows"""
+    return _obsfile_size("letkf_obsfile_bytes", fmt, nrec, nrows)
+
+
+def obsfile_rows(off, cols):
+    """an ObsfileRows over the device columns of `cols` (a dict with OBSFILE_COLUMNS) and the HOST offsets off [nfile + 1]; the
+    struct keeps both alive"""
+    import numpy as np
+    f = ObsfileRows()
+    f._keep = (np.ascontiguousarray(off, dtype=np.int64), dict(cols))
+    f.nfile, f.off = len(f._keep[0]) - 1, f._keep[0].ctypes.data
+    for n in OBSFILE_COLUMNS:
+        setattr(f, n, cols[n].data_ptr())
+    return f
 
 
 def mapproj_setup(basepoint_lon, basepoint_lat, basepoint_x, basepoint_y, lc_lat1, lc_lat2, cxg1, cyg1, dx, dy,
@@ -1325,6 +1409,130 @@ class Context:
         self._check(mapproj_lib().letkf_mapproj_grid_dev(self._c, C.addressof(proj), nlon, nlat, ihalo, jhalo, cx1, cy1,
                                                          _ptr(out.get("lon")), _ptr(out.get("lat")), _ptr(out.get("rotc"))))
         return out
+
+    # ---- the record codec (include/letkf_amd_obsfile.h); an image is a device tensor of the file's bytes, of any dtype
+    @staticmethod
+    def _image_bytes(image):
+        return image.numel() * image.element_size()
+
+    def obs_decode(self, image, fmt, nrec=None, big_endian=False, proj=None, obserr_tc=(5.0e2, 50.0e3, 50.0e3), want=OBSFILE_COLUMNS,
+                   meta=True, check=False, out=None):
+        """letkf_obs_decode_dev: a conventional (fmt 1) or radar (fmt 2) file image to a dict of the columns of `want` (int32 elm,
+        typ; float64 the rest; the others None), with "meta" (float64 [3], radar with meta=True) and "nbad" (check=True).  `out`: a
+        dict of tensors to write into."""
+        import numpy as np
+        import torch
+        nrec = nrec if nrec is not None else 8
+        n = obsfile_count(fmt, nrec, self._image_bytes(image))
+        p = ObsfileParams()
+        p.format, p.nrec, p.big_endian, p.proj_given = fmt, nrec, int(big_endian), int(proj is not None)
+        p.obserr_tcp, p.obserr_tcx, p.obserr_tcy = obserr_tc
+        if out is None:
+            out = {k: torch.empty(n, dtype=torch.int32 if k in ("elm", "typ") else torch.float64, device=image.device) if k in want else None
+                   for k in OBSFILE_COLUMNS}
+        o = ObsfileCols()
+        for k in OBSFILE_COLUMNS:
+            setattr(o, k, _ptr(out.get(k)))
+        head = np.zeros(3) if (meta and fmt == OBSFILE_RADAR) else None
+        nbad = C.c_int64(-1)
+        self._check(obsfile_lib().letkf_obs_decode_dev(self._c, C.addressof(p), C.addressof(proj) if proj is not None else None, _ptr(image),
+                                                       n, C.addressof(o), _hptr(head), C.addressof(nbad) if check else None))
+        res = dict(out)
+        res["meta"], res["nbad"] = head, nbad.value if check else None
+        return res
+
+    def obs_encode(self, cols, fmt, nrec=None, big_endian=False, missing=True, meta=None, out=None):
+        """letkf_obs_encode_dev: the columns (a dict of device tensors) to (image, nwritten): image a uint8 device tensor sized for
+        every row, of which the first obsfile_bytes(fmt, nrec, nwritten) are the file.  missing=False leaves the undefined rows
+        out (one read-back)."""
+        import numpy as np
+        import torch
+        nrec = nrec if nrec is not None else 8
+        n = cols["elm"].numel()
+        p = ObsfileParams()
+        p.format, p.nrec, p.big_endian, p.missing = fmt, nrec, int(big_endian), int(missing)
+        c = ObsfileCols()
+        for k in OBSFILE_COLUMNS:
+            setattr(c, k, _ptr(cols.get(k)))
+        if out is None:
+            out = torch.empty(obsfile_bytes(fmt, nrec, n), dtype=torch.uint8, device=cols["elm"].device)
+        head = None if meta is None else np.ascontiguousarray(meta, dtype=np.float64)
+        nw = C.c_int64(-1)
+        self._check(obsfile_lib().letkf_obs_encode_dev(self._c, C.addressof(p), n, C.addressof(c), _hptr(head), _ptr(out), C.addressof(nw)))
+        return out, nw.value
+
+    def obsda_assemble(self, images, nobs, kld, col=None, nrec=4, big_endian=False, is_member=None, member=0, finish=False, check=False,
+                       out=None):
+        """letkf_obsda_assemble_dev: the obsda file images (device tensors of nobs records each) into a dict set, idx, qc (int32
+        [nobs]), ensval (float64 [nobs, kld]) and, under nrec 6, lev, val2; image m goes to column col[m] (default m).  `out`: the
+        dict to write into (qc, lev and val2 are INOUT; a fresh qc starts at 0, as obs_da_value_allocate leaves it).  check=True
+        adds "ninconsistent" and "nbad"."""
+        import numpy as np
+        import torch
+        nmem = len(images)
+        p = ObsdaParams()
+        p.nrec, p.big_endian, p.nmem, p.finish, p.member, p.nobs, p.kld = nrec, int(big_endian), nmem, int(finish), member, nobs, kld
+        if out is None:
+            dev = images[0].device
+            out = {k: torch.zeros(nobs, dtype=torch.int32, device=dev) for k in ("set", "idx", "qc")}
+            out["ensval"] = torch.zeros((nobs, kld), dtype=torch.float64, device=dev)
+            for k in ("lev", "val2"):
+                out[k] = torch.zeros(nobs, dtype=torch.float64, device=dev) if nrec == 6 else None
+        o = ObsdaCols()
+        for k, _ in ObsdaCols._fields_:
+            setattr(o, k, _ptr(out.get(k)))
+        ptrs = (C.c_void_p * max(nmem, 1))(*[t.data_ptr() for t in images])
+        cols = np.ascontiguousarray(np.arange(nmem) if col is None else col, dtype=np.int32)
+        flags = None if is_member is None else np.ascontiguousarray(is_member, dtype=np.int32)
+        ninc, nbad = C.c_int64(-1), C.c_int64(-1)
+        self._check(obsfile_lib().letkf_obsda_assemble_dev(self._c, C.addressof(p), C.addressof(ptrs), _hptr(cols), _hptr(flags),
+                                                           C.addressof(o), C.addressof(ninc) if check else None,
+                                                           C.addressof(nbad) if check else None))
+        res = dict(out)
+        res["ninconsistent"], res["nbad"] = (ninc.value, nbad.value) if check else (None, None)
+        return res
+
+    def obsda_encode(self, set, idx, qc, ensval=None, col=-1, val=None, lev=None, val2=None, nrec=4, big_endian=False, out=None):
+        """letkf_obsda_encode_dev: write_obs_da's file image (a uint8 device tensor) for column col of ensval [nobs, kld], or for
+        val when col < 0"""
+        import torch
+        n = set.numel()
+        if out is None:
+            out = torch.empty(obsfile_bytes(OBSFILE_OBSDA, nrec, n), dtype=torch.uint8, device=set.device)
+        kld = ensval.shape[1] if ensval is not None and ensval.dim() == 2 else 0
+        self._check(obsfile_lib().letkf_obsda_encode_dev(self._c, nrec, int(big_endian), n, _ptr(set), _ptr(idx), _ptr(qc), _ptr(ensval), kld,
+                                                         col, _ptr(val), _ptr(lev), _ptr(val2), _ptr(out)))
+        return out
+
+    def obsdep_encode(self, set, idx, qc, omb, oma, files, big_endian=False, out=None):
+        """letkf_obsdep_encode_dev: write_obs_dep's file image (a uint8 device tensor); files: an ObsfileRows (obsfile_rows())"""
+        import torch
+        n = set.numel()
+        if out is None:
+            out = torch.empty(obsfile_bytes(OBSFILE_DEP, 11, n), dtype=torch.uint8, device=set.device)
+        self._check(obsfile_lib().letkf_obsdep_encode_dev(self._c, int(big_endian), n, _ptr(set), _ptr(idx), _ptr(qc), _ptr(omb), _ptr(oma),
+                                                          C.addressof(files), _ptr(out)))
+        return out
+
+    def read_obs_file(self, path, fmt, device=None, **kw):
+        """numpy.fromfile -> device -> obs_decode: one call per observation file; kw as obs_decode's"""
+        import numpy as np
+        import torch
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        return self.obs_decode(torch.from_numpy(np.fromfile(path, dtype=np.uint8)).to(dev), fmt, **kw)
+
+    def read_obsda_files(self, paths, kld=None, nrec=4, device=None, **kw):
+        """numpy.fromfile -> device -> obsda_assemble: one call per set of obsda files (one per member, the mean's where col says);
+        kw as obsda_assemble's"""
+        import numpy as np
+        import torch
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        images = [torch.from_numpy(np.fromfile(f, dtype=np.uint8)).to(dev) for f in paths]
+        nobs = obsfile_count(OBSFILE_OBSDA, nrec, self._image_bytes(images[0]))
+        for f, t in zip(paths, images):
+            if self._image_bytes(t) != self._image_bytes(images[0]):
+                raise LetkfError(f"{f}: {self._image_bytes(t)} bytes, {paths[0]} has {self._image_bytes(images[0])}")
+        return self.obsda_assemble(images, nobs, kld if kld is not None else len(images), nrec=nrec, **kw)
 
     def set_obs_finish(self, table, n_all, recv, tot_g=None):
         self._check(self._l.letkf_set_obs_finish_dev(self._c, table._h, _ptr(n_all), _ptr(tot_g),
