@@ -21,6 +21,7 @@ SUPEROB_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_superob.so")   # supe
 OBSSCAN_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsscan.so")   # obsope_cal's first scan (include/letkf_amd_obsscan.h); made by `make obsscan`, after the default goal
 MAPPROJ_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_mapproj.so")   # the map projection (include/letkf_amd_mapproj.h); made by `make mapproj`, in the same way
 OBSFILE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsfile.so")   # the record codec of the observation files (include/letkf_amd_obsfile.h); made by `make obsfile`, in the same way
+NOBSOUT_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_nobsout.so")   # NOBS_OUT (include/letkf_amd_nobsout.h); made by `make nobsout`, in the same way
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -34,12 +35,12 @@ def build(force=False):
     """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*")) + glob.glob(os.path.join(HERE, "csrc", "mapproj", "*"))
-    srcs += glob.glob(os.path.join(HERE, "csrc", "obsfile", "*"))
+    srcs += glob.glob(os.path.join(HERE, "csrc", "obsfile", "*")) + glob.glob(os.path.join(HERE, "csrc", "nobsout", "*"))
     srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
     srcs = [s for s in srcs if os.path.isfile(s)]      # (a directory's time is that of its last new entry, not of a source)
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH, OBSFILE_LIB_PATH)
+    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH, OBSFILE_LIB_PATH, NOBSOUT_LIB_PATH)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
@@ -47,6 +48,7 @@ def build(force=False):
         subprocess.check_call(["make", "-j4", "-C", HERE, "obsscan"], stdout=2)   # (a goal of its own, after the default one)
         subprocess.check_call(["make", "-j4", "-C", HERE, "mapproj"], stdout=2)   # (and so is this)
         subprocess.check_call(["make", "-j4", "-C", HERE, "obsfile"], stdout=2)   # (and this)
+        subprocess.check_call(["make", "-j4", "-C", HERE, "nobsout"], stdout=2)   # (and this)
     return LIB_PATH
 
 
@@ -647,6 +649,23 @@ OBSFILE_CONV, OBSFILE_RADAR, OBSFILE_OBSDA, OBSFILE_DEP = 1, 2, 3, 4
 OBSFILE_TILE_ROWS, OBSFILE_TILE_MEMBERS, OBSFILE_MAX_MEMBERS, OBSFILE_TYP_RADAR = 64, 16, 65536, 22
 OBSFILE_COLUMNS = ("elm", "typ", "lon", "lat", "lev", "dat", "err", "dif")
 
+
+
+class NobsoutParams(C.Structure):
+    """letkf_nobsout_params (include/letkf_amd_nobsout.h): elm_u_ctype / typ_ctype are HOST int32 arrays"""
+    _fields_ = ([(n, C.c_int32) for n in ("nctype", "nobtype", "uid_ref", "uid_re0", "uid_vr", "typ_radar")] +
+                [("pick", C.c_int32 * 5), ("reserved0", C.c_int32), ("elm_u_ctype", C.c_void_p), ("typ_ctype", C.c_void_p)])
+
+
+# ... and of the eleventh companion header include/letkf_amd_nobsout.h: the entries are exported by the library of NOBS_OUT
+# (NOBSOUT_LIB_PATH, nobsout_lib()).  (SIGNATURES, as the two tables before it.)
+NOBSOUT_VERSION = 1
+NOBSOUT_SIGNATURES = {
+    "letkf_das_columns_nobs_dev": [_VP, _VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP],
+    "letkf_nobs_fields_dev": [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _I64],
+}
+NOBSOUT_MAX_CTYPE, NOBSOUT_MAX_OBTYPE, NOBSOUT_NFIELDS = 64, 32, 11
+
 _libs = {}
 
 
@@ -710,6 +729,12 @@ def obsfile_lib():
     """dlopen the library of the record codec, after the main one whose context and scan it uses."""
     lib()
     return _load(OBSFILE_LIB_PATH, (OBSFILE_SIGNATURES,))
+
+
+def nobsout_lib():
+    """dlopen the library of NOBS_OUT, after the main one whose context and main loop it uses."""
+    lib()
+    return _load(NOBSOUT_LIB_PATH, (NOBSOUT_SIGNATURES,))
 
 
 def _obsfile_size(entry, fmt, nrec, n):
@@ -1012,6 +1037,37 @@ class Context:
                            iv_q_last, status, nsweep, rtps_infl_out, warm_run, var_mask, infl_sv)
         self._check(self._l.letkf_das_columns_dev(self._c, C.byref(a), C.byref(tables), nij1, nlev, _ptr(rig), _ptr(rjg),
                                                   _ptr(rlev), _ptr(rz), list_bytes, _ptr(nobs_out)))
+
+    def das_columns_nobs(self, k, nv, tables, nij1, nlev, rig, rjg, rlev, rz, ensval, kld, dep, infl, gues, anal, sp, sm, sv,
+                         list_bytes=0, nobs_out=None, beta=None, det_run=False, infl_adaptive=False, relax_to_inflated_prior=False,
+                         relax_alpha=0.0, relax_alpha_spread=0.0, q_update_top=0.0, q_sprd_max=0.0, iv_p=4, iv_q_first=5,
+                         iv_q_last=10, status=None, nsweep=None, rtps_infl_out=None, warm_run=0, var_mask=0, infl_sv=0,
+                         nobs_ctype=None, cutd_ctype=None):
+        """letkf_das_columns_nobs_dev (include/letkf_amd_nobsout.h): das_columns with the NOBS_OUT diagnostics of its points,
+        nobs_ctype int32 / cutd_ctype float64 [nij1*nlev][nctype] (either may be None), out of the search passes the call runs
+        anyway; zeros where beta = 0."""
+        a = self._das_args(k, nv, nij1 * nlev, ensval, kld, dep, infl, gues, anal, sp, sm, sv, beta, det_run, infl_adaptive,
+                           relax_to_inflated_prior, relax_alpha, relax_alpha_spread, q_update_top, q_sprd_max, iv_p, iv_q_first,
+                           iv_q_last, status, nsweep, rtps_infl_out, warm_run, var_mask, infl_sv)
+        self._check(nobsout_lib().letkf_das_columns_nobs_dev(self._c, C.addressof(a), C.addressof(tables), nij1, nlev, _ptr(rig),
+                                                             _ptr(rjg), _ptr(rlev), _ptr(rz), list_bytes, _ptr(nobs_out),
+                                                             _ptr(nobs_ctype), _ptr(cutd_ctype)))
+
+    def nobs_fields(self, npts, elm_u_ctype, typ_ctype, nobs_ctype, cutd_ctype=None, work3dn=None, fields=None, sp=1, sv=None,
+                    nobtype=24, uid_ref=9, uid_re0=10, uid_vr=11, typ_radar=22, pick=(1, 3, 4, 8, 22)):
+        """letkf_nobs_fields_dev (include/letkf_amd_nobsout.h): work3dn [npts][nobtype + 6] and / or the eleven fields, element
+        (p, f) at p*sp + f*sv (sv = None: npts, the (nij1, nlev, 11) array), from the diagnostics of das_columns_nobs;
+        elm_u_ctype / typ_ctype are host sequences (1-based, as obs_table_info gives them)."""
+        import numpy as np
+        eu = np.ascontiguousarray(elm_u_ctype, dtype=np.int32)
+        ty = np.ascontiguousarray(typ_ctype, dtype=np.int32)
+        p = NobsoutParams()
+        p.nctype, p.nobtype = len(eu), nobtype
+        p.uid_ref, p.uid_re0, p.uid_vr, p.typ_radar = uid_ref, uid_re0, uid_vr, typ_radar
+        p.pick = (C.c_int32 * 5)(*[int(v) for v in pick])
+        p.elm_u_ctype, p.typ_ctype = eu.ctypes.data, ty.ctypes.data
+        self._check(nobsout_lib().letkf_nobs_fields_dev(self._c, C.addressof(p), npts, _ptr(nobs_ctype), _ptr(cutd_ctype), _ptr(work3dn),
+                                                        _ptr(fields), sp, npts if sv is None else sv))
 
     def das_interp(self, k, nv, tables, nx, ny, nlev, stride_x, stride_y, rig, rjg, rlev, rz, ensval, kld, dep, infl, gues,
                    anal, sp, sm, sv, ws_bytes=0, nobs_coarse=None, npts=None, beta=None, det_run=False, infl_adaptive=False,

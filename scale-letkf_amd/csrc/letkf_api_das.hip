@@ -112,25 +112,12 @@ int das_points_impl(letkf_ctx* c, const letkf_das_args* g, const letkf_search_ta
   return launch(c, a, g->warm_run < 0 ? 0 : g->warm_run, g->warm_stride);
 }
 
-}  // namespace letkf::api
-
-extern "C" {
-
-int letkf_das_points_dev(letkf_ctx* c, const letkf_das_args* g) try {
-  return das_points_impl(c, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-} LETKF_ENTRY_END(letkf_das_points_dev)
-
-int letkf_das_points_fused_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const double* ri,
-                               const double* rj, const double* rlev, const double* rz, int32_t* nobs_out) try {
-  if (!t) return fail(LETKF_E_INVALID, "tables is NULL");
-  return das_points_impl(c, g, t, ri, rj, rlev, rz, nobs_out);
-} LETKF_ENTRY_END(letkf_das_points_fused_dev)
-
-// (3c) das_letkf's main loop for a whole subdomain: column search + loop body by slabs of levels whose lists fit a
-// workspace of the library (scale/letkf/letkf_tools.f90:313, the level loop)
-int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, int64_t nij1, int32_t nlev,
-                          const double* rig, const double* rjg, const double* rlev, const double* rz, int64_t list_bytes,
-                          int32_t* nobs_out) try {
+// das_letkf's main loop for a whole subdomain: column search + loop body by slabs of levels whose lists fit a workspace of the
+// library (scale/letkf/letkf_tools.f90:313, the level loop).  letkf_das_columns_dev is this with d = NULL; with d
+// (letkf_das_columns_nobs_dev, include/letkf_amd_nobsout.h) the searches this function runs anyway also write nobsl_t / cutd_t.
+int das_columns_impl(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, int64_t nij1, int32_t nlev,
+                     const double* rig, const double* rjg, const double* rlev, const double* rz, int64_t list_bytes,
+                     int32_t* nobs_out, DasColumnsDiag* d) {
   if (int rc = check_ctx(c)) return rc;
   if (!g || !t) return fail(LETKF_E_INVALID, "args / tables is NULL");
   if (nij1 < 1 || nlev < 1 || g->npts != nij1 * (int64_t)nlev) return fail(LETKF_E_INVALID, "npts must be nij1 * nlev");
@@ -140,6 +127,22 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
   if (int rc = das_args_check(g, false)) return rc;
   const int64_t npts = g->npts;
   if (list_bytes <= 0) list_bytes = (int64_t)8 << 30;
+  // ---- the diagnostics, where asked for: nobsl_t from whichever search pass selects anyway, cutd_t from the limited kernels;
+  // tables without a limit have the criterion's default cut-off everywhere, which the caller fills (d->cutd_from_tables)
+  int32_t* const dn = d ? d->nobs_ctype : nullptr;
+  double* dc = d ? d->cutd_ctype : nullptr;
+  bool dlimited = false;
+  if (dn || dc) {
+    if (t->nctype < 1 || t->ngroup < 1 || t->criterion < 1 || t->criterion > 3)
+      return fail(LETKF_E_INVALID, "bad nctype / ngroup / criterion");
+    if (int rc = tables_limited(c, t, &dlimited)) return rc;
+    if (!dlimited) {
+      d->cutd_from_tables = dc != nullptr;
+      dc = nullptr;
+    }
+  }
+  // (the unlimited column kernel writes the types it walks: the others keep obs_local's initial zeros, :1380-1383)
+  auto zero_diag = [&]() { return dn && !dlimited ? hipMemsetAsync(dn, 0, (size_t)npts * t->nctype * 4, c->stream) : hipSuccess; };
   // ---- the list-free route: where the one-wave kernel serves the call and no combined type has a limit, the horizontal half of
   // obs_local is done once per COLUMN (32 B per survivor) and the vertical half inside the loop body kernel -- no count pass
   // over the levels, no 20 B per (point, observation) written and read back.  Same weights, same order, same analysis to the
@@ -179,7 +182,18 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
         if (int rc = das_points_impl(c, &a, t, nullptr, nullptr, rlev, rz, nobs_out, &sview)) return rc;
         c0 = c1;
       }
-      if (take) return LETKF_OK;
+      if (take) {
+        // (no search by point ran: the unlimited column kernel's count pass, its counts into the scratch buffer the loop is done with)
+        if (dn) {
+          ScanWs cw;
+          if (int rc = scan_ws(c, &c->scratch, (size_t)npts, 0, &cw)) return rc;
+          HIP_TRY(zero_diag());
+          if (int rc = letkf_obs_search_columns_dev(c, t, nij1, nlev, rig, rjg, rlev, rz, 0, cw.counts, nullptr, nullptr, nullptr, nullptr,
+                                                    dn, nullptr))
+            return rc;
+        }
+        return LETKF_OK;
+      }
     }
   }
   // (the searches below -- one count pass, a fill pass per slab -- share the ring-ordered survivors of the dense limited case)
@@ -190,13 +204,21 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
   if (int rc = report_counts(c, sw.counts, npts, g->beta, nobs_out)) return rc;
   if (int rc = offsets_to_host(c, sw, (size_t)nij1)) return rc;
   const std::vector<int64_t>& lev_off = sw.hoff;
+  HIP_TRY(zero_diag());
   // ---- slabs of levels: as many as fit the list workspace (20 B per entry)
   int l0 = 0;
   while (l0 < nlev) {
     const int l1 = (int)chunk_end(lev_off, l0, nlev, 1, 20, list_bytes);
     const int64_t p0 = (int64_t)l0 * nij1, np = (int64_t)(l1 - l0) * nij1;
     ListSlab ls;
-    if (int rc = fill_columns(c, t, nij1, l0, l1, rig, rjg, rlev, rz, sw, &ls)) return rc;
+    if (!dn && !dc) {
+      if (int rc = fill_columns(c, t, nij1, l0, l1, rig, rjg, rlev, rz, sw, &ls)) return rc;
+    } else {   // (fill_columns with the diagnostics of the slab's points)
+      if (int rc = list_slab(c, lev_off[(size_t)l0], lev_off[(size_t)l1], &ls)) return rc;
+      if (int rc = letkf_obs_search_columns_dev(c, t, nij1, l1 - l0, rig, rjg, rlev + p0, rz + p0, 1, nullptr, sw.off + p0, ls.idx, ls.rd,
+                                                ls.rl, dn ? dn + p0 * t->nctype : nullptr, dc ? dc + p0 * t->nctype : nullptr))
+        return rc;
+    }
     letkf_das_args a = *g;
     a.npts = np;
     a.obs_off = sw.off + p0;
@@ -217,6 +239,27 @@ int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_sea
     l0 = l1;
   }
   return LETKF_OK;
+}
+
+}  // namespace letkf::api
+
+extern "C" {
+
+int letkf_das_points_dev(letkf_ctx* c, const letkf_das_args* g) try {
+  return das_points_impl(c, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+} LETKF_ENTRY_END(letkf_das_points_dev)
+
+int letkf_das_points_fused_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const double* ri,
+                               const double* rj, const double* rlev, const double* rz, int32_t* nobs_out) try {
+  if (!t) return fail(LETKF_E_INVALID, "tables is NULL");
+  return das_points_impl(c, g, t, ri, rj, rlev, rz, nobs_out);
+} LETKF_ENTRY_END(letkf_das_points_fused_dev)
+
+// (3c) das_letkf's main loop for a whole subdomain (das_columns_impl above)
+int letkf_das_columns_dev(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, int64_t nij1, int32_t nlev,
+                          const double* rig, const double* rjg, const double* rlev, const double* rz, int64_t list_bytes,
+                          int32_t* nobs_out) try {
+  return das_columns_impl(c, g, t, nij1, nlev, rig, rjg, rlev, rz, list_bytes, nobs_out, nullptr);
 } LETKF_ENTRY_END(letkf_das_columns_dev)
 
 // (3d) weight interpolation (include/letkf_amd_interp.h): letkf_core at the coarse points of a tile by slabs of levels -- the

@@ -4,7 +4,8 @@
 // of superob, letkf_obsmake_entry.hip (include/letkf_amd_obsmake.h), letkf_obssim_entry.hip (include/letkf_amd_obssim.h) and
 // letkf_superob_entry.hip (include/letkf_amd_superob.h) include it, and obsscan/letkf_obsscan_entry.hip
 // (include/letkf_amd_obsscan.h) from the library of the first scan and mapproj/letkf_mapproj_entry.hip
-// (include/letkf_amd_mapproj.h) from the library of the map projection.  Every function is defined in the one unit named above its
+// (include/letkf_amd_mapproj.h) from the library of the map projection, and nobsout/letkf_nobsout_entry.hip
+// (include/letkf_amd_nobsout.h) from the library of NOBS_OUT.  Every function is defined in the one unit named above its
 // declaration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -171,6 +172,18 @@ struct SurvivorView {
 int das_args_check(const letkf_das_args* g, bool lists);
 int das_points_impl(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, const double* ri, const double* rj,
                     const double* rlev, const double* rz, int32_t* nobs_out, const SurvivorView* sview = nullptr);
+// (letkf_das_columns_dev is das_columns_impl with d = NULL.  With d -- nobsout/letkf_nobsout_entry.hip, from the library of
+// include/letkf_amd_nobsout.h -- the search passes of the call also write nobsl_t / cutd_t of its points, dev [npts][nctype], either
+// may be NULL; at return cutd_from_tables says that no combined type has a limit and cutd_ctype is still to be filled with the
+// criterion's default, which is the caller's kernel.  Points with beta = 0 are not zeroed here either.)
+struct DasColumnsDiag {
+  int32_t* nobs_ctype;
+  double* cutd_ctype;
+  bool cutd_from_tables;
+};
+int das_columns_impl(letkf_ctx* c, const letkf_das_args* g, const letkf_search_tables* t, int64_t nij1, int32_t nlev,
+                     const double* rig, const double* rjg, const double* rlev, const double* rz, int64_t list_bytes,
+                     int32_t* nobs_out, DasColumnsDiag* d);
 
 // ---- letkf_api_efso.hip
 int64_t efso_entry_bytes(int nterm);
