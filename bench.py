@@ -9,11 +9,16 @@ eigen-solve, relaxation, transform of the nv = 11 variables).  At N = 1 the work
 tile of that size (weak scaling) and each step starts with the path's one exchange: the all-gather of the
 observation-table shards (the localisation-halo exchange of scale/letkf/letkf_obs.f90:1036-1046).
 
-Prints ONE JSON line on rank 0: the contract fields, `roofline` for the dominant kernel (its name and average launch
-duration come from the library: HIP events on the launch stream), `cpu_baseline` (the oracle's OpenMP restatement on a
-bounded sample of the same points, kind "port") with `parity_sample_max_rel` = the GPU analysis against that very
-oracle run (exit status 3 if it exceeds 1e-10), and `cpu_baseline_reference` (the reference's own letkf_core compiled
-into oracle/_ref, kind "reference", when that library travelled with the repository).
+Prints ONE JSON line on rank 0: the contract fields and `roofline` for the dominant kernel (its name and average launch
+duration come from the library: HIP events on the launch stream, taken during the timed steps themselves).
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds everything that takes work of its own, and the line then also carries: `cpu_baseline` (the oracle's OpenMP
+restatement on a bounded sample of the same points, kind "port") with `parity_sample_max_rel` = the GPU analysis against
+that very oracle run (exit status 3 if it exceeds 1e-10), `cpu_baseline_reference` (the reference's own letkf_core
+compiled into oracle/_ref, kind "reference", when that library travelled with the repository), `search_ms` (obs_local
+timed by itself) and the check of the device search's list sizes against the torch builder's.  Without --full those
+fields are null.  The steps, their inputs, `value`, `ms_per_step` and the dumped arrays are the same either way.
 """
 import argparse
 import json
@@ -37,8 +42,12 @@ def main():
                          "scales (mean level spacing / vertical scale against dx / horizontal scale)")
     ap.add_argument("--warm-run", type=int, default=0, help="run length (letkf_das_args.warm_run; 0 = library default)")
     ap.add_argument("--workload", default="C2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines and the parity sample against the oracle (exit status 3 above "
+                         "1e-10), obs_local timed by itself (search_ms), and the torch builder's lists as a check of the device "
+                         "search's sizes and for the checkers; without it those fields of the line are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: neither CPU baseline, no parity sample")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: the length of the CPU baseline's run")
     ap.add_argument("--relax", default="rtps", choices=["rtps", "rtpp", "none"])
     ap.add_argument("--list-gb", type=float, default=8.0, help="--lists pipeline: list workspace of the library in GiB")
     ap.add_argument("--lists", default="columns", choices=["columns", "search", "torch", "fused", "pipeline"],
@@ -168,7 +177,7 @@ def main():
                 "metric": "grid-point LETKF solves/sec", "value": r["npts_total"] * args.steps / r["elapsed"],
                 "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": r["elapsed"] / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(args.full),
                 "config": {"workload": f"{args.workload}: ONE {bw.CONFIGS[args.workload]['nx']}x{bw.CONFIGS[args.workload]['ny']}x"
                                        f"{bw.CONFIGS[args.workload]['nz']} domain as {r['tiles']}, k={k_}, nv={nv_}, mean "
                                        f"{r['n_mean']:.1f} local obs/point, relax={args.relax}; per step and rank: mesh sort, "
@@ -195,7 +204,10 @@ def main():
         sys.exit("--level-slab: the column search inside the step, one GPU, the reference's state layout")
     if args.no_torch_lists and args.lists not in ("fused", "pipeline"):
         sys.exit("--no-torch-lists goes with --lists fused / pipeline")
-    w = bw.build(args.workload, dev, rank=rank, world=world, ensval_kind=args.ensval, lists=not (slab_mode or args.no_torch_lists))
+    # the torch builder's lists: the step's input under --lists torch; otherwise a check of the device search and the lists
+    # of the checkers, which is --full's (the builder draws nothing: the state and the table are the same with and without)
+    torch_lists = args.lists == "torch" or (args.full and not (slab_mode or args.no_torch_lists))
+    w = bw.build(args.workload, dev, rank=rank, world=world, ensval_kind=args.ensval, lists=torch_lists)
     k, nv, npts = w["k"], w["nv"], w["npts"]
     bw.relayout_state(w, args.state_layout)
     # the streaming passes either side of the loop: mean into slot k, members -> perturbations
@@ -226,7 +238,7 @@ def main():
         nij_s = w["cfg"]["nx"] * w["cfg"]["ny"]
         rig_s, rjg_s = pts_s[0][:nij_s].contiguous(), pts_s[1][:nij_s].contiguous()
     elif args.lists in ("search", "columns"):
-        n_torch = int(w["obs_off"][-1].item())
+        n_torch = int(w["obs_off"][-1].item()) if torch_lists else None
         nij_s = w["cfg"]["nx"] * w["cfg"]["ny"]
         rig_s, rjg_s = pts_s[0][:nij_s].contiguous(), pts_s[1][:nij_s].contiguous()
 
@@ -235,13 +247,18 @@ def main():
                 return ctx.obs_search_columns(t_s, nij_s, w["cfg"]["nz"], rig_s, rjg_s, pts_s[2], pts_s[3])
             return ctx.obs_search(t_s, *pts_s)
 
-        for rep in range(3):   # (the last one runs on blocks the caching allocator already owns)
+        # Set-up: the lists a step without a search of its own takes as input, and the two sets of list blocks a step with one
+        # alternates between (the new lists are allocated while the last ones are alive), in the caching allocator before
+        # the first step as they always were -- no step pays for an allocation, whatever --warmup.  --full: a third search,
+        # on blocks the allocator already owns, and that one is timed by itself.
+        for rep in range(3 if args.full else 2):
             torch.cuda.synchronize()
             t0s = time.perf_counter()
             off_s, idx_s, rd_s, rl_s = do_search()
             torch.cuda.synchronize()
-            search_ms = (time.perf_counter() - t0s) * 1e3
-        if args.max_nobs == 0:
+            if args.full:
+                search_ms = (time.perf_counter() - t0s) * 1e3
+        if n_torch is not None and args.max_nobs == 0:
             assert int(off_s[-1].item()) == n_torch, "device search and torch builder disagree on the list sizes"
         w["obs_off"], w["obs_idx"], w["rdiag"], w["rloc"] = off_s, idx_s, rd_s, rl_s
         cnt = (off_s[1:] - off_s[:-1])
@@ -451,7 +468,7 @@ def main():
         cpu = cpu_ref = None
         parity = None
         parity_note = None
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             # The checker's local-observation lists come from the ORACLE's obs_local (oracle/letkf_oracle.c orc_obs_local, limit
             # and criterion included) on a host copy of the same tables -- not from the device search, whichever route the step
             # took: the list-free and pipeline routes and the runs under MAX_NOBS_PER_GRID are checked like every other.
@@ -473,7 +490,7 @@ def main():
         out = {"metric": "grid-point LETKF solves/sec", "value": value, "unit": "solves/s", "n_gpus": n_gpus,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-               "data": "synthetic",
+               "data": "synthetic", "full": bool(args.full),
                "config": {"workload": f"{args.workload}: {w['cfg']['nx']}x{w['cfg']['ny']}x{w['cfg']['nz']} grid, "
                                       f"k={k} members, nv={nv}, mean {n_mean:.1f} (max {w['n_max']}) local obs/point, "
                                       f"relax={args.relax}, ensval={args.ensval}, obs-space spread {obs_spread:.2f} obs errors" + (", state member-fastest" if args.state_layout == "member" else "")

@@ -6,7 +6,7 @@ TAG=${1:-vX}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 500 python bench.py --steps 3 --warmup 1 > $OUT/bench_c2.json 2> $OUT/bench.err || exit 1
+timeout -k 10 500 python bench.py --full --steps 3 --warmup 1 > $OUT/bench_c2.json 2> $OUT/bench.err || exit 1
 tail -c 2500 $OUT/bench_c2.json; echo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1 || exit 1
 find $OUT/trace -type f | head -20

@@ -8,4 +8,4 @@ d=json.load(open(f"gpurun_out/zg_{sys.argv[1]}.json"))
 print("grid x", sys.argv[1], "ms/step", round(d["ms_per_step"],2), "sweeps", round(d.get("jacobi_sweeps_mean"),3), flush=True)
 PY
 done
-timeout -k 10 400 python bench.py > gpurun_out/zfull.json 2> gpurun_out/zfull.err; cat gpurun_out/zfull.json | cut -c1-1500
+timeout -k 10 400 python bench.py --full 2>/dev/null | cut -c1-1500

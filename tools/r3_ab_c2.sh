@@ -7,11 +7,11 @@ j() { python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitli
 for rep in 1 2; do
   for lib in base $V; do
     if [ $lib = base ]; then unset LETKF_AMD_LIB; else export LETKF_AMD_LIB=$GRAFT_REPO_ROOT/scale-letkf_amd/lib/libletkf_amd_$V.so; fi
-    timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --cpu-seconds 2 2>/dev/null | j "$lib C2"
+    timeout -k 10 300 python3 bench.py --full --steps 6 --warmup 2 --cpu-seconds 2 2>/dev/null | j "$lib C2"
   done
 done
 for lib in base $V; do
   if [ $lib = base ]; then unset LETKF_AMD_LIB; else export LETKF_AMD_LIB=$GRAFT_REPO_ROOT/scale-letkf_amd/lib/libletkf_amd_$V.so; fi
-  timeout -k 10 300 python3 bench.py --workload C2-mini-sparse --steps 6 --warmup 2 --cpu-seconds 2 2>/dev/null | j "$lib C2-mini-sparse"
-  timeout -k 10 300 python3 bench.py --workload C2-slab-k100 --eigen-stage-only --steps 4 --warmup 1 --cpu-seconds 2 2>/dev/null | j "$lib k100-eig-only"
+  timeout -k 10 300 python3 bench.py --full --workload C2-mini-sparse --steps 6 --warmup 2 --cpu-seconds 2 2>/dev/null | j "$lib C2-mini-sparse"
+  timeout -k 10 300 python3 bench.py --full --workload C2-slab-k100 --eigen-stage-only --steps 4 --warmup 1 --cpu-seconds 2 2>/dev/null | j "$lib k100-eig-only"
 done

@@ -17,7 +17,7 @@ if [ $PART = A ]; then
   timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-search-in-step 2>/dev/null | tee $O/bench_c2_solveonly.json | j C2-solve-only
   timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --state-layout member 2>/dev/null | tee $O/bench_c2_member.json | j C2-member-layout
   for w in C2-mini C2-mini-k20 C2-k20 C1 C2-mini-k100 C2-slab-k100 C2-cols-k100 C2-disc C2-mini-disc C2-mini-sparse C4-slab C4-mini C3-mini C3-slab C5-slab; do
-    timeout -k 10 300 python3 bench.py --workload $w --steps 3 --warmup 1 --cpu-seconds 4 2>/dev/null | tee $O/bench_$w.json | j $w
+    timeout -k 10 300 python3 bench.py --full --workload $w --steps 3 --warmup 1 --cpu-seconds 4 2>/dev/null | tee $O/bench_$w.json | j $w
   done
   echo "== strong scaling, N = 1"; timeout -k 10 300 python3 bench.py --scaling strong --steps 3 --warmup 1 2>/dev/null | tee $O/bench_c2_strong_n1.json | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('C2 strong N=1', 'ms/step', round(d['ms_per_step'],2), 'solves/s', int(d['value']))"
   echo "== cycle"; timeout -k 10 300 python3 bench_cycle.py 2>&1 | tail -3

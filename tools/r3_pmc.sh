@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=$1; shift
 O=gpurun_out/pmc_$TAG
 rm -rf $O; mkdir -p $O
-timeout -k 10 400 python3 bench.py --steps 3 --warmup 1 --cpu-seconds 4 "$@" > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 4 "$@" > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $O/trace.log 2>&1 || { tail -5 $O/trace.log; exit 1; }
 find $O/trace -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \; ; rm -rf $O/trace
 grep -E "letkf::|\"Name\"" $O/kernel_stats.csv | cut -c1-200

@@ -9,6 +9,6 @@ j() { python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitli
 for rep in 1 2; do for w in $WL; do
   for lib in base $V; do
     if [ $lib = base ]; then unset LETKF_AMD_LIB; else export LETKF_AMD_LIB=$GRAFT_REPO_ROOT/scale-letkf_amd/lib/libletkf_amd_$V.so; fi
-    timeout -k 10 300 python3 bench.py --workload $w --steps 5 --warmup 2 --cpu-seconds 2 $ARGS 2>/dev/null | j "$lib $w"
+    timeout -k 10 300 python3 bench.py --full --workload $w --steps 5 --warmup 2 --cpu-seconds 2 $ARGS 2>/dev/null | j "$lib $w"
   done
 done; done
