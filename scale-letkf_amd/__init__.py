@@ -22,6 +22,7 @@ OBSSCAN_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsscan.so")   # obso
 MAPPROJ_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_mapproj.so")   # the map projection (include/letkf_amd_mapproj.h); made by `make mapproj`, in the same way
 OBSFILE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsfile.so")   # the record codec of the observation files (include/letkf_amd_obsfile.h); made by `make obsfile`, in the same way
 NOBSOUT_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_nobsout.so")   # NOBS_OUT (include/letkf_amd_nobsout.h); made by `make nobsout`, in the same way
+TCVITAL_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_tcvital.so")   # the TC vitals (include/letkf_amd_tcvital.h); made by `make tcvital`, in the same way
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -36,11 +37,13 @@ def build(force=False):
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*")) + glob.glob(os.path.join(HERE, "csrc", "mapproj", "*"))
     srcs += glob.glob(os.path.join(HERE, "csrc", "obsfile", "*")) + glob.glob(os.path.join(HERE, "csrc", "nobsout", "*"))
+    srcs += glob.glob(os.path.join(HERE, "csrc", "tcvital", "*"))
     srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
     srcs = [s for s in srcs if os.path.isfile(s)]      # (a directory's time is that of its last new entry, not of a source)
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
-    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH, OBSFILE_LIB_PATH, NOBSOUT_LIB_PATH)
+    libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH, OBSFILE_LIB_PATH, NOBSOUT_LIB_PATH) + (
+        TCVITAL_LIB_PATH,)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
@@ -49,6 +52,7 @@ def build(force=False):
         subprocess.check_call(["make", "-j4", "-C", HERE, "mapproj"], stdout=2)   # (and so is this)
         subprocess.check_call(["make", "-j4", "-C", HERE, "obsfile"], stdout=2)   # (and this)
         subprocess.check_call(["make", "-j4", "-C", HERE, "nobsout"], stdout=2)   # (and this)
+        subprocess.check_call(["make", "-j4", "-C", HERE, "tcvital"], stdout=2)   # (and this)
     return LIB_PATH
 
 
@@ -666,6 +670,24 @@ NOBSOUT_SIGNATURES = {
 }
 NOBSOUT_MAX_CTYPE, NOBSOUT_MAX_OBTYPE, NOBSOUT_NFIELDS = 64, 32, 11
 
+
+class TcvitalParams(C.Structure):
+    """letkf_tcvital_params (include/letkf_amd_tcvital.h): the grid as the projection has it, this rank's offsets, TC_SEARCH_DIS"""
+    _fields_ = ([(n, C.c_double) for n in ("dx", "dy", "cxg1", "cyg1")] + [("i_off", C.c_int32), ("j_off", C.c_int32)] +
+                [("tc_search_dis", C.c_double)])
+
+
+# ... and of the twelfth companion header include/letkf_amd_tcvital.h: the entries are exported by the library of the TC vitals
+# (TCVITAL_LIB_PATH, tcvital_lib()).  (SIGNATURES, as the three tables before it.)
+TCVITAL_VERSION = 1
+TCVITAL_SIGNATURES = {
+    "letkf_tcvital_rows_dev": [_VP, _I64, _VP, _VP, _F64, _F64, _VP, _VP],
+    "letkf_tcvital_search_dev": [_VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_tcvital_fill_dev": [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _I64],
+}
+TCVITAL_ID_TCX, TCVITAL_ID_TCY, TCVITAL_ID_TCP, TCVITAL_QC_BAD = 99991, 99992, 99993, 50
+TCVITAL_NONE = 9.99e33
+
 _libs = {}
 
 
@@ -735,6 +757,12 @@ def nobsout_lib():
     """dlopen the library of NOBS_OUT, after the main one whose context and main loop it uses."""
     lib()
     return _load(NOBSOUT_LIB_PATH, (NOBSOUT_SIGNATURES,))
+
+
+def tcvital_lib():
+    """dlopen the library of the TC vitals, after the main one whose context and scratch buffer it uses."""
+    lib()
+    return _load(TCVITAL_LIB_PATH, (TCVITAL_SIGNATURES,))
 
 
 def _obsfile_size(entry, fmt, nrec, n):
@@ -1068,6 +1096,40 @@ class Context:
         p.elm_u_ctype, p.typ_ctype = eu.ctypes.data, ty.ctypes.data
         self._check(nobsout_lib().letkf_nobs_fields_dev(self._c, C.addressof(p), npts, _ptr(nobs_ctype), _ptr(cutd_ctype), _ptr(work3dn),
                                                         _ptr(fields), sp, npts if sv is None else sv))
+
+    def tcvital_rows(self, elm, dif, slot_lb, slot_ub, n=None):
+        """letkf_tcvital_rows_dev (include/letkf_amd_tcvital.h): the last 1-based rows of the TCX / TCY / TCP elements among the
+        decoded columns elm (int32) and dif (float64) of one file, 0 where there is none, and whether they are one report of the
+        slot (slot_lb, slot_ub].  Returns (rows int64 [3], valid)."""
+        import numpy as np
+        rows, valid = np.full(3, -1, dtype=np.int64), C.c_int32(-1)
+        self._check(tcvital_lib().letkf_tcvital_rows_dev(self._c, elm.numel() if n is None else n, _ptr(elm), _ptr(dif), slot_lb,
+                                                         slot_ub, _hptr(rows), C.addressof(valid)))
+        return rows, bool(valid.value)
+
+    def tcvital_search(self, params, fields, ritc, rjtc, cand=None):
+        """letkf_tcvital_search_dev: (tcx, tcy, mslp) of the lowest smoothed sea-level pressure within params.tc_search_dis of the
+        grid coordinates ritc / rjtc (device tensors of one float64 each) for the fields.nmem members of one subdomain, 9.99e33
+        thrice where there is none.  params: TcvitalParams; fields: ObsopeFields (v2d, its strides, sizes and halos are read).
+        Returns cand float64 [nmem, 3] (or writes into the one given)."""
+        import torch
+        if cand is None:
+            cand = torch.empty((fields.nmem, 3), dtype=torch.float64, device=ritc.device)
+        self._check(tcvital_lib().letkf_tcvital_search_dev(self._c, C.addressof(params), C.addressof(fields), _ptr(ritc), _ptr(rjtc),
+                                                           _ptr(cand)))
+        return cand
+
+    def tcvital_fill(self, cand_all, rows, qc, ensval, kld, m0=0, qc_replace=True, nproc=None, nmem=None):
+        """letkf_tcvital_fill_dev: cand_all float64 [nproc, nmem, 3] (every rank's candidates) to the obsda rows `rows` (0-based
+        TCX, TCY, TCP; negative: not on this rank): per member the lowest rank among those with the lowest mslp below 1100 hPa
+        into ensval[row, m0 + m], undef without one; qc 50 on the rows if any member has none, else 0 (qc_replace) or merged by
+        maximum."""
+        import numpy as np
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        nproc = cand_all.shape[0] if nproc is None else nproc
+        nmem = cand_all.shape[1] if nmem is None else nmem
+        self._check(tcvital_lib().letkf_tcvital_fill_dev(self._c, nproc, nmem, m0, _ptr(cand_all), _hptr(r), int(qc_replace), _ptr(qc),
+                                                         _ptr(ensval), kld))
 
     def das_interp(self, k, nv, tables, nx, ny, nlev, stride_x, stride_y, rig, rjg, rlev, rz, ensval, kld, dep, infl, gues,
                    anal, sp, sm, sv, ws_bytes=0, nobs_coarse=None, npts=None, beta=None, det_run=False, infl_adaptive=False,

@@ -5,8 +5,8 @@
 // letkf_superob_entry.hip (include/letkf_amd_superob.h) include it, and obsscan/letkf_obsscan_entry.hip
 // (include/letkf_amd_obsscan.h) from the library of the first scan and mapproj/letkf_mapproj_entry.hip
 // (include/letkf_amd_mapproj.h) from the library of the map projection, and nobsout/letkf_nobsout_entry.hip
-// (include/letkf_amd_nobsout.h) from the library of NOBS_OUT.  Every function is defined in the one unit named above its
-// declaration.
+// (include/letkf_amd_nobsout.h) from the library of NOBS_OUT, and tcvital/letkf_tcvital_entry.hip (include/letkf_amd_tcvital.h)
+// from the library of the TC vitals.  Every function is defined in the one unit named above its declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 
