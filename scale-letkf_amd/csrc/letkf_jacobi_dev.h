@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "letkf_lane_dev.h"
+#include "letkf_rot_rule.h"
 
 // Warm-started runs hand their eigenvectors on sorted by eigenvalue (1, the default) or in the order the iteration stopped in
 // (-DLETKF_WARM_SORT=0, for an A/B twin): letkf_wave_dev.h warm_rank, letkf_trio.hip jacobi_trio.
@@ -16,6 +17,18 @@
 // Sorted, the column of rank r goes to line position r ^ 1 (1, the default) or r (-DLETKF_WARM_ORDER=0): letkf_wave_dev.h warm_position.
 #ifndef LETKF_WARM_ORDER
 #define LETKF_WARM_ORDER 1
+#endif
+
+// One-wave points decide the three magnitude tests of a rotation (rotate, stop, early) on the upper dwords of g2 and ab with
+// integer instructions, against powers of two (letkf_rot_rule.h) (1, the default), or in FP64 against the decimal tolerances
+// below as two-wave points do (-DLETKF_ROT_INT_TESTS=0, for an A/B twin) ...
+#ifndef LETKF_ROT_INT_TESTS
+#define LETKF_ROT_INT_TESTS 1
+#endif
+// ... and, with them, vote once per step pair on the larger of its two rotations' margins (1, the default) or once per rotation
+// (-DLETKF_ROT_VOTE_PAIR=0).
+#ifndef LETKF_ROT_VOTE_PAIR
+#define LETKF_ROT_VOTE_PAIR 1
 #endif
 
 namespace letkf {
@@ -38,6 +51,9 @@ __device__ __forceinline__ bool pany(bool v) {
   else return __syncthreads_or(v) != 0;
 }
 
+// The decimal tolerances below are what two-wave points, letkf_trio.hip and the staged path's eigen stages compare with in FP64;
+// one-wave points of jacobi_split read rot_rule::kRotExp / kStopExp / kEarlyExp (powers of two not looser than these) unless
+// built with -DLETKF_ROT_INT_TESTS=0, and their A/B knobs are -DLETKF_ROT_EXP / -DLETKF_STOP_EXP / -DLETKF_EARLY_EXP.
 constexpr double kRotTol2W = 1e-30;   // rotate when cos^2 > 1e-30
 #ifndef LETKF_EARLY_TOL2
 #define LETKF_EARLY_TOL2 1e-16
@@ -179,9 +195,12 @@ __device__ __forceinline__ double slot_sum_nw(double v, double* xs, int& ph) {
 // then update) instead of keeping it: +2 instructions per row, no AGPR traffic.
 // stop_tol2: the squared cosine of the stop rule (kStopTol2W; the block Jacobi of letkf_kernels.hip, whose 32 x 32 problems are
 // Gram matrices -- squared condition, a noise floor of eps cond^2 on their cosines -- keeps round 2's 1e-20).
+// stop_exp: the same for the integer tests of one-wave points, cos^2 > 2^-stop_exp (rot_rule::kStopExp); two-wave points read
+// stop_tol2, one-wave points stop_exp.
 template <int KR, int NW, int RC = 24, bool EARLY = true, bool INPLACE = false>
 __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const int max_sweep, double* lds,
-                                            int* pairs_out = nullptr, int* conv_out = nullptr, const double stop_tol2 = kStopTol2W) {
+                                            int* pairs_out = nullptr, int* conv_out = nullptr, const double stop_tol2 = kStopTol2W,
+                                            const int stop_exp = rot_rule::kStopExp) {
   static_assert(KR % 2 == 0, "row halves");
   constexpr int H = KR / 2;
   static_assert(RC % 2 == 0, "RC rows per conversion chunk: RC * 64 NW doubles of LDS");
@@ -192,6 +211,9 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
   // callers keep k <= 62 on one wave (launch_wave_kernel; the block Jacobi of letkf_kernels.hip has k = 32).  Two-wave
   // points run every lane and keep the selects.
   constexpr bool ENDS = NW == 1;
+  // INTT: the magnitude tests on the upper dwords (letkf_rot_rule.h); VOTEP: their votes once per step pair
+  constexpr bool INTT = LETKF_ROT_INT_TESTS && NW == 1, VOTEP = INTT && LETKF_ROT_VOTE_PAIR;
+  const int stop_lim = rot_rule::limit(stop_exp);
   static_assert(!ENDS || KR <= 64, "one wave: k <= 62, lane 31 stays switched off");
   constexpr int NL = 64 * NW;
   int lane = threadIdx.x & (NL - 1);
@@ -256,6 +278,7 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
         // the two votes of the step pair, kept as lane masks (scalar registers): accumulated as per-lane booleans hipcc holds
         // them in a vector register and converts back and forth (5 vector instructions per step pair)
         unsigned long long notconv = 0, notconv2 = 0;
+        int mgE = 0;   // (INTT) the even rotation's margin, kept for the step pair's vote
         // ---------------- even step: the slot's own two columns (A at the lower position)
         {
           double p0 = 0.0, p1 = 0.0;
@@ -269,21 +292,29 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
           const double ga = slot_sum_nw<NW>(p0 + p1, lds, ph) * (isA * isB);
           const double a = alA, b = alB;
           const double g2 = ga * ga, ab = a * b;
-          notconv |= __builtin_amdgcn_ballot_w64(g2 > stop_tol2 * ab);
+          // (INTT: g2 = 0 and NaN have the margin that exceeds nothing -- no rotation, no vote)
+          if constexpr (INTT) mgE = rot_rule::margin(__double2hiint(g2), __double2hiint(ab));
+          if constexpr (!INTT) notconv |= __builtin_amdgcn_ballot_w64(g2 > stop_tol2 * ab);
+          else if constexpr (!VOTEP) notconv |= __builtin_amdgcn_ballot_w64(rot_rule::exceeds(mgE, stop_lim));
           // tan(theta) = gamma sign(h) / (|h| + sqrt(h^2 + gamma^2)), h = (beta - alpha) / 2 (the smaller root of
           // t^2 + 2 (h / gamma) t - 1 = 0).  Pairs with |cos| <= 1e-15 are NOT rotated: inside a cluster of equal eigenvalues
           // (every point with fewer observations than members) h is rounding noise as well, the angle would be 45 degrees at a
           // cosine that is noise, and such a rotation shuffles the couplings of its two columns to all others after those
           // were visited (tried without the test: tests/test_gpu_sparse_margin.py 1.5e-14 -> 2e-12).  It also keeps the
           // 0 * rsq(0) = NaN of two zero columns out.
-          const bool rot = g2 > kRotTol2W * ab;
+          const bool rot = INTT ? rot_rule::exceeds(mgE, rot_rule::limit(rot_rule::kRotExp)) : g2 > kRotTol2W * ab;
           const double h = 0.5 * (b - a);
           const double x = fma(h, h, g2);
           const double den = fma(x, fast_rsqrt1(x), fabs(h));
           double tt = ga * fast_rcp1(copysign(den, h));
           tt = rot ? tt : 0.0;
-          if constexpr (EARLY)
+          if constexpr (EARLY && !INTT)
             notconv2 |= __builtin_amdgcn_ballot_w64(g2 > kEarlyTol2W * ab) | __builtin_amdgcn_ballot_w64(fabs(tt) > kEarlyTW);
+          else if constexpr (EARLY && !VOTEP)
+            notconv2 |= __builtin_amdgcn_ballot_w64(rot_rule::exceeds(mgE, rot_rule::limit(rot_rule::kEarlyExp))) |
+                        __builtin_amdgcn_ballot_w64(fabs(tt) > kEarlyTW);
+          else if constexpr (EARLY)
+            notconv2 |= __builtin_amdgcn_ballot_w64(fabs(tt) > kEarlyTW);
           const double w = fma(tt, tt, 1.0);
           const double c = fast_rsqrt(w);
           const double tg = tt * ga, wc = w * c;
@@ -359,15 +390,30 @@ __device__ __forceinline__ int jacobi_split(double (&g)[KR], const int k, const 
           const double ga = slot_sum_nw<NW>(p0 + p1, lds, ph) * (isB * isAr);
           const double a = alB, b = alAr;
           const double g2 = ga * ga, ab = a * b;
-          notconv |= __builtin_amdgcn_ballot_w64(g2 > stop_tol2 * ab) & hasRm;
-          const bool rot = hasR && g2 > kRotTol2W * ab;
+          // (INTT: the votes need no hasRm -- a lane without a right partner fetched zeros, its g2 = 0 has the margin that exceeds
+          // nothing, and its tangent is 0 without `rot`)
+          const int mgO = INTT ? rot_rule::margin(__double2hiint(g2), __double2hiint(ab)) : 0;
+          if constexpr (!INTT) notconv |= __builtin_amdgcn_ballot_w64(g2 > stop_tol2 * ab) & hasRm;
+          else if constexpr (!VOTEP) notconv |= __builtin_amdgcn_ballot_w64(rot_rule::exceeds(mgO, stop_lim));
+          const bool rot = hasR && (INTT ? rot_rule::exceeds(mgO, rot_rule::limit(rot_rule::kRotExp)) : g2 > kRotTol2W * ab);
           const double h = 0.5 * (b - a);
           const double x = fma(h, h, g2);
           const double den = fma(x, fast_rsqrt1(x), fabs(h));
           double tt = ga * fast_rcp1(copysign(den, h));
           tt = rot ? tt : 0.0;
-          if constexpr (EARLY)
+          if constexpr (EARLY && !INTT)
             notconv2 |= (__builtin_amdgcn_ballot_w64(g2 > kEarlyTol2W * ab) | __builtin_amdgcn_ballot_w64(fabs(tt) > kEarlyTW)) & hasRm;
+          else if constexpr (EARLY && !VOTEP)
+            notconv2 |= __builtin_amdgcn_ballot_w64(rot_rule::exceeds(mgO, rot_rule::limit(rot_rule::kEarlyExp))) |
+                        __builtin_amdgcn_ballot_w64(fabs(tt) > kEarlyTW);
+          else if constexpr (EARLY)
+            notconv2 |= __builtin_amdgcn_ballot_w64(fabs(tt) > kEarlyTW);
+          if constexpr (VOTEP) {
+            // one vote for the step pair: what either rotation exceeds, the larger margin exceeds
+            const int mg = max(mgE, mgO);
+            notconv = __builtin_amdgcn_ballot_w64(rot_rule::exceeds(mg, stop_lim));
+            if constexpr (EARLY) notconv2 |= __builtin_amdgcn_ballot_w64(rot_rule::exceeds(mg, rot_rule::limit(rot_rule::kEarlyExp)));
+          }
           const double w = fma(tt, tt, 1.0);
           const double c = fast_rsqrt(w);
           const double tg = tt * ga, wc = w * c;
