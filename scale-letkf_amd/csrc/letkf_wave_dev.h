@@ -602,6 +602,16 @@ __device__ __forceinline__ bool letkf_check_fail(unsigned long long* rec, const 
 #define LETKF_CHECK(ok, code, val, lim) true
 #endif
 
+// the kernel's arguments as the argument segment holds them, and a copy of that pointer that hipcc cannot see through: what is
+// read through it is read where it is used, by scalar loads, and nothing built from it can be hoisted out of the point loop
+// (letkf_wave_kernel; one-wave instantiations only -- two-wave points get the pointer back as it is and do not use it)
+using KernArgs = const __attribute__((address_space(4))) PointArgs;
+template <int NW>
+__device__ __forceinline__ KernArgs* fresh_args(KernArgs* p) {
+  if constexpr (NW == 1) asm volatile("" : "+s"(p));
+  return p;
+}
+
 template <int KR, int NV, bool KKOUT, int NW, int FUSED>
 __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) letkf_wave_kernel(const PointArgs A) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -613,6 +623,18 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
   const int wvp = (NW == 1) ? 0 : (threadIdx.x >> 6);   // wave inside the point
   const int wv = (NW == 1) ? (threadIdx.x >> 6) : 0;    // point slot inside the workgroup
   const int k = A.k;
+  // (r12) The arguments a second time, as the argument segment holds them.  hipcc reads PointArgs in the prologue with
+  // s_load_dwordx8 / x16, cannot keep the tuples in SGPRs across the point loop, parks them in lanes of a spill VGPR and fetches
+  // the WHOLE tuple back -- 8 or 16 v_readlane_b32, vector issue slots -- in front of every use of one field: 1074 of the
+  // production instantiation's 2926 lane reads wrote a scalar nobody read (tools/isa_point_census.py), 16 per variable of the
+  // analysis loop to get q_sprd_max.  Masks built from a field and the lane number (lane < k && in-class, per variable) were
+  // hoisted and parked the same way, two lane reads per use.  Through a pointer laundered at the head of a phase (fresh_args)
+  // the phase re-reads what it needs with scalar loads, which are not vector instructions, and nothing built from those values
+  // can be hoisted out of the point loop.  One-wave instantiations only: two-wave points keep A (and their assembly).
+  // (every phase takes its own laundered copy, fresh_args: one laundered value carried from phase to phase would meet itself
+  // behind branches hipcc takes for divergent -- the point number comes from a vector value -- and an SGPR cannot be merged
+  // there.)
+  [[maybe_unused]] KernArgs* const Ak0 = (KernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   const int nv = A.nv;                        // == NV on the das path, 0 on the letkf_core batch path
   const double km1 = (double)(k - 1);
 
@@ -1275,6 +1297,11 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       // lane l holds rows (l>>4) + 4*reg, column l&15 of its 16x16 tile.
       constexpr int LDA = 18;
       double* abuf = slice;                                    // [64 NW][LDA], spans the tile + bmat regions
+      // diagonal: trace for the adaptive inflation, then the shift (common_letkf.f90:140-143)
+      [[maybe_unused]] const double shift = (NW == 1) ? km1 / infl_old : 0.0;   // (two-wave points: where it was, below)
+      double diag = 0.0;
+      [[maybe_unused]] int ln = lane;                          // (laundered: what is built from it is built per point, not fetched)
+      if constexpr (NW == 1) asm volatile("" : "+v"(ln));
       if constexpr (STRIP) {                                   // the narrow block's sums over the four observation residues q
 #pragma unroll
         for (int a = 0; a < RS; ++a)
@@ -1354,6 +1381,19 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           // isa_exec_audit.py looks for that pattern in every unit's ISA; the Makefile runs it on every build.
           const int lrow = lane < 16 * NBLK ? lane : 16 * NBLK - 1;
           const bool mine = lane < 16 * NBLK;
+          {
+            // (r12) the diagonal, while the column is still in LDS: lane j < k owns A[j][j], element j & 15 of its row in the pass
+            // of block j >> 4 -- the trace takes it as it is and the shift goes on top before the column is read.  (As 50 masked
+            // adds in registers, `if (r == lane && lane < k)`, every row had a lane mask of its own, all hoisted out of the point
+            // loop and fetched from a spill register by two v_readlane_b32 each.)  No branch: a lane that owns nothing in this
+            // pass stores what it read into the padding of its row (elements 16, 17 of LDA = 18 are never read).
+            const bool own = (ln >> 4) == I && ln < k;
+            double* const dp = &abuf[lrow * LDA + (ln & 15)];
+            const double d = *dp;
+            diag = own ? d : diag;
+            *(own ? dp : &abuf[lrow * LDA + 16]) = own ? d + shift : d;
+            psync<NW>();
+          }
 #pragma unroll
           for (int e = 0; e < 16; e += 2) {
             if (16 * I + e < KR) {
@@ -1392,17 +1432,29 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       }
       psync<NW>();
       // rows >= k of a column (the augmented rows) and whole columns >= k play no part in the eigenproblem
+      if constexpr (NW == 1) {
+        // (r12) one lane mask for the columns, made here from the laundered lane number, and a wave-uniform test for the rows --
+        // only those at and above the smallest k the instantiation is launched for (launch_wave) can be augmented rows
+        const bool colzero = ln >= k || ln >= 16 * NBLK;
+        int ku = k;
+        asm volatile("" : "+s"(ku));
 #pragma unroll
-      for (int r = 0; r < KR; ++r)
-        if (r >= k || lane >= k || lane >= 16 * NBLK) g[r] = 0.0;
-      // diagonal: trace for the adaptive inflation, then the shift (common_letkf.f90:140-143)
-      const double shift = km1 / infl_old;
-      double diag = 0.0;
+        for (int r = 0; r < KR; ++r) {
+          g[r] = colzero ? 0.0 : g[r];
+          if (r >= KMIN && r >= ku) g[r] = 0.0;
+        }
+      } else {
 #pragma unroll
-      for (int r = 0; r < KR; ++r) {
-        if (r == lane && lane < k) {
-          diag = g[r];
-          g[r] += shift;
+        for (int r = 0; r < KR; ++r)
+          if (r >= k || lane >= k || lane >= 16 * NBLK) g[r] = 0.0;
+        // diagonal: trace for the adaptive inflation, then the shift (common_letkf.f90:140-143)
+        const double shift2 = km1 / infl_old;
+#pragma unroll
+        for (int r = 0; r < KR; ++r) {
+          if (r == lane && lane < k) {
+            diag = g[r];
+            g[r] += shift2;
+          }
         }
       }
       double parm1 = 0.0, parm2 = 0.0, parm3 = 0.0;
@@ -1446,8 +1498,15 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
     constexpr int kObOff = (32 * KR >= 1024) ? 0 : kBmOff + 16 * kBmRows + 128;   // MAPPLY: output transposition buffer [64][16], clear of B
     if constexpr (!MAPPLY) {
       if (!solved) {
+        if constexpr (NW == 1) {
+          int li = lane;                           // (the compares are made here, per point -- see `ln` above)
+          asm volatile("" : "+v"(li));
 #pragma unroll
-        for (int r = 0; r < KR; ++r) g[r] = (r == lane && lane < k) ? 1.0 : 0.0;
+          for (int r = 0; r < KR; ++r) g[r] = (r == li && li < k) ? 1.0 : 0.0;
+        } else {
+#pragma unroll
+          for (int r = 0; r < KR; ++r) g[r] = (r == lane && lane < k) ? 1.0 : 0.0;
+        }
       }
     }
     const double infl_new = (A.infl_adaptive && n > 0) ? p1 : infl_old;
@@ -1456,15 +1515,17 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
     if constexpr (MAPPLY) {
       // the state loads of the apply phase, issued here so that their latency (8-byte accesses npts*8 B apart) runs
       // under the normalisation, the workspace store and the status reductions
+      KernArgs* const Ax = fresh_args<NW>(Ak0);
+      const long sv_ = Ax->sv, sm_ = Ax->sm;
       const double* gp = g0 + moff;
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         xv[v] = (lane < k) ? *gp : 0.0;
-        gp += A.sv;
+        gp += sv_;
       }
       if (lane < NV) {
-        xm_l = g0[k * A.sm + lane * A.sv];
-        xd_l = A.det_run ? g0[(k + 1) * A.sm + lane * A.sv] : 0.0;
+        xm_l = g0[k * sm_ + lane * sv_];
+        xd_l = Ax->det_run ? g0[(k + 1) * sm_ + lane * sv_] : 0.0;
       }
       asm volatile("" ::: "memory");
     }
@@ -1645,17 +1706,21 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       vg += wshfl_xor(vg, 16);
       vg += wshfl_xor(vg, 32);
       {
+        KernArgs* const Ar = fresh_args<NW>(Ak0);
         const int v = c - 2;
         const bool isv = c >= 2 && c < NB;
+        const double ra_ = Ar->relax_alpha, ras_ = Ar->relax_alpha_spread;
         double cfv = 1.0;
-        if (A.relax_alpha != 0.0) {
-          cfv = 1.0 - A.relax_alpha;
-        } else if (A.relax_alpha_spread != 0.0) {
-          cfv = rtps_factor(A, isv ? relax_parm(A, pt, v) : 1.0, vg, va, km1);
+        if (ra_ != 0.0) {
+          cfv = 1.0 - ra_;
+        } else if (ras_ != 0.0) {                                        // (rules_dev::relax_parm and rtps_factor, restated)
+          const double parm = (isv && Ar->relax_to_inflated_prior) ? Ar->infl[pt + Ar->infl_sv * (long)v] : 1.0;
+          if (vg > 0.0 && va > 0.0) cfv = ras_ * sqrt(vg * parm / (va * km1)) - ras_ + 1.0;
         }
-        if (A.rtps_out && q == 0 && isv && ((A.var_mask >> v) & 1u)) {   // (rules_dev::rtps_reported, restated)
-          const bool skipv = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-          A.rtps_out[pt + A.infl_sv * (long)v] = (A.relax_alpha == 0.0 && A.relax_alpha_spread != 0.0 && !skipv) ? cfv : 1.0;
+        double* const rtps_out_ = Ar->rtps_out;
+        if (rtps_out_ && q == 0 && isv && ((Ar->var_mask >> v) & 1u)) {   // (rules_dev::rtps_reported, restated)
+          const bool skipv = qskip && v >= Ar->iv_q_first && v <= Ar->iv_q_last;
+          rtps_out_[pt + Ar->infl_sv * (long)v] = (ra_ == 0.0 && ras_ != 0.0 && !skipv) ? cfv : 1.0;
         }
 #pragma unroll
         for (int vv = 0; vv < NV; ++vv) cf[vv] = readlane_d(cfv, 2 + vv);
@@ -1750,60 +1815,137 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
     }
     PROF_MARK(7)
     // ------------------------------------------------------------ analysis members
-    if (NV > 0 && das) {
-      double* ap = a0 + moff;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;   // (rules_dev::var_skipped, restated)
-        double x, xm, xdt;
-        if constexpr (MAPPLY) {
-          // x' comes back from the LDS copy of B (it survives the output transposition): keeping the 22 registers of xv
-          // alive through the matrix phase made hipcc spill LDS addresses there -- a scratch round trip in front of
-          // every MFMA step of the U product (PROF build ISA)
-          const double xl = slice[kBmOff + (lane < kBmRows ? lane : kBmRows - 1) * 16 + 2 + v];
-          x = (lane < k) ? xl : 0.0;
-          xm = readlane_d(xm_l, v);
-          xdt = readlane_d(xd_l, v);
-        } else {
-          x = (lane < k) ? bmat[mrow_l * NBP + 2 + v] : 0.0;
-          xm = xmean[v];
-          xdt = xdet[v];
-        }
-        const double sdot = preduce<NW, 0>(x * out[0], red, rslot);
-        const double sdotd = A.det_run ? preduce<NW, 0>(x * out[1], red, rslot) : 0.0;
-        double val;
-        if (skip) {
-          val = xm + x;
-        } else {
-          const double pert = cf[v] * out[2 + v] + rtpp_diag(A, pt, v) * x;
-          val = analysis_value(xm, x, beta, pert, sdot);
-          if (A.q_sprd_max > 0.0 && v == A.iv_q_first) {
-            const double q_mean = preduce<NW, 0>(lane < k ? val : 0.0, red, rslot) / (double)k;
-            const double dq = (lane < k) ? val - q_mean : 0.0;
-            const double q_sprd = sqrt(preduce<NW, 0>(dq * dq, red, rslot) / km1) / q_mean;
-            val = q_clamped(val, q_mean, dq, q_sprd, A.q_sprd_max);
-          }
-        }
-        const bool inclass = (A.var_mask >> v) & 1u;
-        if (lane < k && inclass) *ap = val;
-        ap += A.sv;
-        if (A.det_run && lane == 0 && inclass)
-          a0[(k + 1) * A.sm + v * A.sv] = skip ? xdt : xdt + sdotd * beta;     // :489-497
-      }
-      if (A.infl_adaptive) {                       // (rules_dev::var_updated, restated; also without obs: the class copies its first slot), after every parm read above
+    // One-wave points read the arguments of this phase from the argument segment (fresh_args, above) and restate the rules of
+    // letkf_rules_dev.h on them; two-wave points keep the phase as it was, statement for statement, in the branch below: their
+    // register allocation moves with any restatement of shared code (tools/isa_compare.py holds letkf_wave2 to its assembly),
+    // so A CHANGE TO ONE BRANCH BELONGS IN THE OTHER TOO.
+    if constexpr (NW == 1) {
+      if (NV > 0 && das) {
+        double* ap = a0 + moff;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-          const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
-          if (!skip && lane == 0 && ((A.var_mask >> v) & 1u)) A.infl[pt + A.infl_sv * (long)v] = infl_new;
+          KernArgs* const Av = fresh_args<NW>(Ak0);                                 // (per variable: what it reads lives for one iteration, in SGPRs)
+          const int ivq0 = Av->iv_q_first, det_run_ = Av->det_run;
+          const bool skip = qskip && v >= ivq0 && v <= Av->iv_q_last;   // (rules_dev::var_skipped, restated)
+          double x, xm, xdt;
+          if constexpr (MAPPLY) {
+            // x' comes back from the LDS copy of B (it survives the output transposition): keeping the 22 registers of xv
+            // alive through the matrix phase made hipcc spill LDS addresses there -- a scratch round trip in front of
+            // every MFMA step of the U product (PROF build ISA)
+            const double xl = slice[kBmOff + (lane < kBmRows ? lane : kBmRows - 1) * 16 + 2 + v];
+            x = (lane < k) ? xl : 0.0;
+            xm = readlane_d(xm_l, v);
+            xdt = readlane_d(xd_l, v);
+          } else {
+            x = (lane < k) ? bmat[mrow_l * NBP + 2 + v] : 0.0;
+            xm = xmean[v];
+            xdt = xdet[v];
+          }
+          const double sdot = preduce<NW, 0>(x * out[0], red, rslot);
+          const double sdotd = det_run_ ? preduce<NW, 0>(x * out[1], red, rslot) : 0.0;
+          double val;
+          if (skip) {
+            val = xm + x;
+          } else {
+            double rd = 0.0;                         // (rules_dev::rtpp_diag and relax_parm, restated)
+            if (const double ra_ = Av->relax_alpha; ra_ != 0.0)
+              rd = ra_ * sqrt(Av->relax_to_inflated_prior ? Av->infl[pt + Av->infl_sv * (long)v] : 1.0);
+            // (the contraction hipcc chose for `cf * out + rtpp_diag * x` before the restatement, written out: left to it, the
+            // restated sum is contracted the other way round and RTPP results move in the last bit)
+            const double pert = fma(cf[v], out[2 + v], rd * x);
+            val = analysis_value(xm, x, beta, pert, sdot);
+            const double qsm = Av->q_sprd_max;
+            if (qsm > 0.0 && v == ivq0) {
+              const double q_mean = preduce<NW, 0>(lane < k ? val : 0.0, red, rslot) / (double)k;
+              const double dq = (lane < k) ? val - q_mean : 0.0;
+              const double q_sprd = sqrt(preduce<NW, 0>(dq * dq, red, rslot) / km1) / q_mean;
+              val = q_clamped(val, q_mean, dq, q_sprd, qsm);
+            }
+          }
+          const bool inclass = (Av->var_mask >> v) & 1u;
+          const long sv_ = Av->sv;
+          if (lane < k && inclass) *ap = val;
+          ap += sv_;
+          if (det_run_ && lane == 0 && inclass)
+            a0[(k + 1) * Av->sm + v * sv_] = skip ? xdt : xdt + sdotd * beta;     // :489-497
         }
+        KernArgs* const Ai = fresh_args<NW>(Ak0);
+        if (Ai->infl_adaptive) {                   // (rules_dev::var_updated, restated; also without obs: the class copies its first slot), after every parm read above
+          const int ivq0 = Ai->iv_q_first, ivq1 = Ai->iv_q_last;
+          const unsigned vmask = Ai->var_mask;
+          double* const infl_ = Ai->infl;
+          const long isv_ = Ai->infl_sv;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            const bool skip = qskip && v >= ivq0 && v <= ivq1;
+            if (!skip && lane == 0 && ((vmask >> v) & 1u)) infl_[pt + isv_ * (long)v] = infl_new;
+          }
+        }
+      } else if (A.infl_adaptive && n > 0 && lane == 0) {
+        A.infl[pt] = infl_new;
       }
-    } else if (A.infl_adaptive && n > 0 && lane == 0) {
-      A.infl[pt] = infl_new;
+    } else {
+      if (NV > 0 && das) {
+        double* ap = a0 + moff;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;   // (rules_dev::var_skipped, restated)
+          double x, xm, xdt;
+          if constexpr (MAPPLY) {
+            // x' comes back from the LDS copy of B (it survives the output transposition): keeping the 22 registers of xv
+            // alive through the matrix phase made hipcc spill LDS addresses there -- a scratch round trip in front of
+            // every MFMA step of the U product (PROF build ISA)
+            const double xl = slice[kBmOff + (lane < kBmRows ? lane : kBmRows - 1) * 16 + 2 + v];
+            x = (lane < k) ? xl : 0.0;
+            xm = readlane_d(xm_l, v);
+            xdt = readlane_d(xd_l, v);
+          } else {
+            x = (lane < k) ? bmat[mrow_l * NBP + 2 + v] : 0.0;
+            xm = xmean[v];
+            xdt = xdet[v];
+          }
+          const double sdot = preduce<NW, 0>(x * out[0], red, rslot);
+          const double sdotd = A.det_run ? preduce<NW, 0>(x * out[1], red, rslot) : 0.0;
+          double val;
+          if (skip) {
+            val = xm + x;
+          } else {
+            const double pert = cf[v] * out[2 + v] + rtpp_diag(A, pt, v) * x;
+            val = analysis_value(xm, x, beta, pert, sdot);
+            if (A.q_sprd_max > 0.0 && v == A.iv_q_first) {
+              const double q_mean = preduce<NW, 0>(lane < k ? val : 0.0, red, rslot) / (double)k;
+              const double dq = (lane < k) ? val - q_mean : 0.0;
+              const double q_sprd = sqrt(preduce<NW, 0>(dq * dq, red, rslot) / km1) / q_mean;
+              val = q_clamped(val, q_mean, dq, q_sprd, A.q_sprd_max);
+            }
+          }
+          const bool inclass = (A.var_mask >> v) & 1u;
+          if (lane < k && inclass) *ap = val;
+          ap += A.sv;
+          if (A.det_run && lane == 0 && inclass)
+            a0[(k + 1) * A.sm + v * A.sv] = skip ? xdt : xdt + sdotd * beta;     // :489-497
+        }
+        if (A.infl_adaptive) {                       // (rules_dev::var_updated, restated; also without obs: the class copies its first slot), after every parm read above
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            const bool skip = qskip && v >= A.iv_q_first && v <= A.iv_q_last;
+            if (!skip && lane == 0 && ((A.var_mask >> v) & 1u)) A.infl[pt + A.infl_sv * (long)v] = infl_new;
+          }
+        }
+      } else if (A.infl_adaptive && n > 0 && lane == 0) {
+        A.infl[pt] = infl_new;
+      }
     }
 
     // ------------------------------------------------------------ optional outputs
-    if (A.transm_out && lane < k) A.transm_out[(size_t)pt * k + lane] = out[0];
-    if (A.transmd_out && lane < k) A.transmd_out[(size_t)pt * k + lane] = out[1];
+    if constexpr (NW == 1) {
+      KernArgs* const Ao = fresh_args<NW>(Ak0);
+      if (double* const t_ = Ao->transm_out; t_ && lane < k) t_[(size_t)pt * k + lane] = out[0];
+      if (double* const t_ = Ao->transmd_out; t_ && lane < k) t_[(size_t)pt * k + lane] = out[1];
+    } else {
+      if (A.transm_out && lane < k) A.transm_out[(size_t)pt * k + lane] = out[0];
+      if (A.transmd_out && lane < k) A.transmd_out[(size_t)pt * k + lane] = out[1];
+    }
     if (KKOUT && (A.trans_out || A.pa_out)) {
       // T = V diag(sc1) V^T and Pa = V diag(sc2) V^T: same row-gather with C[j][:] = sc * v_j
       #pragma unroll 1
@@ -1852,7 +1994,14 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       }
     }
     PROF_MARK(8)
-    if (lane == 0) {
+    if constexpr (NW == 1) {
+      KernArgs* const As = fresh_args<NW>(Ak0);
+      if (lane == 0) {
+        if (int* const o_ = As->status) o_[pt] = st;
+        if (int* const o_ = As->nsweep) o_[pt] = sweeps;
+        if (int* const o_ = As->nobs_out) o_[pt] = n;
+      }
+    } else if (lane == 0) {
       if (A.status) A.status[pt] = st;
       if (A.nsweep) A.nsweep[pt] = sweeps;
       if (A.nobs_out) A.nobs_out[pt] = n;
