@@ -10,6 +10,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "letkf_api_internal.h"
+#include "letkf_sched_dev.h"
 
 using namespace letkf::api;
 
@@ -228,12 +229,15 @@ std::string route_path(const letkf::PointArgs& a, const Route& r) {
 int prepare_wave(letkf_ctx* c, letkf::PointArgs& a, const Route& r, int warm_run, long warm_stride) {
   int run_req = warm_run;
   if (const char* e = LETKF_KNOB("LETKF_AMD_RUN_LEN")) run_req = std::atoi(e);   // PROF knob: 1 = all cold
-  size_t wbytes = 0;
   a.warm_stride = warm_stride > 1 ? warm_stride : 1;
   if (a.npts % a.warm_stride != 0) return fail(LETKF_E_INVALID, "warm_stride does not divide npts");
-  letkf::wave_launch_shape(a.k, a.mode, a.npts, c->num_cu, run_req, a.warm_stride, &a.run_len, &a.wave_grid, &wbytes);
+  // (occupancy 0: the launcher asks again with its kernel's; what is taken here does not depend on it)
+  const letkf::LaunchShape s = letkf::launch_shape(r.family == Family::trio, a.k, a.mode, a.npts, a.warm_stride, run_req, c->num_cu,
+                                                   0, true, letkf::wave_grid_per_cu());
+  a.run_len = s.run_len;
+  a.wave_grid = s.grid_ws;
   if (r.family == Family::wave) {   // (the trio kernel parks its eigenvectors in LDS)
-    if (int rc = grow(c, &c->warm_ws, wbytes)) return rc;
+    if (int rc = grow(c, &c->warm_ws, s.warm_bytes)) return rc;
     a.warm_ws = reinterpret_cast<double*>(c->warm_ws.p);
   }
   if (a.mode == 3) {   // one local-list slot per wave of the grid (4 waves per workgroup): idx | rdiag | rloc

@@ -125,13 +125,13 @@ struct PointArgs {
   int* sl_idx;
   double *sl_rd, *sl_rl;
   long sl_cap;
-  // wave kernel: launch shape and warm-start workspace (wave_launch_shape)
+  // wave kernel: launch shape and warm-start workspace (letkf_launch_shape.h)
   double* warm_ws;
   int run_len, wave_grid, warm_dbg;
   long warm_stride;           // >= 1: a run walks points p, p + warm_stride, ... (letkf_das_args.warm_stride)
   int skip_trivial;           // points with beta == 0 or without observations were done by letkf_trivial_points_kernel: skip them
   unsigned* sched;            // dynamic run scheduling: 8 counters 64 bytes apart, zeroed before the launch (null: static dealing)
-  SchedPlan plan;             // ... and its plan, filled in by launch_wave_kernel for the grid it launches
+  SchedPlan plan;             // ... and its plan, filled in by the launcher for the grid it launches
   unsigned long long* prof;   // profiling build (-DLETKF_WAVE_PROF) only: per-phase s_memtime totals, else null
 };
 
@@ -235,17 +235,13 @@ hipError_t launch_search_columns_limited(const letkf_search_tables& t, long nij1
                                          int* nobs_ctype, double* cutd_ctype, int num_cu, hipStream_t st);
 hipError_t launch_point_kernel(const PointArgs& a, const PointPlan& p, hipStream_t st);
 bool wave_kernel_supports(int k, int nv, int mode);
-int wave_kernel_kr(int k);   // rows of the instantiation that serves k
-int wave_kernel_nw(int k);   // ... and its wavefronts per point
-void wave_launch_shape(int k, int mode, long npts, int num_cu, int run_req, long stride, int* run_len, int* grid,
-                       size_t* ws_bytes);
+int wave_grid_per_cu();       // 16; the PROF twin's knob (launch shape: letkf_launch_shape.h)
 hipError_t launch_wave_kernel(const PointArgs& a, int num_cu, hipStream_t st);
 // three points per wave for k <= 20 (letkf_trio.hip)
 bool trio_kernel_supports(const PointArgs& a);
 hipError_t launch_trio_kernel(const PointArgs& a, int num_cu, hipStream_t st);
 int trio_kernel_kr(int k);
 int trio_points_per_wave(int k);
-int sched_plan_check(long npts, long stride, int run_len, int grid, int ppw, int resident_per_xcd, int ub_of);
 bool trivial_pass_supports(const PointArgs& a);
 hipError_t launch_trivial_points(const PointArgs& a, hipStream_t st);
 // (letkf_trivial.hip) transmd[nbatch][ne] zeroed where nobsl == 0; counts zeroed where beta == 0

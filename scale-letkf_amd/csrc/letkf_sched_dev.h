@@ -1,10 +1,12 @@
 // letkf_sched_dev.h -- the dynamic run scheduling of the solve kernels (letkf_wave_dev.h: one run per unit; letkf_trio.hip:
-// units of three runs): how a wave draws its next unit on the device, and how the host makes the plan and readies the
-// counters for a launch.  sched_plan_check (letkf_wave.hip) walks a plan on the host for the tests.
+// units of three runs): how a wave draws its next unit on the device, and how the host readies the counters for a launch
+// and walks a plan for the tests.  The plan itself is made with the launch shape, in letkf_launch_shape.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "letkf_device.h"
+#include <vector>
+
+#include "letkf_launch_shape.h"
 
 namespace letkf {
 
@@ -76,42 +78,37 @@ __device__ __forceinline__ int sched_next(const SchedPlan& P, unsigned* cnt, con
   return -1;
 }
 
-// host: the plan for a grid of `grid` workgroups with ppw wave-slots each, `resident` wave-slots in flight per XCD
-inline void sched_make_plan(SchedPlan& P, const long npts, const long stride, const int run_len, const int grid, const int ppw,
-                            const int resident_per_xcd, const int ub_of = 1) {
-  const long S = stride > 1 ? stride : 1, rl = run_len > 1 ? run_len : 1;
-  const long nruns = S * ((npts / S + rl - 1) / rl);
-  // short runs are bundled (a draw should cover ~16 points), as long as that leaves every wave-slot of the grid four units
-  int ub = rl >= 16 ? 1 : (int)((16 + rl - 1) / rl);
-  const long most = nruns / (4L * grid * ppw);
-  if (ub > most) ub = most < 1 ? 1 : (int)most;
-  // ub_of > 1 (letkf_trio.hip: three runs are walked in step): whole multiples of it
-  if (ub_of > 1) ub = (ub + ub_of - 1) / ub_of * ub_of;
-  const long n = (nruns + ub - 1) / ub;
-  // whole runs of 8 points or more may be quartered at the end of a range: as many as the XCD has wave-slots in flight
-  const int fs = (ub == 1 && rl >= 8) ? ((long)grid * ppw / 8 < resident_per_xcd ? (int)((long)grid * ppw / 8) : resident_per_xcd) : 0;
-  const int q = (int)(n >> 3), r = (int)(n & 7);
+// host (include/letkf_amd.h, letkf_sched_plan_check): every run exactly once, whole or as four quarters?  0, or what failed
+inline int sched_plan_check(long npts, long stride, int run_len, int grid, int ppw, int resident_per_xcd, int ub_of) {
+  if (npts < 0 || grid < 1 || ppw < 1 || run_len < 1 || ub_of < 1) return -1;
+  SchedPlan P;
+  sched_make_plan(P, npts, stride, run_len, grid, ppw, resident_per_xcd, ub_of);
+  if (P.nruns > (1L << 27)) return -2;
+  if (P.ub % ub_of != 0) return -9;                            // (letkf_trio.hip: units are whole multiples of three runs)
+  std::vector<unsigned char> seen((size_t)P.nruns, 0);   // bit 7: whole, bits 0-3: quarters
   for (int x = 0; x < 8; ++x) {
-    const int len = q + (x < r ? 1 : 0);
-    P.base[x] = x * q + (x < r ? x : r);
-    P.f[x] = fs < len ? fs : len;
-    P.whole[x] = len - P.f[x];
-    P.t[x] = P.f[x] > 0 ? len / P.f[x] : 1;
-    const long mine = (long)((grid - x + 7) >> 3) * ppw;              // wave-slots of the grid that sit on XCD x
-    const long units = (long)P.whole[x] + 4L * P.f[x];
-    P.nstat[x] = (int)(mine < units ? mine : units);
-    P.magic[x] = P.t[x] > 1 ? ((1ull << 40) / (unsigned long long)(P.t[x] - 1)) + 1ull : 0ull;
+    if (P.nstat[x] < 0 || P.nstat[x] > P.whole[x] + 4 * P.f[x]) return -3;
+    for (int i = 0; i < P.whole[x] + 4 * P.f[x]; ++i) {
+      const int code = sched_unit(P, x, i);
+      const long u = code >> 3;
+      for (long rid = u * P.ub; rid < (u + 1) * P.ub && rid < P.nruns; ++rid) {
+        if (rid < 0) return -4;
+        const unsigned char bit = (code & 4) ? (unsigned char)(1u << (code & 3)) : (unsigned char)0x80;
+        if ((code & 4) && P.ub != 1) return -5;
+        if (seen[(size_t)rid] & (bit | ((code & 4) ? 0x80 : 0x0f))) return -6;    // handed out twice
+        seen[(size_t)rid] |= bit;
+      }
+      if (u * P.ub >= P.nruns) return -7;                                          // a unit beyond the last run
+    }
   }
-  P.ub = ub;
-  P.nruns = nruns;
+  for (long rid = 0; rid < P.nruns; ++rid)
+    if (seen[(size_t)rid] != 0x80 && seen[(size_t)rid] != 0x0f) return -8;         // missed, or quartered in part
+  return 0;
 }
 
-// host, after sched_make_plan and before the launch: the counters start at zero -- unless every unit is given out by position
-// (a small batch): then nothing is drawn, and whatever non-negative counts an earlier launch left behind read as "nothing left"
-inline hipError_t sched_reset_counters(const SchedPlan& P, unsigned* sched, hipStream_t st) {
-  bool draws = false;
-  for (int x = 0; x < 8; ++x) draws = draws || P.whole[x] + 4 * P.f[x] > P.nstat[x];
-  return draws ? hipMemsetAsync(sched, 0, 512, st) : hipSuccess;
+// host, before the launch: the counters start at zero where the shape's plan draws from them
+inline hipError_t sched_reset_counters(const LaunchShape& s, unsigned* sched, hipStream_t st) {
+  return s.reset_counters ? hipMemsetAsync(sched, 0, 512, st) : hipSuccess;
 }
 
 }  // namespace letkf

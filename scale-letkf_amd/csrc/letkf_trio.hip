@@ -917,29 +917,13 @@ hipError_t launch_trio(const PointArgs& a, int num_cu, hipStream_t st) {
   if (hipError_t e = lds_opt_in(&letkf_trio_kernel<KR, P>, lds)) return e;
   const int occ = resident_blocks(&letkf_trio_kernel<KR, P>, 256, lds, 2);
   if (!a.sched) return hipErrorInvalidValue;
-  const long res = (long)occ * num_cu;
-  constexpr long kMinRun = 4, kUnitsPerWave = 2;
-  long rl_ = a.npts / (P * kUnitsPerWave * res * 4);
-  if (rl_ < kMinRun) rl_ = kMinRun;
-  if (rl_ > a.run_len) rl_ = a.run_len;
-  const long S = a.warm_stride > 1 ? a.warm_stride : 1, rl = rl_ > 1 ? rl_ : 1;
-  const long nruns = S * ((a.npts / S + rl - 1) / rl);
-  const long nunits = (nruns + P - 1) / P;
-  long grid_ = (nunits + 3) / 4;               // a wave-slot per unit, at most what is resident together
-  if (grid_ > res) grid_ = res;
-  const int grid = (int)(grid_ < 1 ? 1 : grid_);
+  static_assert(P == kTrioRuns, "launch_shape: units of P runs");
+  const LaunchShape s = launch_shape(true, a.k, a.mode, a.npts, a.warm_stride, a.run_len, num_cu, occ, true, wave_grid_per_cu());
   PointArgs b = a;
-  // a small domain (BASELINE configs[0]: 1600 columns of 30 levels) has fewer units of three whole runs than the GPU has waves:
-  // shorter runs then (the first point of a run starts cold), down to 4 points, until there are two units per wave
-  {
-    const long slots = res * 4;
-    long want = a.npts / (P * kUnitsPerWave * slots);
-    if (want < kMinRun) want = kMinRun;
-    if (b.run_len > want) b.run_len = (int)want;
-  }
-  sched_make_plan(b.plan, a.npts, a.warm_stride, b.run_len, grid, 4, 256, P);   // units of P runs
-  if (hipError_t e = sched_reset_counters(b.plan, a.sched, st)) return e;
-  hipLaunchKernelGGL((letkf_trio_kernel<KR, P>), dim3(grid), dim3(256), lds, st, b);
+  b.run_len = s.run_len;
+  b.plan = s.plan;
+  if (hipError_t e = sched_reset_counters(s, a.sched, st)) return e;
+  hipLaunchKernelGGL((letkf_trio_kernel<KR, P>), dim3(s.grid), dim3(256), lds, st, b);
   return hipGetLastError();
 }
 

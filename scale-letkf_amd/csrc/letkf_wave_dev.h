@@ -531,14 +531,11 @@ __host__ __device__ constexpr int wave_kmin(int KR, int NW) {
 // conversion chunk is KR rows (not 24), the apply phase's output buffer 32 rows (not 64): 12.5 KB per wave, 50 KB per workgroup,
 // room for THREE workgroups per CU.  Measured (r4, A/B in one gpurun call, -DLETKF_SMALL_OCC=3 against 2): the register budget
 // of three waves per SIMD (168) costs this kernel 464 B/lane of scratch instead of 136 -- C2-k20 -6 %, C1 +4 %.  The default
-// stays at two; the slice stays small.
+// stays at two (letkf_launch_shape.h, which counts the wave-slots in flight with it); the slice stays small.
 __host__ __device__ constexpr bool wave_small(int KR, int NW) { return NW == 1 && KR <= 20; }
 __host__ __device__ constexpr int wave_base_doubles(int KR, int NW) { return wave_small(KR, NW) ? 1280 : 1536 * NW; }
 __host__ __device__ constexpr int wave_jacobi_rc(int KR, int NW) { return wave_small(KR, NW) ? KR : 24; }   // rows per conversion chunk
 __host__ __device__ constexpr int wave_ob_rows(int KR) { return KR <= 20 ? 32 : 64; }                        // rows of the MAPPLY output buffer
-#ifndef LETKF_SMALL_OCC
-#define LETKF_SMALL_OCC 2
-#endif
 __host__ __device__ constexpr int wave_occupancy(int KR, int NW) { return NW == 1 ? (wave_small(KR, NW) ? LETKF_SMALL_OCC : 2) : 1; }
 
 // per-wave LDS slice (doubles)
@@ -2017,33 +2014,15 @@ static hipError_t launch_wave(const PointArgs& a, int num_cu, hipStream_t st) {
   const size_t lds = (size_t)(NW == 1 ? 4 : 1) * wave_slice_doubles(KR, NV, NW) * sizeof(double);
   if (a.k < wave_kmin(KR, NW) || a.k > KR) return hipErrorInvalidValue;   // the Gram assumes its full member blocks
   if (hipError_t e = lds_opt_in(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, lds)) return e;
-  // Dynamic scheduling: a grid of exactly the workgroups that are resident together (every wave owns its first unit by
-  // its position, the rest is drawn; a workgroup that had to wait for a slot would sit on its first unit until the others
-  // have drawn everything else).  The PROF twin's static dealing keeps round 1's oversubscribed grid.
-  int grid = a.wave_grid;
-  if (a.sched) {
-    const int occ = resident_blocks(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, NW == 1 ? 256 : 128, lds, NW == 1 ? 2 : 1);
-    const long res = (long)occ * num_cu;
-    const long S = a.warm_stride > 1 ? a.warm_stride : 1, rl = a.run_len > 1 ? a.run_len : 1;
-    const long nruns = S * ((a.npts / S + rl - 1) / rl);
-    constexpr int PPW = NW == 1 ? 4 : 1;
-    if (NW == 1 && nruns < 8 * res * PPW) {
-      // A small batch (fewer than 8 runs per resident wave) on one-wave points: every wave gets exactly one run, by its
-      // position, and the hardware starts the next workgroup when one is done.  Measured with the PROF twin on C2-mini
-      // (2.25 runs per wave): of two waves on a SIMD the older one is served first and draws most of the runs, the
-      // younger one is left with its last run when everything is drawn, alone on its SIMD -- 4.9 ms against 4.4 ms.
-      const long need = 8 * (((nruns + 7) / 8 + PPW - 1) / PPW);
-      if (grid > need) grid = (int)need;
-    } else if (grid > res) {
-      grid = (int)res;
-    }
-  }
+  // (the PROF twin's static dealing launches the shape's unclamped grid and needs no occupancy)
+  const int occ = a.sched ? resident_blocks(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, NW == 1 ? 256 : 128, lds, NW == 1 ? 2 : 1) : 0;
+  const LaunchShape s = launch_shape(false, a.k, a.mode, a.npts, a.warm_stride, a.run_len, num_cu, occ, a.sched != nullptr, wave_grid_per_cu());
+  static_assert(NW != 1 || wave_occupancy(KR, NW) == (KR <= 20 ? LETKF_SMALL_OCC : 2), "launch_shape counts resident_per_xcd with these");
   PointArgs b = a;
-  if (a.sched) {
-    sched_make_plan(b.plan, a.npts, a.warm_stride, a.run_len, grid, NW == 1 ? 4 : 1, NW == 1 ? 128 * wave_occupancy(KR, NW) : 64);   // wave-slots in flight per XCD (32 CUs)
-    if (hipError_t e = sched_reset_counters(b.plan, a.sched, st)) return e;
-  }
-  hipLaunchKernelGGL((letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>), dim3(grid), dim3(NW == 1 ? 256 : 128), lds, st, b);
+  b.run_len = s.run_len;
+  b.plan = s.plan;
+  if (hipError_t e = sched_reset_counters(s, a.sched, st)) return e;
+  hipLaunchKernelGGL((letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>), dim3(s.grid), dim3(NW == 1 ? 256 : 128), lds, st, b);
   return hipGetLastError();
 }
 

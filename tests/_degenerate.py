@@ -216,11 +216,11 @@ def run_positions(npts, run_len, warm_stride):
     return [rid % 3, a % run_len]
 
 
-TRIO_RUN_CAP = 4        # letkf_trio.hip launch_trio: on a batch too small to give every resident wave two units of three runs
+TRIO_RUN_CAP = 4        # letkf_launch_shape.h launch_shape: on a batch too small to give every resident wave two units of three runs
 #                         (P * 2 * resident waves * 4 points: tens of thousands) the kernel shortens the runs to four points
 ARRANGEMENTS = {        # name -> (warm_run passed, run length it gives, stride: 0 consecutive / "nij1")
     # warm_run = 0, the library's default, means runs of UP TO 16: 16 from 64 points per wave slot of the GPU on, shorter below
-    # (letkf_wave.hip wave_launch_shape), one on a test-sized batch.  So the default's length is asked for by its number.
+    # (letkf_launch_shape.h launch_shape), one on a test-sized batch.  So the default's length is asked for by its number.
     "run16": (16, 16, 0),
     "off": (1, 1, 0),
     "stride": (4, 4, "nij1"),
