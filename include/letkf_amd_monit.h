@@ -7,7 +7,8 @@
  *   letkf_monit_obs_dev          the loop of monit_obs (common_obs_scale.f90:1467-1599) and its monit_dep (:1819)
  *   letkf_monit_type             the list of monitored elements (:1821-1837)
  * DESIGN.md section 13 has the details.  The ranks' MPI_ALLREDUCE of the statistics, the MPI_GATHERV of the records,
- * write_obs_dep, the LOG_LEVEL >= 3 prints, H08 and the TC vitals stay the host's.
+ * write_obs_dep, the LOG_LEVEL >= 3 prints, DEPARTURE_STAT_H08 and the TC vitals stay the host's (the H08 operator itself is
+ * letkf_amd_h08.h).
  *
  * letkf_state_to_history_dev.  Writes member slot 0 of the layout `layout` describes (dimensions, halos, the strides
  * s3k .. s3v and s2i .. s2v, nv3dd >= 13, nv2dd >= 7) into v3d / v2d; layout->v3d, v2d, nmem, m0, s3m and s2m are not read.

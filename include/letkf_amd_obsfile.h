@@ -19,7 +19,7 @@
  *                                                            radar lon, lat, z           write_obs_radar :2411-2594
  *   3 LETKF_OBSFILE_OBSDA         4, 6 under -DH08           none                        read_obs_da / write_obs_da :2275-2352
  *   4 LETKF_OBSFILE_DEP           11                         none                        write_obs_dep :2354-2409
- * The H08 observation format (read_obs_H08) is NOT handled.
+ * The H08 observation format (read_obs_H08) is handled by letkf_amd_h08.h, not here.
  * wk = elm, lon, lat, lev, dat, err, typ, dif (conventional, radar); set, idx, value, qc [, lev, val2] (obsda); the eight of the
  * file row, then qc, omb, oma (departure).
  *

@@ -11,7 +11,7 @@
  * DESIGN.md section 14 has the details.  THE HOST'S PART: zeroing files->dat before the first slot (:807-809); the
  * MPI_REDUCE of dat over the subdomains (:1008) between the slots and the noise; write_obs_all (:1055); reading the nature
  * run (read_ens_history_iter, :817); the clock seed idate(8) + idate(7) * 1000 of com_randn, if the clock is wanted.
- * H08-format files are not passed.
+ * H08-format files are not passed (their records and operator are letkf_amd_h08.h; the reference marks obsmake for H08 unavailable).
  *
  * THE RANDOM STREAM.  letkf_rand is host state: the generator of one init_gen_rand(seed).
  *   letkf_rand_res53(r, n, out)   out (HOST) = the next n values of genrand_res53: com_rand without its clock seeding.

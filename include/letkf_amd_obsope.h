@@ -23,6 +23,7 @@
  *   qc from the coordinate search (98 outside 1 .. nlonh / nlath, 20 too high, 21 too low) leaves the value 0.
  * The real literals the reference writes without a kind (273.16, 1e-3, 1.84, ...) are single precision there and are
  * widened from single precision here.  H08, TC vitals, rain and USE_RADAR_PSEUDO_RH are not covered: qc 90.
+ * (H08 rows are served by letkf_amd_h08.h after this entry, TC vitals by letkf_amd_tcvital.h.)
  * stggrd = 1 (what monit_obs passes): U is read at ri - 0.5, V at rj - 0.5 and, in the radar operator only, W at rk - 0.5.
  *
  * WHERE THE REFERENCE IS UNDEFINED.  CEILING of an integer coordinate puts weight exactly 0 on index i - 1; at

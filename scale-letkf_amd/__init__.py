@@ -23,6 +23,7 @@ MAPPROJ_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_mapproj.so")   # the 
 OBSFILE_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_obsfile.so")   # the record codec of the observation files (include/letkf_amd_obsfile.h); made by `make obsfile`, in the same way
 NOBSOUT_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_nobsout.so")   # NOBS_OUT (include/letkf_amd_nobsout.h); made by `make nobsout`, in the same way
 TCVITAL_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_tcvital.so")   # the TC vitals (include/letkf_amd_tcvital.h); made by `make tcvital`, in the same way
+H08_LIB_PATH = os.path.join(HERE, "lib", "libletkf_amd_h08.so")           # the Himawari-8 radiances (include/letkf_amd_h08.h); made by `make h08`, in the same way
 
 LETKF_OK = 0
 ST_OK, ST_NOT_CONVERGED, ST_NONPOSITIVE, ST_ILLCOND = 0, 1, 2, 3
@@ -37,13 +38,13 @@ def build(force=False):
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     srcs += glob.glob(os.path.join(HERE, "csrc", "obsscan", "*")) + glob.glob(os.path.join(HERE, "csrc", "mapproj", "*"))
     srcs += glob.glob(os.path.join(HERE, "csrc", "obsfile", "*")) + glob.glob(os.path.join(HERE, "csrc", "nobsout", "*"))
-    srcs += glob.glob(os.path.join(HERE, "csrc", "tcvital", "*"))
+    srcs += glob.glob(os.path.join(HERE, "csrc", "tcvital", "*")) + glob.glob(os.path.join(HERE, "csrc", "h08", "*"))
     srcs += glob.glob(os.path.join(HERE, "..", "include", "letkf_amd*.h"))
     srcs = [s for s in srcs if os.path.isfile(s)]      # (a directory's time is that of its last new entry, not of a source)
     if os.environ.get("LETKF_AMD_LIB") and os.path.exists(LIB_PATH) and not force:
         return LIB_PATH                      # an A/B or profiling twin: taken as it is, whatever its age
     libs = (LIB_PATH, OSSE_LIB_PATH, OBSSIM_LIB_PATH, SUPEROB_LIB_PATH, OBSSCAN_LIB_PATH, MAPPROJ_LIB_PATH, OBSFILE_LIB_PATH, NOBSOUT_LIB_PATH) + (
-        TCVITAL_LIB_PATH,)
+        TCVITAL_LIB_PATH,) + (H08_LIB_PATH,)
     stale = force or not all(os.path.exists(l) for l in libs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(l) for l in libs) for s in srcs)
     if stale:                                # (make's chatter to stderr: stdout belongs to the caller's JSON line)
@@ -53,6 +54,7 @@ def build(force=False):
         subprocess.check_call(["make", "-j4", "-C", HERE, "obsfile"], stdout=2)   # (and this)
         subprocess.check_call(["make", "-j4", "-C", HERE, "nobsout"], stdout=2)   # (and this)
         subprocess.check_call(["make", "-j4", "-C", HERE, "tcvital"], stdout=2)   # (and this)
+        subprocess.check_call(["make", "-j4", "-C", HERE, "h08"], stdout=2)       # (and this)
     return LIB_PATH
 
 
@@ -688,6 +690,54 @@ TCVITAL_SIGNATURES = {
 TCVITAL_ID_TCX, TCVITAL_ID_TCY, TCVITAL_ID_TCP, TCVITAL_QC_BAD = 99991, 99992, 99993, 50
 TCVITAL_NONE = 9.99e33
 
+
+class H08Params(C.Structure):
+    """letkf_h08_params (include/letkf_amd_h08.h): sizes and switches, H08_CH_USE, this rank's offsets, the constants of the
+    profile conversion and of the zenith angle, H08_CLDSKY_THRS and the buffer box"""
+    _fields_ = ([(n, C.c_int32) for n in ("nlev", "nprof_file", "top_down", "stggrd", "rttov_units", "reject_land", "use_obs23",
+                                          "finish", "member", "reserved0")] + [("ch_use", C.c_int32 * 10)] +
+                [(n, C.c_double) for n in ("ri_off", "rj_off", "rd", "rv", "q_ppmv", "qmin", "minq", "cfrac_cnst", "sub_lon", "r_pol",
+                                           "r_sat", "ell_tan", "ell_ecc", "cldsky_thrs", "bris", "brie", "brjs", "brje")])
+
+
+class H08Profiles(C.Structure):
+    """letkf_h08_profiles (include/letkf_amd_h08.h): the outputs of letkf_h08_profiles_dev, device arrays"""
+    _fields_ = [(n, C.c_void_p) for n in ("lev3", "sfc", "cloud", "pflag")]
+
+
+# ... and of the thirteenth companion header include/letkf_amd_h08.h: the entries are exported by the library of the Himawari-8
+# radiances (H08_LIB_PATH, h08_lib()).  (SIGNATURES, as the four tables before it.)
+H08_VERSION = 1
+H08_SIGNATURES = {
+    "letkf_h08_count": [_I64, _VP],
+    "letkf_h08_bytes": [_I64, _VP],
+    "letkf_h08_decode_dev": [_VP, _I32, _VP, _I64, _VP, _VP, _VP],
+    "letkf_h08_encode_dev": [_VP, _I32, _I64, _VP, _VP],
+    "letkf_h08_select_dev": [_VP, _VP, _VP, _I64, _I64, _I32, _I64, _VP, _VP, _VP],
+    "letkf_h08_profiles_dev": [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    "letkf_h08_rows_dev": [_VP, _VP, _I64, _I64, _VP, _VP, _I32, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32,
+                           _VP, _VP, _I64, _VP, _VP],
+}
+H08_NCH, H08_ID, H08_QC_BAD = 10, 8800, 50
+
+
+def h08_params(**kw):
+    """H08Params with the reference's constants (scale_H08_fwd.F90:137-139, :553-555; scale_const's Rdry / Rvap; RTTOV's
+    q_mixratio_to_ppmv and qmin; H08_CLDSKY_THRS = -5, H08_RTTOV_MINQ = 0.1, H08_RTTOV_CFRAC_CNST = 0.1, every channel used, no
+    buffer), overridden by the keywords; ch_use takes a sequence of ten"""
+    d = dict(use_obs23=1, member=1, rd=287.04, rv=461.46, q_ppmv=1.60771704e6, qmin=0.1e-10, minq=0.1, cfrac_cnst=0.1, sub_lon=140.7,
+             r_pol=6356.7523e3, r_sat=42164.0e3, ell_tan=0.993305616, ell_ecc=0.00669438444, cldsky_thrs=-5.0, bris=-1.0e300,
+             brie=1.0e300, brjs=-1.0e300, brje=1.0e300, ch_use=(1,) * 10)
+    d.update(kw)
+    p = H08Params()
+    for k, v in d.items():
+        if k == "ch_use":
+            p.ch_use[:] = [int(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 _libs = {}
 
 
@@ -763,6 +813,30 @@ def tcvital_lib():
     """dlopen the library of the TC vitals, after the main one whose context and scratch buffer it uses."""
     lib()
     return _load(TCVITAL_LIB_PATH, (TCVITAL_SIGNATURES,))
+
+
+def h08_lib():
+    """dlopen the library of the Himawari-8 radiances, after the main one whose context, scratch buffer and scan it uses."""
+    lib()
+    return _load(H08_LIB_PATH, (H08_SIGNATURES,))
+
+
+def h08_count(nbytes):
+    """letkf_h08_count: the profiles of a Himawari-8 file of nbytes (ten rows each); LetkfError unless a whole number of records"""
+    out = C.c_int64()
+    rc = h08_lib().letkf_h08_count(nbytes, C.addressof(out))
+    if rc != LETKF_OK:
+        raise LetkfError(rc, lib().letkf_amd_last_error().decode())
+    return out.value
+
+
+def h08_bytes(nprof):
+    """letkf_h08_bytes: the bytes of a Himawari-8 file of nprof profiles"""
+    out = C.c_int64()
+    rc = h08_lib().letkf_h08_bytes(nprof, C.addressof(out))
+    if rc != LETKF_OK:
+        raise LetkfError(rc, lib().letkf_amd_last_error().decode())
+    return out.value
 
 
 def _obsfile_size(entry, fmt, nrec, n):
@@ -1130,6 +1204,88 @@ class Context:
         nmem = cand_all.shape[1] if nmem is None else nmem
         self._check(tcvital_lib().letkf_tcvital_fill_dev(self._c, nproc, nmem, m0, _ptr(cand_all), _hptr(r), int(qc_replace), _ptr(qc),
                                                          _ptr(ensval), kld))
+
+    # ---- the Himawari-8 radiances (include/letkf_amd_h08.h)
+    def h08_decode(self, image, obserr, big_endian=False, want=OBSFILE_COLUMNS, check=False, out=None, nprof=None):
+        """letkf_h08_decode_dev: a Himawari-8 file image to a dict of the columns of `want`, ten rows per profile (lev = 7 .. 16,
+        err = obserr[channel], dif = 0), with "nbad" (check=True).  `out`: a dict of tensors to write into."""
+        import numpy as np
+        import torch
+        n = h08_count(self._image_bytes(image)) if nprof is None else nprof
+        if out is None:
+            out = {k: torch.empty(n * H08_NCH, dtype=torch.int32 if k in ("elm", "typ") else torch.float64, device=image.device)
+                   if k in want else None for k in OBSFILE_COLUMNS}
+        o = ObsfileCols()
+        for k in OBSFILE_COLUMNS:
+            setattr(o, k, _ptr(out.get(k)))
+        e = np.ascontiguousarray(obserr, dtype=np.float64)
+        assert e.size == H08_NCH
+        nbad = C.c_int64(-1)
+        self._check(h08_lib().letkf_h08_decode_dev(self._c, int(big_endian), _ptr(image), n, _hptr(e), C.addressof(o),
+                                                   C.addressof(nbad) if check else None))
+        res = dict(out)
+        res["nbad"] = nbad.value if check else None
+        return res
+
+    def h08_encode(self, cols, big_endian=False, out=None, nprof=None):
+        """letkf_h08_encode_dev: the columns (a dict of device tensors, ten rows per profile) to the file image, a uint8 device
+        tensor: per profile elm, typ, lon, lat of its first row and the dat of its ten rows."""
+        import torch
+        n = cols["dat"].numel() // H08_NCH if nprof is None else nprof
+        c = ObsfileCols()
+        for k in OBSFILE_COLUMNS:
+            setattr(c, k, _ptr(cols.get(k)))
+        if out is None:
+            out = torch.empty(h08_bytes(n), dtype=torch.uint8, device=cols["dat"].device)
+        self._check(h08_lib().letkf_h08_encode_dev(self._c, int(big_endian), n, C.addressof(c), _ptr(out)))
+        return out
+
+    def h08_select(self, set_, idx, h08_set, nprof_file, row0=0, nrows=None, prof_list=None, slot_of_prof=None):
+        """letkf_h08_select_dev: the profiles of file h08_set (1-based) that the obsda rows [row0, row0 + nrows) name.  Returns
+        (prof_list int32 [nprof_file] of which the first nsel are written, ascending; slot_of_prof int32 [nprof_file], -1 where
+        not selected; nsel)."""
+        import torch
+        nrows = set_.numel() - row0 if nrows is None else nrows
+        if prof_list is None:
+            prof_list = torch.full((nprof_file,), -1, dtype=torch.int32, device=set_.device)
+        if slot_of_prof is None:
+            slot_of_prof = torch.empty(nprof_file, dtype=torch.int32, device=set_.device)
+        nsel = C.c_int64(-1)
+        self._check(h08_lib().letkf_h08_select_dev(self._c, _ptr(set_), _ptr(idx), row0, nrows, h08_set, nprof_file, _ptr(prof_list),
+                                                   _ptr(slot_of_prof), C.addressof(nsel)))
+        return prof_list, slot_of_prof, nsel.value
+
+    def h08_profiles(self, params, fields, nsel, prof_list, ri, rj, lon, lat, rotc=None, out=None):
+        """letkf_h08_profiles_dev: the profile arrays of the fields.nmem members at the nsel profiles of prof_list; ri, rj, lon,
+        lat (and rotc [., 2]) are per FILE profile.  params: H08Params; fields: ObsopeFields.  Returns a dict lev3 [nmem, nsel, 5,
+        nlev], sfc [nmem, nsel, 8], pflag int32 [nsel] and, under params.rttov_units, cloud [nmem, nsel, 3, nlev - 1] (else None);
+        or writes into the dict given."""
+        import torch
+        nmem, nlev, dev = fields.nmem, fields.nlev, prof_list.device
+        if out is None:
+            out = dict(lev3=torch.empty((nmem, nsel, 5, nlev), dtype=torch.float64, device=dev),
+                       sfc=torch.empty((nmem, nsel, 8), dtype=torch.float64, device=dev),
+                       cloud=torch.empty((nmem, nsel, 3, nlev - 1), dtype=torch.float64, device=dev) if params.rttov_units else None,
+                       pflag=torch.empty(nsel, dtype=torch.int32, device=dev))
+        o = H08Profiles()
+        for k, _ in H08Profiles._fields_:
+            setattr(o, k, _ptr(out.get(k)))
+        self._check(h08_lib().letkf_h08_profiles_dev(self._c, C.addressof(params), C.addressof(fields), nsel, _ptr(prof_list), _ptr(ri),
+                                                     _ptr(rj), _ptr(lon), _ptr(lat), _ptr(rotc), C.addressof(o)))
+        return out
+
+    def h08_rows(self, params, set_, idx, h08_set, slot_of_prof, nsel, prof, btall, btclr, trans, rig, rjg, qc, ensval, kld, lev, val2,
+                 nmem=None, m0=0, qc_replace=True, row0=0, nrows=None):
+        """letkf_h08_rows_dev: the obsda rows [row0, row0 + nrows) of file h08_set whose profile is selected, from the radiative
+        transfer's btall, btclr [nmem, nsel, 10] and trans [nmem, nsel, 10, nlev] and the dict `prof` of h08_profiles: ensval[row,
+        m0 + m], qc (replaced or merged by maximum), lev += the weighting function's peak, val2 += btclr, member after member,
+        divided by params.member where params.finish."""
+        nrows = set_.numel() - row0 if nrows is None else nrows
+        nmem = btall.shape[0] if nmem is None else nmem
+        self._check(h08_lib().letkf_h08_rows_dev(self._c, C.addressof(params), row0, nrows, _ptr(set_), _ptr(idx), h08_set,
+                                                 _ptr(slot_of_prof), nsel, nmem, m0, _ptr(prof["lev3"]), _ptr(prof["sfc"]),
+                                                 _ptr(prof["pflag"]), _ptr(btall), _ptr(btclr), _ptr(trans), _ptr(rig), _ptr(rjg),
+                                                 int(qc_replace), _ptr(qc), _ptr(ensval), kld, _ptr(lev), _ptr(val2)))
 
     def das_interp(self, k, nv, tables, nx, ny, nlev, stride_x, stride_y, rig, rjg, rlev, rz, ensval, kld, dep, infl, gues,
                    anal, sp, sm, sv, ws_bytes=0, nobs_coarse=None, npts=None, beta=None, det_run=False, infl_adaptive=False,

@@ -6,7 +6,8 @@
 // (include/letkf_amd_obsscan.h) from the library of the first scan and mapproj/letkf_mapproj_entry.hip
 // (include/letkf_amd_mapproj.h) from the library of the map projection, and nobsout/letkf_nobsout_entry.hip
 // (include/letkf_amd_nobsout.h) from the library of NOBS_OUT, and tcvital/letkf_tcvital_entry.hip (include/letkf_amd_tcvital.h)
-// from the library of the TC vitals.  Every function is defined in the one unit named above its declaration.
+// from the library of the TC vitals, and h08/letkf_h08_entry.hip (include/letkf_amd_h08.h) from the library of the Himawari-8
+// radiances.  Every function is defined in the one unit named above its declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 
