@@ -951,7 +951,27 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       //   MFMA : per 4-obs step 2 ds_read_b128 + NBLK row loads (three steps in flight) + NBLK multiplies
       constexpr int kSC = 256;                                 // obs per batch (4 kSC doubles <= wave_base_doubles of the slice)
       double* stg = slice;
-      const bool mode0 = A.mode != 1;                          // rows come from the obs table (member-fastest)
+      // TRIM (r13, default on; -DLETKF_GRAM_TRIM=0 gives the loop as it was for an A/B; one-wave instantiations only): the tile
+      // loop issues nothing per step that its result does not need.
+      //  * A step past the end is fetched (the pipeline has no conditions around its loads) but never consumed, so its weights
+      //    are not selected to zero, and its chunk index is not clamped: behind the nsp entries of a batch the stage phase
+      //    leaves kPad entries with the row base of the batch's FIRST entry and zero weights (every batch that reaches
+      //    run_steps has one: nsp > 0), which is all the fetches can reach -- chunk nch + 2 kGramDepth - 2 at most.  No row
+      //    base that the stage of THIS batch did not write becomes a load address; the padding of the last step (entries
+      //    ns .. nsp - 1, which ARE consumed, with weight zero) carries that row base too, not row 0 of the table.
+      //  * STRIP: the narrow block is not masked per step.  Its lanes at and past member k hold member 0 of the row (the
+      //    clamped offset below), times sqrt(w): finite.  No matrix instruction reads that operand; what those lanes and the
+      //    broadcast members >= k add up is zeroed once per point behind the loop (accS, racc, rdacc) or lies in columns >= k
+      //    of the matrix, which the eigenproblem's column mask (colzero) clears.
+      //  * The das instantiations (NV > 0) read the obs table, always (launch_wave refuses the dense batch for them), and a
+      //    block below the smallest k of the instantiation needs no clamp: the row offsets are constants.
+#ifndef LETKF_GRAM_TRIM
+#define LETKF_GRAM_TRIM 1
+#endif
+      constexpr bool TRIM = LETKF_GRAM_TRIM && NW == 1;
+      constexpr int kPad = 4 * (2 * kGramDepth - 1);           // TRIM: staged entries behind nsp that a fetch can reach
+      static_assert(!TRIM || 4 * (kSC + kPad) <= wave_base_doubles(KR, NW), "the padded staging area must fit the Gram's part of the slice");
+      const bool mode0 = (TRIM && NV > 0) || A.mode != 1;      // rows come from the obs table (member-fastest)
       const double* ybase = mode0 ? A.ensval : A.hdxb;
       bool rowok[NBLK];
       long mo[NBLK];
@@ -959,9 +979,17 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       for (int I = 0; I < NBLK; ++I) {
         const int m = 16 * I + c16;
         rowok[I] = m < k;
-        const long mm = rowok[I] ? m : 0;
+        // (the last block's clamp stays: a row holds kld >= k doubles, and a lane must not read past the table's last row)
+        const long mm = (TRIM && 16 * (I + 1) <= KMIN) ? m : rowok[I] ? m : 0;
         mo[I] = mode0 ? mm : mm * (long)A.nobs;
       }
+      // TRIM: entries [from, upto) of the staging area <- (row base rb0, weights zero); upto - from <= 64
+      [[maybe_unused]] auto stage_pad = [&](const int from, const int upto, const long rb0) {
+        if (wlane < upto - from) {
+          *reinterpret_cast<double2*>(&stg[4 * (from + wlane)]) = double2{__longlong_as_double(rb0), 0.0};
+          *reinterpret_cast<double2*>(&stg[4 * (from + wlane) + 2]) = double2{0.0, 0.0};
+        }
+      };
       const bool is_d = c16 == (k & 15), is_dd = c16 == ((k + 1) & 15);   // lanes of the two augmented columns
       const int blk_d = k >> 4, blk_dd = (k + 1) >> 4;
       struct Step {
@@ -971,8 +999,20 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
 
       // MFMA steps of 4 obs over the first nsp (multiple of 4) staged entries; with two waves each takes every other step
       auto run_steps = [&](const int nsp) {
-        const int nch = nsp >> 2;
+        // (TRIM: the step count on the scalar unit -- the observation count comes from a vector value, the point number)
+        const int nch = TRIM ? uniform(nsp >> 2) : nsp >> 2;
         auto fetch = [&](const int c, Step& t) {
+          if constexpr (TRIM) {
+            const int i = 4 * c + q;                            // unclamped: see stage_pad
+            const double2 a2 = *reinterpret_cast<const double2*>(&stg[4 * i]);
+            const double2 b2 = *reinterpret_cast<const double2*>(&stg[4 * i + 2]);
+            const long rb = __double_as_longlong(a2.x);
+            t.sw = a2.y;
+            t.dsw = b2.x;
+            t.ddsw = b2.y;
+#pragma unroll
+            for (int I = 0; I < NBLK; ++I) t.f[I] = ybase[rb + mo[I]];
+          } else {
           const bool ok = c < nch;
           const int i = 4 * (ok ? c : 0) + q;
           const double2 a2 = *reinterpret_cast<const double2*>(&stg[4 * i]);
@@ -983,6 +1023,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           t.ddsw = ok ? b2.y : 0.0;
 #pragma unroll
           for (int I = 0; I < NBLK; ++I) t.f[I] = ybase[rb + mo[I]];
+          }
         };
         auto mma = [&](const Step& t) {
           double y[NBLK];
@@ -992,7 +1033,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
             // (blocks that lie below the smallest k this instantiation is dispatched for are all members at compile
             // time: hipcc turns the wave-uniform test into 9 v_cndmask per block and step otherwise)
             if (16 * (I + 1) > KMIN && 16 * (I + 1) > k) {     // wave-uniform: block reaches past the members
-              v = rowok[I] ? v : 0.0;
+              if constexpr (!(TRIM && STRIP)) v = rowok[I] ? v : 0.0;   // (TRIM: the narrow block is cleaned up behind the loop)
               if constexpr (!STRIP) {
                 if (I == blk_d && is_d) v = t.dsw;
                 if (I == blk_dd && is_dd) v = t.ddsw;
@@ -1036,7 +1077,8 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           }
         };
         // PD steps in flight.  Three things keep the pipeline the way it is written (each found in the ISA):
-        //  * no conditions around the fetches (a step past the end has sw = dsw = ddsw = 0 and adds nothing): with
+        //  * no conditions around the fetches (a step past the end is fetched from a valid row and never given to mma: the
+        //    wave-uniform test in front of each mma below, and the loop condition for u = 0, keep it out of every sum): with
         //    branches hipcc can no longer count the loads in flight and waits for ALL of them -- s_waitcnt vmcnt(0) --
         //    at the top of every iteration, one exposed L2 latency per iteration;
         //  * the empty asm statements keep each fetch where it is written: left alone, hipcc rotates the loop so that
@@ -1194,6 +1236,10 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
                   psync<NW>();
                   convert();
                   psync<NW>();
+                  if constexpr (TRIM) {                                      // behind the 0..3 left-over entries: stale candidates
+                    stage_pad(cnt, nuse + kPad, __double_as_longlong(stg[0]));
+                    psync<NW>();
+                  }
                   run_steps(nuse);
                   psync<NW>();
                   // the 0..3 left-over entries (already converted) move to the front
@@ -1217,6 +1263,12 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
           psync<NW>();
           convert();
           const int nsp = (cnt + 3) & ~3;
+          if constexpr (TRIM) {                                              // pad the last step and what the fetches reach behind it
+            if (cnt > 0) {                                                   // (wave-uniform; entry 0 is in final form)
+              psync<NW>();
+              stage_pad(cnt, nsp + kPad, __double_as_longlong(stg[0]));
+            }
+          } else
           if (wlane < nsp - cnt) {                                           // pad the last step with weight-0 rows
             *reinterpret_cast<double2*>(&stg[4 * (cnt + wlane)]) = double2{0.0, 0.0};
             *reinterpret_cast<double2*>(&stg[4 * (cnt + wlane) + 2]) = double2{0.0, 0.0};
@@ -1267,13 +1319,19 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
             }
           }
         }
+        // TRIM: the row base of the batch's first entry (lane 0 of pass 0; ns > 0) for every padding entry
+        long rb0 = 0;
+        if constexpr (TRIM) {
+          rb0 = mode0 ? (long)uniform(iob[0]) * A.kld : pt * (long)A.nobs * (long)k + s0;
+          stage_pad(nsp, nsp + kPad, rb0);
+        }
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
           const int i = ps * NL + lane;
           if (i < nsp) {
             // sqrt(w) with w = 1/rdiag (or rloc/rdiag): one rsqrt + Newton instead of an IEEE division and sqrt
             double sw = 0.0;
-            long rb = 0;
+            long rb = rb0;
             if (i < ns) {
               sw = fast_rsqrt(rdv[ps]);
               if (!mode0 && !A.rdiag_wloc) sw *= sqrt(rlv[ps]);
@@ -1300,6 +1358,16 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
       [[maybe_unused]] int ln = lane;                          // (laundered: what is built from it is built per point, not fetched)
       if constexpr (NW == 1) asm volatile("" : "+v"(ln));
       if constexpr (STRIP) {                                   // the narrow block's sums over the four observation residues q
+        if constexpr (TRIM) {
+          // the block went into the sums unmasked: a broadcast member at or past k (wave-uniform; none below the smallest k of
+          // the instantiation) leaves zeros, as its masked lane did
+#pragma unroll
+          for (int a = 0; a < RS; ++a)
+            if (16 * (NBLK - 1) + a >= KMIN && 16 * (NBLK - 1) + a >= k) {
+#pragma unroll
+              for (int I = 0; I < NBLK; ++I) accS[a][I] = 0.0;
+            }
+        }
 #pragma unroll
         for (int a = 0; a < RS; ++a)
 #pragma unroll
@@ -1324,6 +1392,10 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : 128, wave_occupancy(KR, NW)) l
             racc = accD[I];
             rdacc = accDD[I];
           }
+        if constexpr (TRIM) {                                  // (the narrow block's lanes at and past k: member 0's sums)
+          racc = ln < k ? racc : 0.0;
+          rdacc = ln < k ? rdacc : 0.0;
+        }
         p1 = accP;                                             // A_aug[k][k] = sum w dep^2
       }
 #pragma unroll
@@ -2013,6 +2085,7 @@ template <int KR, int NV, bool KKOUT, int NW, int FUSED = 0>
 static hipError_t launch_wave(const PointArgs& a, int num_cu, hipStream_t st) {
   const size_t lds = (size_t)(NW == 1 ? 4 : 1) * wave_slice_doubles(KR, NV, NW) * sizeof(double);
   if (a.k < wave_kmin(KR, NW) || a.k > KR) return hipErrorInvalidValue;   // the Gram assumes its full member blocks
+  if (NV > 0 && a.mode == 1) return hipErrorInvalidValue;                 // ... and, with variables to analyse, rows of the obs table
   if (hipError_t e = lds_opt_in(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, lds)) return e;
   // (the PROF twin's static dealing launches the shape's unclamped grid and needs no occupancy)
   const int occ = a.sched ? resident_blocks(&letkf_wave_kernel<KR, NV, KKOUT, NW, FUSED>, NW == 1 ? 256 : 128, lds, NW == 1 ? 2 : 1) : 0;
